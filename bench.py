@@ -1,20 +1,30 @@
 """GIM episodes/s on MI355X: one "step" = one training iteration of the hot path on one episode batch
 (generator step + discriminator step, both Adam updates; training/gim_img_training.py:225-239) over synthetic
-inputs already resident in HBM.
+inputs already resident in HBM, every step from the same seeded, numerically conditioned initial weights (restored after
+each step; see conditioned_state and step() in main).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload vox64|om32|vox128] [--batch B] [--no-cpu-baseline] ...
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload vox64|om32|vox128] [--batch B] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-kernel-bench] [--no-traffic]] ...
 
 ``--gpus N`` with N > 1 launches itself: when WORLD_SIZE is not set the script starts N child processes (one rank per
 GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT in their environment), relays rank 0's JSON line
 and exits with the worst return code.  Under ``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`` it
 uses the environment it is given.
 
-Prints ONE JSON line on rank 0 (contract in the task statement): whole-job episodes/s; the MFMA roofline of the step -
-the ALGORITHMIC figure of SURVEY.md 8(d) (FLOPs of the unfused reference ops) and, beside it, the EXECUTED figure (the pool /
-sub-pixel folds run 16/36 resp. 100/324 of a 3x3 / 9x9 convolution's taps: that one is the matrix-pipe utilisation); the
-dominant convolution's own roofline from a HIP-event microbenchmark through the C ABI; HBM traffic per step from rocprofv3
-PMC passes of this same command; the CPU baseline (the oracle, a port of the reference's path, timed on the host cores on
-a bounded sample).
+Prints ONE JSON line on rank 0 (contract in the task statement): whole-job episodes/s over exactly K timed steps after W
+warm-up steps, ms_per_step, the ALGORITHMIC MFMA roofline figure of SURVEY.md 8(d) (FLOPs of the unfused reference ops,
+arithmetic only).  A plain run does nothing else.  ``--full`` adds what takes work of its own: the start-up spin test of the
+engine's streams; the EXECUTED roofline figure (one extra counted step after the timed region: the pool / sub-pixel folds run
+16/36 resp. 100/324 of a 3x3 / 9x9 convolution's taps: that one is the matrix-pipe utilisation); the dominant convolution's
+own roofline from a HIP-event microbenchmark through the C ABI; HBM traffic per step from rocprofv3 PMC passes of this same
+command; the CPU baseline (the oracle, a port of the reference's path, timed on the host cores on a bounded sample).
+
+``--dump-outputs DIR`` writes what the last timed step returned to its caller (gim_step's generator and discriminator
+tuples, rank 0) as DIR/<name>.npy in float32, before anything of ``--full`` runs.  Inputs, initial weights and latents are
+seeded, and every step trains from the same initial weights (see step() in main), so two runs with the same arguments
+compute the same outputs up to the rounding of one step: the engine's default path sums some partial results with float
+atomics in an order that varies from run to run.  Under GIM_DETERMINISTIC=1 (config.deterministic in the JSON line) they are
+bit-identical.
 """
 import argparse
 import csv
@@ -74,10 +84,44 @@ def synthetic_batch(B, m, n, k, C, S, device, seed):
     return mk(m), mk(n), mk(k)
 
 
+_IN_MARKERS = (".in1.", ".in2.", "in_layers.")   # instance-norm affine entries (state-dict key names)
+
+
+def conditioned_state(module, seed):
+    """A seeded, numerically conditioned state for `module`: the rules of oracle/portable_fill.fill_value (the weights of the
+    parity tests) drawn from torch's CPU generator.  From default init the generator network amplifies rounding noise
+    (instance norm of near-constant maps, DESIGN.md "Conditioning"), so two runs whose float-atomic sums round differently
+    would return visibly different images; from this state they agree to rounding.  Shapes and work are unchanged."""
+    g = torch.Generator().manual_seed(seed)
+    out = {}
+    for key, t in module.state_dict().items():
+        u = torch.rand(t.shape, generator=g) * 2 - 1
+        is_in = any(mk in "." + key for mk in _IN_MARKERS)
+        if key.endswith(("weight_u", "weight_v")):
+            out[key] = u / u.norm()
+        elif key.endswith("gamma"):
+            out[key] = 0.1 * (1 + u.abs())
+        elif is_in and key.endswith("weight"):
+            out[key] = 1 + 0.3 * u
+        elif is_in and key.endswith("bias"):
+            out[key] = 0.3 * u
+        elif key.endswith("bias"):
+            out[key] = 0.1 * u
+        elif key.endswith(("weight_orig", "weight")):
+            fan_in = int(torch.tensor(t.shape[1:]).prod()) if t.dim() > 1 else t.shape[0]
+            out[key] = (3.0 / fan_in) ** 0.5 * 1.4 * u
+        else:
+            raise KeyError("no conditioning rule for %s" % key)
+    return out
+
+
 def build_trainer(S, C, n, m, k, device, style_dim=512, reg_param=0.0):
     import optimalstrategiesagainstgenerativeattacks_amd as G
     torch.manual_seed(1)  # train_gim_on_imgs.py:6
-    au, im = G.get_au(S, C, style_dim).to(device), G.get_im(S, C, style_dim).to(device)
+    au, im = G.get_au(S, C, style_dim), G.get_im(S, C, style_dim)
+    au.load_state_dict(conditioned_state(au, 11))
+    im.load_state_dict(conditioned_state(im, 12))
+    au, im = au.to(device), im.to(device)
     with tempfile.TemporaryDirectory() as td:
         tr = G.GIMImgTrainer(td, m, n, k, au, im, au_lr=1e-4, im_lr=1e-4, env_noise_mapping_lr=1e-6, beta1=0.0, beta2=0.99,
                              reg_param=reg_param)
@@ -217,6 +261,39 @@ def dominant_kernel_roofline(per, device):
             "algorithmic_gflop_per_launch": round(ops.conv_algorithmic_flops(*cfg) / 1e9, 2), **out}
 
 
+# what gim_step returns, in its order: (generator tuple, discriminator tuple)
+OUTPUT_NAMES = (("g_loss", "g_fake_sample", "g_au_out"),
+                ("d_loss", "d_loss_on_real", "d_loss_on_fake", "d_reg", "d_out_on_real", "d_out_on_fake", "d_pred_on_real",
+                 "d_pred_on_fake", "d_fake_out"))
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out, d):
+    """The last step's returned tensors -> d/<name>.npy (float32).  Within DUMP_BUDGET_BYTES in all: an array larger than its
+    share of what is left is replaced by a fixed sample of its flattened elements (sorted indices, numpy seed 0)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrs = {}
+    for names, tup in zip(OUTPUT_NAMES, out):
+        assert len(names) == len(tup), (names, len(tup))
+        for name, t in zip(names, tup):
+            arrs[name] = t.detach().float().cpu().numpy()
+    left, todo = DUMP_BUDGET_BYTES, sorted(arrs, key=lambda n_: arrs[n_].size)
+    for i, name in enumerate(todo):
+        a = arrs[name]
+        cap = left // (len(todo) - i) // 4
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))
+            log("dump: %s %s sampled to %d of %d elements" % (name, a.shape, cap, a.size))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), np.asarray(a, dtype=np.float32))
+        left -= a.size * 4
+    log("dump: %d arrays, %.1f MB in %s" % (len(todo), (DUMP_BUDGET_BYTES - left) / 1e6, d))
+    from optimalstrategiesagainstgenerativeattacks_amd import ops
+    if not ops.deterministic():
+        log("dump: default mode - reproducible up to rounding (float atomics); GIM_DETERMINISTIC=1 for bit-identical outputs")
+
+
 def cpu_baseline(workload, m, n, k, sample_B):
     """The oracle (CPU port of the reference's path, parity-pinned by tests/golden) on a bounded sample: steps of `sample_B`
     episodes (the GPU's own batch where one such step fits the ~10-30 s budget) after a small warm-up step."""
@@ -275,9 +352,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="vox64", choices=sorted(UNIT))
     ap.add_argument("--batch", type=int, default=0, help="episodes per GPU (default: 16 for vox64, 32 for om32, 2 for vox128)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-bench", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 PMC passes (roofline.traffic = null)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the stream self-check, the executed roofline (one extra counted step), the dominant kernel's microbenchmark, "
+                         "HBM traffic (two rocprofv3 PMC passes) and the CPU baseline; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's returned tensors (rank 0) as DIR/<name>.npy, float32, <= 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baseline")
+    ap.add_argument("--no-kernel-bench", action="store_true", help="(with --full) skip the dominant kernel's microbenchmark")
+    ap.add_argument("--no-traffic", action="store_true", help="(with --full) skip the two rocprofv3 PMC passes (roofline.traffic = null)")
     ap.add_argument("--no-bf16x3", action="store_true", help="accepted and ignored (round-2 scripts): the bf16x3 matrix path was removed in round 3")
     ap.add_argument("--reg-param", type=float, default=0.0, help="R1 weight (BASELINE's metric is quoted at 0; 10 = the paper's VoxCeleb2 setting)")
     ap.add_argument("--matrix-path", default="fp32", choices=["fp32", "fp16"],
@@ -286,6 +368,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="rendezvous only: argument parsing, process group, one all-reduce, JSON line")
     ap.add_argument("--inner", action="store_true", help="(used by the traffic passes) run the steps and print nothing else")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     u = UNIT[args.workload]
     m, n, k = u.get("mnk", (1, 5, 10))
     args.batch = args.batch or u.get("batch", 16 if args.workload == "vox64" else 32)
@@ -320,7 +404,7 @@ def main():
 
     # HBM traffic first: the profiled runs are child processes and this process has not touched the GPU yet
     traffic, traffic_note = None, "not measured"
-    if world == 1 and not (args.no_traffic or args.inner or os.environ.get("GIM_BENCH_NO_TRAFFIC")):
+    if args.full and world == 1 and not (args.no_traffic or args.inner or os.environ.get("GIM_BENCH_NO_TRAFFIC")):
         traffic, traffic_note = measure_hbm_traffic(args)
         log("HBM traffic: %s" % (traffic["hbm_bytes_per_step"] if traffic else traffic_note))
 
@@ -342,14 +426,40 @@ def main():
     zgen = torch.Generator(device=device).manual_seed(4321 + rank)
 
     # do the engine's streams run concurrently here (one hardware queue each)?  warns loudly when they do not
-    streams_check = G.stream_concurrency_check(device)
-    log("stream self-check: %s" % streams_check)
+    streams_check = None
+    if args.full:
+        streams_check = G.stream_concurrency_check(device)
+        log("stream self-check: %s" % streams_check)
+
+    # Every step trains from the same weights: at the end of each step the networks' parameters and buffers go back to their
+    # values before the first one.  A step is then a function of the seeded inputs alone (episode batch, initial weights, its own
+    # z), reproducible from run to run up to rounding.  Along a training trajectory it is not: the default path's float atomics
+    # (split-K and weight-gradient sums, in an order that varies from run to run) leave last-bit differences that a few dozen
+    # GAN / Adam updates grow to O(1).  The work of a step is unchanged but for one copy of the weights: the generator's on the
+    # caller's stream behind its Adam update, the discriminator's on lane 1 behind its own (joined where its weights are read next).
+    from optimalstrategiesagainstgenerativeattacks_amd import ops as _ops
+    from optimalstrategiesagainstgenerativeattacks_amd.gim_img_models import lane_stream
+    dstream = lane_stream(device, 1)
+    g_state = list(tr.impersonator.parameters()) + list(tr.impersonator.buffers())
+    d_state = list(tr.authenticator.parameters()) + list(tr.authenticator.buffers())
+    g_init, d_init = [t.detach().clone() for t in g_state], [t.detach().clone() for t in d_state]
+
+    def restore_weights():
+        with torch.no_grad():
+            cur = torch.cuda.current_stream()
+            torch._foreach_copy_(g_state, g_init)     # in place: bumps the version counters the folded-weight caches key on
+            _ops.stream_wait(dstream, cur)
+            with torch.cuda.stream(dstream):
+                torch._foreach_copy_(d_state, d_init)
+        _ops.defer_join(dstream)
 
     def step():
         z = torch.randn((B, n, 512), device=device, generator=zgen)
         tr.do_global_step()
         tr.update_learning_rate()
-        return G.gim_step(trainer, leaked, real, si, z=z, defer_join=True)   # joined by the next step / the final synchronize
+        out = G.gim_step(trainer, leaked, real, si, z=z, defer_join=True)   # joined by the next step / the final synchronize
+        restore_weights()
+        return out
 
     def fence():
         torch.cuda.synchronize()
@@ -359,7 +469,6 @@ def main():
 
     import warnings
     warnings.filterwarnings("ignore")
-    from optimalstrategiesagainstgenerativeattacks_amd import ops as _ops
     _ops.set_matrix_path(args.matrix_path)
 
     def timed(label):
@@ -420,23 +529,27 @@ def main():
         fence()
         return
 
-    log("models built; counting the executed work of one step")
-    with _ops.count_flops() as counts:   # one extra (un-timed) step with the per-launch accounting switched on
-        step()
-        _ops.join_lanes()
-        torch.cuda.synchronize()
-    exe_gf, algo_launch_gf, per_conv = summarize_flops(counts, _ops)
-
+    log("models built")
     matrix_path = "fp32 MFMA" if args.matrix_path == "fp32" else "fp16 operands / fp32 accumulate on eligible convolutions (v_mfma_f32_32x32x16_f16), fp32 MFMA elsewhere"
     dt, dev_ms, per_step, out, allreduce_ms, ranks_dt, host_ms = timed(matrix_path)
     g_loss, d_loss = float(out[0][0]), float(out[1][0])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
+
+    if args.full:
+        # after the timed region and the dump, so that both see the same training state as a plain run
+        log("counting the executed work of one step")
+        with _ops.count_flops() as counts:   # one extra (un-timed) step with the per-launch accounting switched on
+            step()
+            _ops.join_lanes()
+            torch.cuda.synchronize()
+        exe_gf, algo_launch_gf, per_conv = summarize_flops(counts, _ops)
 
     if rank == 0:
         eps = B * world * args.steps / dt
         med = sorted(per_step)[len(per_step) // 2] if len(per_step) % 2 else 0.5 * sum(sorted(per_step)[len(per_step) // 2 - 1:len(per_step) // 2 + 1])
         algo = algo_gflop_per_episode(args.workload, m, n, k)
         achieved = eps * algo / 1e3 / world            # ALGORITHMIC TFLOP/s per GPU (SURVEY.md 8(d) convention)
-        executed = exe_gf / 1e3 / (dt / args.steps)     # EXECUTED TFLOP/s per GPU (this rank's launches)
         PEAK = PEAK_FP32_MFMA_TFLOPS if args.matrix_path == "fp32" else PEAK_FP16_MFMA_TFLOPS
         line = {
             "metric": "GIM episodes/sec (%dx%dx%d, m=%d n=%d k=%d)" % (u["S"], u["S"], u["C"], m, n, k),
@@ -460,28 +573,35 @@ def main():
                                    "G step + D step + 2 Adam updates per step, reg_param=%g" % (args.workload, u["S"], u["S"], u["C"], m, n, k, B, args.reg_param),
                        "global_batch": B * world, "parallelism": "dp%d (episodes sharded, 1 RCCL all-reduce per optimizer step)" % world,
                        "backend": dist.get_backend() if dist.is_initialized() else None,
-                       "launch": "eager", "matrix_path": matrix_path},
-            "roofline": {"bound": "mfma", "achieved": round(executed, 3), "peak": PEAK, "unit": "TFLOP/s",
-                         "frac": round(executed / PEAK, 4),
-                         "what": "achieved / frac: FLOPs the kernels EXECUTE per second (every conv / linear / batched-GEMM launch of one step "
-                                 "counted per launch; the pool / sub-pixel folds run (K+1)^2 taps at a quarter of the pixels) over the fp32 MFMA "
-                                 "peak = the matrix-pipe utilisation of the step (<= 1 by construction).  algo_tflops / algo_frac: the "
-                                 "ALGORITHMIC figure of SURVEY.md 8(d) (the unfused reference ops at full resolution) - it counts taps the "
-                                 "folded kernels never execute and can exceed 1; it is not a utilisation",
+                       "launch": "eager", "matrix_path": matrix_path, "deterministic": _ops.deterministic()},
+            # a plain run: the ALGORITHMIC figure only (arithmetic on the step time); --full adds the EXECUTED one and the traffic
+            "roofline": {"bound": "mfma", "peak": PEAK, "unit": "TFLOP/s",
+                         "what": "algo_tflops / algo_frac: the ALGORITHMIC figure of SURVEY.md 8(d) (the unfused reference ops at full "
+                                 "resolution) - it counts taps the folded kernels never execute and can exceed 1; it is not a utilisation.  "
+                                 "achieved / frac / executed_* (--full only): FLOPs the kernels EXECUTE per second",
                          "algo_gflop_per_episode": round(algo, 1), "algo_gflop_per_step": round(algo * B, 1),
                          "algo_tflops": round(achieved, 3), "algo_frac": round(achieved / PEAK, 4),
-                         "executed_gflop_per_step": round(exe_gf, 1), "executed_tflops": round(executed, 3),
-                         "executed_frac": round(executed / PEAK, 4),
-                         "launched_ops_at_full_resolution_gflop_per_step": round(algo_launch_gf, 1),
-                         "traffic": traffic["hbm_bytes_per_step"] if traffic else None,
-                         "traffic_unit": "HBM bytes/step", "traffic_detail": traffic if traffic else traffic_note,
                          "device_ms_per_step": round(dev_ms / args.steps, 3)},
             "final_losses": {"g": round(g_loss, 5), "d": round(d_loss, 5)},
         }
-        if not args.no_kernel_bench:
+        if args.full:
+            executed = exe_gf / 1e3 / (dt / args.steps)     # EXECUTED TFLOP/s per GPU (this rank's launches)
+            line["roofline"].update({
+                "achieved": round(executed, 3), "frac": round(executed / PEAK, 4),
+                "what": "achieved / frac: FLOPs the kernels EXECUTE per second (every conv / linear / batched-GEMM launch of one step "
+                        "counted per launch; the pool / sub-pixel folds run (K+1)^2 taps at a quarter of the pixels) over the fp32 MFMA "
+                        "peak = the matrix-pipe utilisation of the step (<= 1 by construction).  algo_tflops / algo_frac: the "
+                        "ALGORITHMIC figure of SURVEY.md 8(d) (the unfused reference ops at full resolution) - it counts taps the "
+                        "folded kernels never execute and can exceed 1; it is not a utilisation",
+                "executed_gflop_per_step": round(exe_gf, 1), "executed_tflops": round(executed, 3),
+                "executed_frac": round(executed / PEAK, 4),
+                "launched_ops_at_full_resolution_gflop_per_step": round(algo_launch_gf, 1),
+                "traffic": traffic["hbm_bytes_per_step"] if traffic else None,
+                "traffic_unit": "HBM bytes/step", "traffic_detail": traffic if traffic else traffic_note})
+        if args.full and not args.no_kernel_bench:
             line["dominant_kernel"] = dominant_kernel_roofline(per_conv, device)
             log("kernel microbenchmark done")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.workload, m, n, k, sample_B=B)
             log("cpu baseline done")
             line["cpu_baseline"]["gpu_over_cpu"] = round(eps / line["cpu_baseline"]["value"], 1)

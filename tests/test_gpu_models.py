@@ -1228,7 +1228,7 @@ def test_bench_two_ranks_non_dry_on_one_card():
     env = {k_: v for k_, v in os.environ.items() if k_ not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(GIM_BENCH_BACKEND="gloo", GIM_BENCH_ONE_DEVICE="1")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4",
-                        "--no-cpu-baseline", "--no-kernel-bench", "--no-traffic"],
+                        "--full", "--no-cpu-baseline", "--no-kernel-bench", "--no-traffic"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1252,3 +1252,89 @@ def test_bench_two_ranks_non_dry_on_one_card():
     assert sc["streams"] >= 3 and sc["one_ms"] > 0.2 and sc["all_ms"] >= 0.9 * sc["one_ms"] and isinstance(sc["concurrent"], bool)
     if line["cpu_affinity"] is not None:     # two ranks, disjoint halves of this process's cores
         assert len(line["cpu_affinity"]) >= 2 and len(line["cpu_affinity"]) <= len(os.sched_getaffinity(0)) // 2
+
+
+def test_bench_plain_run_dumps_last_step_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps, prints ONE JSON line without the --full extras, and
+    --dump-outputs writes the last timed step's returned tensors (float32 .npy, the names of bench.OUTPUT_NAMES)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k_: v for k_, v in os.environ.items() if k_ not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4",
+                        "--dump-outputs", str(d)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and len(line["per_step_ms"]) == 3
+    assert line["unit"] == "episodes/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["ms_per_step"] > 0 and abs(line["value"] - 4 / (line["ms_per_step"] * 1e-3)) < 1e-2 * line["value"]
+    assert "dominant_kernel" not in line and "cpu_baseline" not in line and "executed_frac" not in line["roofline"]
+    assert line["hw_queues"]["streams_check"] is None
+    names = ["g_loss", "g_fake_sample", "g_au_out", "d_loss", "d_loss_on_real", "d_loss_on_fake", "d_reg", "d_out_on_real",
+             "d_out_on_fake", "d_pred_on_real", "d_pred_on_fake", "d_fake_out"]
+    assert sorted(p.name for p in d.iterdir()) == sorted(n_ + ".npy" for n_ in names)
+    arrs = {n_: np.load(d / (n_ + ".npy")) for n_ in names}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+    assert arrs["g_fake_sample"].shape == (4, 5, 3, 64, 64)
+    assert abs(float(arrs["g_loss"]) - line["final_losses"]["g"]) <= 1e-5 * max(1.0, abs(line["final_losses"]["g"]))
+    assert abs(float(arrs["d_loss"]) - line["final_losses"]["d"]) <= 1e-5 * max(1.0, abs(line["final_losses"]["d"]))
+
+
+def test_bench_dumps_are_bit_reproducible_in_deterministic_mode(tmp_path):
+    """Two plain `bench.py --dump-outputs` runs with the same arguments under GIM_DETERMINISTIC=1 write bit-identical arrays: the
+    inputs, initial weights and latents are seeded, and the switch fixes the order of every sum (the default path's float atomics
+    do not; see test_deterministic_mode_is_bit_reproducible)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k_: v for k_, v in os.environ.items() if k_ not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["GIM_DETERMINISTIC"] = "1"
+    dirs = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4",
+                            "--dump-outputs", str(d)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert line["config"]["deterministic"] is True and line["steps"] == 2
+        dirs.append(d)
+    files = sorted(p.name for p in dirs[0].iterdir())
+    assert len(files) == 12 and files == sorted(p.name for p in dirs[1].iterdir())
+    diff = [f for f in files if not np.array_equal(np.load(dirs[0] / f), np.load(dirs[1] / f))]
+    assert not diff, "arrays that differ between two deterministic runs: %s" % diff
+
+
+def test_bench_dumps_agree_up_to_rounding_in_default_mode(tmp_path):
+    """Two plain `bench.py --dump-outputs` runs with the same arguments, default (atomic) path: every step trains from the same
+    conditioned initial weights on seeded inputs, so the last step's outputs differ only by the rounding of one step's
+    float-atomic sums - not by a training trajectory that amplifies those last bits (what the run-to-run spread of
+    profiles/r03_g_* grows into), nor by the default init's instance norms on near-constant maps (DESIGN.md "Conditioning")."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k_: v for k_, v in os.environ.items() if k_ not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT",
+                                                                "GIM_DETERMINISTIC")}
+    dirs = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--batch", "4",
+                            "--dump-outputs", str(d)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert line["config"]["deterministic"] is False
+        dirs.append(d)
+    files = sorted(p.name for p in dirs[0].iterdir())
+    assert len(files) == 12 and files == sorted(p.name for p in dirs[1].iterdir())
+    bad = {}
+    for f in files:
+        a, b = np.load(dirs[0] / f).astype(np.float64), np.load(dirs[1] / f).astype(np.float64)
+        err = float(np.abs(a - b).max())
+        if err > 1e-4 * float(np.abs(a).max()) + 1e-6:
+            bad[f] = (err, float(np.abs(a).max()))
+    assert not bad, "outputs that differ by more than rounding between two runs (max error, max |value|): %s" % bad

@@ -285,6 +285,40 @@ def test_bench_self_launch_dry_run_gloo_world2():
     assert bad.returncode != 0 and "WORLD_SIZE=1 but --gpus 2" in bad.stderr
 
 
+def test_bench_dump_outputs_names_dtype_and_budget(tmp_path):
+    """bench.dump_outputs: one float32 .npy per returned tensor, named after gim_step's tuples; an output larger than its share
+    of the byte budget is replaced by the same seeded sample of its elements on every call.  (A child process: importing
+    bench sets GPU_MAX_HW_QUEUES in its environment.)"""
+    import subprocess
+    import numpy as np
+    code = (
+        "import sys, torch; sys.path.insert(0, %r); import bench\n"
+        "bench.DUMP_BUDGET_BYTES = 1 << 16\n"
+        "g = torch.Generator().manual_seed(0)\n"
+        "big = torch.rand(4, 5, 3, 32, 32, generator=g, dtype=torch.float64)\n"
+        "im = (torch.tensor(1.5), big, torch.rand(4, 5, generator=g))\n"
+        "au = tuple(torch.tensor(float(i)) for i in range(6)) + (torch.rand(4, 5) > 0.5, torch.rand(4, 5) > 0.5, torch.rand(4, 5))\n"
+        "bench.dump_outputs((im, au), sys.argv[1]); bench.dump_outputs((im, au), sys.argv[2])\n"
+        "torch.save(big, sys.argv[3])\n" % ROOT)
+    a, b, big = str(tmp_path / "a"), str(tmp_path / "b"), str(tmp_path / "big.pt")
+    r = subprocess.run([sys.executable, "-c", code, a, b, big], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    files = sorted(os.listdir(a))
+    assert files == sorted(n_ + ".npy" for n_ in ("g_loss", "g_fake_sample", "g_au_out", "d_loss", "d_loss_on_real", "d_loss_on_fake",
+                                                   "d_reg", "d_out_on_real", "d_out_on_fake", "d_pred_on_real", "d_pred_on_fake",
+                                                   "d_fake_out")), files
+    total = 0
+    for f in files:
+        x, y = np.load(os.path.join(a, f)), np.load(os.path.join(b, f))
+        assert x.dtype == np.float32 and np.array_equal(x, y), f
+        total += x.nbytes
+    assert total <= 1 << 16
+    assert np.load(os.path.join(a, "g_loss.npy")).shape == () and float(np.load(os.path.join(a, "g_loss.npy"))) == 1.5 and np.load(os.path.join(a, "g_au_out.npy")).shape == (4, 5)
+    s = np.load(os.path.join(a, "g_fake_sample.npy"))
+    full = torch.load(big).numpy().astype(np.float32).reshape(-1)
+    assert s.ndim == 1 and 0 < s.size < full.size and np.isin(s, full).all()     # a sample of the real elements, not a summary
+
+
 def test_conv_shape_struct_matches_the_header():
     """The ctypes mirror of gim_conv_shape has the header's fields in the header's order (matrix path and launch overrides are
     per-call fields: the library has no precision / tuning globals)."""

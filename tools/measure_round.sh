@@ -12,9 +12,9 @@ cd $R
 timeout -k 10 900 python -m pytest tests -m gpu -q > $out/pytest_gpu.log 2>&1; rc=$?
 echo "pytest rc=$rc: $(grep -E 'passed|failed' $out/pytest_gpu.log | tail -1)"; grep -E "^FAILED|^ERROR" $out/pytest_gpu.log | head
 [ $rc -ge 124 ] && exit $rc
-timeout -k 10 600 python bench.py > $out/bench_vox64_B16.log 2> $out/bench_vox64_B16.err || exit 1
+timeout -k 10 600 python bench.py --full > $out/bench_vox64_B16.log 2> $out/bench_vox64_B16.err || exit 1
 echo "bench: $(grep -o '"value": [0-9.]*, "unit"' $out/bench_vox64_B16.log | head -1) $(grep -o '"executed_frac": [0-9.]*' $out/bench_vox64_B16.log)"
-Q="--no-cpu-baseline --no-kernel-bench --no-traffic"
+Q="--full --no-cpu-baseline --no-kernel-bench --no-traffic"
 timeout -k 10 300 python bench.py --workload om32 $Q > $out/bench_om32_B32.log 2>&1 || exit 1
 timeout -k 10 300 python bench.py --batch 64 $Q > $out/bench_vox64_B64.log 2>&1 || exit 1
 timeout -k 10 300 python bench.py --reg-param 10 $Q > $out/bench_vox64_B16_r1.log 2>&1 || exit 1
