@@ -514,13 +514,17 @@ BENCH_BATCH_GRADS = {   # one tensor per conv kind (oracle/make_golden.py BENCH_
 }
 
 
-@pytest.mark.parametrize("cfg,B", [("64_3_512", 16), ("32_1_512", 32)])
-def test_gim_step_at_benchmark_batch_vs_oracle(cfg, B):
+@pytest.mark.parametrize("cfg,B,reg_param", [pytest.param("64_3_512", 16, 0.0, id="64_3_512-16"), pytest.param("32_1_512", 32, 0.0, id="32_1_512-32"),
+                                              pytest.param("64_3_512", 16, 10.0, id="64_3_512-16-r1")])
+def test_gim_step_at_benchmark_batch_vs_oracle(cfg, B, reg_param):
     """What bench.py times is one gim_step on 16 episodes of 64x64x3 (BASELINE config 3; 32 episodes of 32x32x1 for config 2);
     every other whole-network fixture is B = 1-2.  Here the SAME call at the SAME batch - m1 n5 k10, style 512, conditioned
     fill, the path's learning rates - is checked against the fp64 oracle's step on the box's host threads
     (training/gim_img_training.py:157-183): per-episode generator loss, logits, fake images, discriminator losses / logits at
-    1e-3 (north_star), ten whole gradient tensors (one per conv kind), and every parameter after the two Adam updates."""
+    1e-3 (north_star), ten whole gradient tensors (one per conv kind), and every parameter after the two Adam updates.
+    reg_param = 10: the R1 step exactly as `bench.py --reg-param 10` runs it (80 / 160 images per encoder pass: position-major rows,
+    tuned table rows, lanes and side streams, the queued weight-gradient arena adding the R1 gradients on top of the first-order ones);
+    the R1 value is checked too (the oracle's CPU side: ~2 min at 16 threads)."""
     import optimalstrategiesagainstgenerativeattacks_amd as G
     import tempfile
     s, c, d = map(int, cfg.split("_"))
@@ -529,12 +533,13 @@ def test_gim_step_at_benchmark_batch_vs_oracle(cfg, B):
     keys = load_keys(cfg)
     lrs = {"au": 1e-4, "im": 1e-4}
     torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))
-    otr = go.OracleTrainer(filled_sd(keys["au"], tag + "/au/"), filled_sd(keys["im"], tag + "/im/"), n, lrs["au"], lrs["im"], 1e-6)
+    otr = go.OracleTrainer(filled_sd(keys["au"], tag + "/au/"), filled_sd(keys["im"], tag + "/im/"), n, lrs["au"], lrs["im"], 1e-6,
+                           reg_param=reg_param)
     leaked, real, si, z = episode(tag, B, m, n, k, c, s, d)
     g_o, d_o = otr.step(leaked, real, si, z)
     au, im = _product_models(tag, cfg)
     with tempfile.TemporaryDirectory() as td:
-        tr = G.GIMImgTrainer(td, m, n, k, au, im, lrs["au"], lrs["im"], 1e-6, reg_param=0.0)
+        tr = G.GIMImgTrainer(td, m, n, k, au, im, lrs["au"], lrs["im"], 1e-6, reg_param=reg_param)
     gi, di = G.gim_step(G.DataParallelMock(tr), *[t.float().to(dev()) for t in (leaked, real, si)], z=z.float().to(dev()))
     torch.cuda.synchronize()
     assert relerr(gi[0], g_o[0].mean()) < 1e-3, "generator loss"
@@ -543,6 +548,9 @@ def test_gim_step_at_benchmark_batch_vs_oracle(cfg, B):
     assert relerr(di[0], d_o[0].mean()) < 1e-3 and relerr(di[1], d_o[1].mean()) < 1e-3 and relerr(di[2], d_o[2].mean()) < 1e-3
     assert relerr(di[4], d_o[4].mean()) < 1e-3 and relerr(di[5], d_o[5].mean()) < 1e-3
     assert (di[6].cpu() == d_o[6]).all() and (di[7].cpu() == d_o[7]).all(), "predictions"
+    if reg_param > 0:
+        assert float(d_o[3].min()) > 0 and float(di[3]) > 0, "R1 value"
+        assert relerr(di[3], d_o[3].mean()) < 1e-3, "R1 value (mean over the episodes)"
     last = len(au.src_encoder.down_blocks) - 1
     rows = []
     for nm, mod, sd_o, tol in (("im", im, otr.im_sd, 3e-3), ("au", au, otr.au_sd, 1e-3)):   # (G-step tolerance: see _check_nets)
@@ -636,20 +644,30 @@ def test_gaussian_caller_loop_vs_reference_golden(tmp_path):
             assert relerr(v, g["final/im/" + kk]) < 1e-3, kk
 
 
-@pytest.mark.parametrize("cfg", ["16_1_32", "32_1_512", "64_3_512"])
-def test_r1_double_backward_vs_oracle(cfg):
+@pytest.mark.parametrize("cfg,bench", [pytest.param("16_1_32", False, id="16_1_32"), pytest.param("32_1_512", False, id="32_1_512"),
+                                       pytest.param("64_3_512", False, id="64_3_512"), pytest.param("64_3_512", True, id="64_3_512-bench")])
+def test_r1_double_backward_vs_oracle(cfg, bench):
     """The R1 term alone (training/utils.py:115-124): per-episode value and the gradient it sends to EVERY
     authenticator parameter (second order through convs, pool folds, attention, max-pool, the set statistics and the
-    spectral-norm chain rule), product fp32 vs oracle fp64 autograd double backward."""
+    spectral-norm chain rule), product fp32 vs oracle fp64 autograd double backward.
+    bench: the benchmark batch (B = 16, m1 n5 k10: 160 / 80 images per encoder pass - position-major rows, tuned table rows) with the
+    optimizer's flat gradient bucket in place, so the R1 weight gradients take the queued arena and the batched finish, as in a
+    training step - isolated from the first-order gradients that test_gim_step_at_benchmark_batch_vs_oracle adds them to
+    (the oracle's CPU side: ~1 min at 16 threads)."""
     import optimalstrategiesagainstgenerativeattacks_amd as G
     from optimalstrategiesagainstgenerativeattacks_amd.training_utils import compute_grad2
     tag = "r1"
     s, c, d = map(int, cfg.split("_"))
-    B, m, n, k = (1, 1, 2, 3) if s == 64 else (2, 1, 3, 4)
+    B, m, n, k = (16, 1, 5, 10) if bench else ((1, 1, 2, 3) if s == 64 else (2, 1, 3, 4))
+    if bench:
+        torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))
     keys = load_keys(cfg)
     au_o = filled_sd(keys["au"], tag + "/au/")
     go.set_requires_grad(au_o)
     au, _ = _product_models(tag, cfg)
+    if bench:
+        opt = G.FusedAdam(au.parameters(), lr=1e-4, betas=(0.0, 0.99))
+        opt.zero_grad()      # every .grad is now a view of the flat bucket, zero: the R1 gradients are ADDED there
     _, real, si, _ = episode(tag, B, m, n, k, c, s, d)
     real_o, si_o = real.clone().requires_grad_(), si.clone().requires_grad_()
     out_o = go.authenticator(au_o, real_o, si_o, True)
