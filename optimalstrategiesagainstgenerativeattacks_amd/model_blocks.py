@@ -110,28 +110,28 @@ class SNConv2d(nn.Module):
         self.register_buffer("weight_v", v)
 
         self._sn_queue = collections.deque()  # (sigma, u, v) triples precomputed by an SNPlan round
-        self._fold_cache = (None, None, None, None, False)   # ((storage, version, optimizer epoch), folded weights F, ready event, stream, recorded in a capture)
+        self._fold_cache = None     # ops._DerivedWeights: the folded weights F of weight_orig at version _fold_version()
         self._wants_fold = False    # set by the first folded() call: SNPlan.run then folds this conv together with the others
 
-    def folded(self):
-        """The (k+1)^2-tap folded weights for the pool / sub-pixel forms, recomputed only when weight_orig changed
-        (autograd version counter for torch-side writes, optim.weights_epoch(w) for the fused Adam kernel)."""
+    def _fold_version(self):
+        """What F was made from: weight_orig's storage, autograd version counter (torch-side writes) and optim.weights_epoch (the
+        fused Adam kernel)."""
         from . import optim
         w = self.weight_orig
+        return (w.data_ptr(), w._version, optim.weights_epoch(w))
+
+    def fold_is_stale(self):
+        return self._fold_cache is None or self._fold_cache.version != self._fold_version()
+
+    def folded(self):
+        """The (k+1)^2-tap folded weights for the pool / sub-pixel forms, recomputed only when weight_orig changed; other streams
+        (one per encoder pass) reuse F behind the kernel that wrote it (ops._StreamReady)."""
         self._wants_fold = True
-        key = (w.data_ptr(), w._version, optim.weights_epoch(w))
-        raw = ops._stream()   # raw handle: building a torch Stream object per call costs microseconds of host time
-        if self._fold_cache[0] != key:
+        if self.fold_is_stale():
             with torch.no_grad():
-                f = ops._folded(ops.weight_phys(w), self.out_channels, self.in_channels, self.kernel_size)
-            # other streams (one per encoder pass) reuse F: they wait for the kernel that wrote it
-            self._fold_cache = (key, f, torch.cuda.current_stream().record_event(), raw, torch.cuda.is_current_stream_capturing())
-        elif self._fold_cache[3] != raw:
-            cur = torch.cuda.current_stream()
-            if self._fold_cache[4] or not torch.cuda.is_current_stream_capturing():   # see ops.WgradQueue.take
-                cur.wait_event(self._fold_cache[2])
-            self._fold_cache[1].record_stream(cur)   # F was allocated on another stream: keep its memory until this one is done with it
-        return self._fold_cache[1]
+                f = ops._folded(ops.weight_phys(self.weight_orig), self.out_channels, self.in_channels, self.kernel_size)
+            self._fold_cache = ops._DerivedWeights(f, self._fold_version())
+        return self._fold_cache.use_on_current_stream()
 
     def forward(self, x, res=None, ups=0, pre_slope=1.0, pool=False, res_ups=False, post_slope=1.0, x_act=False, fork_pool_slope=None):
         """post_slope != 1: returns (y, activated) - see ops.conv2d_post_act; x_act: x was stored activated by such a producer.
@@ -242,25 +242,18 @@ class SNPlan:
         """The folded weights (pool / sub-pixel forms) of every conv of the plan whose weights changed since its last fold, in ONE
         launch (each conv would otherwise fold itself at its first use: ~30 launches of ~10 us per training step, on the
         forward's critical path).  Results go where SNConv2d.folded() keeps them."""
-        from . import optim
-        todo = []
-        for c in self.convs:
-            if c._wants_fold:
-                w = c.weight_orig
-                key = (w.data_ptr(), w._version, optim.weights_epoch(w))
-                if c._fold_cache[0] != key:
-                    todo.append((c, key))
+        todo = [c for c in self.convs if c._wants_fold and c.fold_is_stale()]
         if len(todo) < 2:
             return     # a single stale conv folds itself at its call
-        dev = todo[0][0].weight_orig.device
-        sig = tuple(c.weight_orig.data_ptr() for c, _ in todo)
+        dev = todo[0].weight_orig.device
+        sig = tuple(c.weight_orig.data_ptr() for c in todo)
         ent = getattr(self, "_fold_tab", {}).get(sig)
         if ent is None:
             if torch.cuda.is_current_stream_capturing():
                 return
             jobs = np.zeros(len(todo), dtype=np.dtype([("w", "<u8"), ("f", "<u8"), ("Cout", "<i4"), ("Cin", "<i4"), ("KH", "<i4"), ("r", "<i4")]))
             bufs, tab = [], []
-            for j, (c, _) in enumerate(todo):
+            for j, c in enumerate(todo):
                 KF = c.kernel_size + 1
                 n = c.out_channels * KF * KF * c.in_channels
                 if n >= 1 << 31:
@@ -275,10 +268,8 @@ class SNPlan:
             self._fold_tab[sig] = ent
         dj, dt, nb, bufs = ent
         _lib.check(_lib.load().gim_conv2d_fold_weights_batched(dj.data_ptr(), dt.data_ptr(), nb, ops._stream()), "fold_weights_batched")
-        ev = torch.cuda.current_stream().record_event()
-        raw, cap = ops._stream(), torch.cuda.is_current_stream_capturing()
-        for (c, key), f in zip(todo, bufs):
-            c._fold_cache = (key, f, ev, raw, cap)
+        for c, f in zip(todo, bufs):
+            c._fold_cache = ops._DerivedWeights(f, c._fold_version())
 
 
 def sn_convs(*modules):

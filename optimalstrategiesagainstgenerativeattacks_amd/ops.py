@@ -105,22 +105,21 @@ def conv_algorithmic_flops(N, H, W, Cin, Cout, KH, *_):
     return 2.0 * N * H * W * Cin * Cout * KH * KH
 
 
-def _note_conv(kind, cfg, sh=None, plan_kind=None):
+def _note_conv(kind, geom, sh=None, plan_kind=None):
     """Count one conv launch (ops.count_flops).  sh / plan_kind (the launch's gim_conv_shape and its gim_conv_launch_plan kind): the
-    library is asked which share of the launch's K steps its kernel skips (position-major rows on small maps skip padding taps,
-    include/gim_hip.h gim_conv_launch_plan out[7]) - skipped multiply-adds are not executed FLOPs."""
-    N, H, W, Cin, Cout, KH, ups, pre_slope, has_bias, has_res, pool, fold, res_ups = cfg
-    key = (kind, (N, H, W, Cin, Cout, KH, int(ups), int(bool(pool)), int(fold)))
-    ent = _FLOPS.get(key)
+    library is asked which share of the launch's K steps its kernel skips (position-major rows on small maps skip padding taps) -
+    skipped multiply-adds are not executed FLOPs."""
+    ent = _FLOPS.get((kind, geom.key))
     if ent is None:
-        share = 1.0
-        if sh is not None:
-            out = (ctypes.c_int32 * 8)()
-            check(_lib.load().gim_conv_launch_plan(ctypes.byref(sh), plan_kind, ctypes.cast(out, ctypes.c_void_p)), "conv_launch_plan")
-            share = 1.0 - (out[7] >> 8) / 1000.0
-        _FLOPS[key] = [1, conv_executed_flops(*key[1]) * share]
+        share = 1.0 if sh is None else 1.0 - _launch_plan(sh, plan_kind, geom.key).skipped_permille / 1000.0
+        _FLOPS[(kind, geom.key)] = [1, conv_executed_flops(*geom.key) * share]
     else:
         ent[0] += 1
+
+
+def _note_bgemm(batch, M, N, K, launches=1):     # count `launches` batched-GEMM launches of one shape (ops.count_flops)
+    if _FLOPS is not None:
+        _FLOPS.setdefault(("bgemm", (batch, M, N, K)), [0, 2.0 * batch * M * N * K])[0] += launches
 
 
 def _stream():
@@ -258,19 +257,21 @@ def _tuned(sh, kind, key):
 # (per stream, 64 MB at a time): views keep their page alive, so tensor lifetimes are the usual ones; whether a launch splits K
 # is asked from the library once per shape (gim_conv_launch_plan) and cached.
 _ZERO_POOL = os.environ.get("GIM_NO_ZERO_POOL") is None   # A/B switch (host side)
-_SPLITS_K = {}
+_SPLITS_K = {}    # (plan kind,) + ConvGeom.key -> _Plan; cleared when the mode / matrix path / launch overrides change
 _ZERO_PAGES = {}
 _ZERO_PAGE = 16 << 20   # floats per page (64 MB)
+_Plan = collections.namedtuple("_Plan", "ksplit skipped_permille")
 
 
-def _splits_k(sh, plan_kind, key):
-    """Does this launch combine K slices with atomics (and so need a zeroed output)?"""
+def _launch_plan(sh, plan_kind, key):
+    """What the library would launch for `sh` (include/gim_hip.h gim_conv_launch_plan; plan_kind 0 fwd, 1 dgrad, 2 dgrad_t), asked
+    once per shape: the K-split factor (> 1: slices combined with atomics into a ZEROED output) and the skipped share of its K steps in 1/1000."""
     k_ = (plan_kind,) + key
     v = _SPLITS_K.get(k_)
     if v is None:
         out = (ctypes.c_int32 * 8)()
         check(_lib.load().gim_conv_launch_plan(ctypes.byref(sh), plan_kind, ctypes.cast(out, ctypes.c_void_p)), "conv_launch_plan")
-        v = _SPLITS_K[k_] = out[3] > 1
+        v = _SPLITS_K[k_] = _Plan(out[3], out[7] >> 8)
     return v
 
 
@@ -296,7 +297,7 @@ def _zeros_from_pool(shape, device):
 def _conv_out(sh, plan_kind, key, shape, device):
     """Output buffer of a forward (plan_kind 0) / dgrad (1, 2) launch: zeros from the pool when the launch splits K (and
     sh.out_zeroed tells the library not to clear it again), plain torch.empty otherwise."""
-    if _ZERO_POOL and _splits_k(sh, plan_kind, key) and not torch.cuda.is_current_stream_capturing():
+    if _ZERO_POOL and _launch_plan(sh, plan_kind, key).ksplit > 1 and not torch.cuda.is_current_stream_capturing():
         sh.out_zeroed = 1
         return _zeros_from_pool(shape, device)
     return torch.empty(shape, device=device, dtype=torch.float32)
@@ -329,6 +330,39 @@ def _folded(wp, Cout, Cin, KH):
     return f
 
 
+class _StreamReady:
+    """A buffer that ONE stream writes and others then use (the lanes and the encoders' side streams share WgradQueue pages, _transposed
+    and SNConv2d.folded weights).  Built right after the writing work was issued on the current stream."""
+    __slots__ = ("tensor", "event", "streams", "in_capture")
+
+    def __init__(self, tensor):
+        self.tensor = tensor
+        self.rewritten()
+
+    def rewritten(self):
+        """The current stream has just (re)written the buffer: every other stream has to order itself behind that again."""
+        self.event = torch.cuda.current_stream().record_event()
+        self.streams = {_stream()}     # raw handles of the streams already ordered behind `event`
+        self.in_capture = torch.cuda.is_current_stream_capturing()
+
+    def use_on_current_stream(self, raw=None):
+        """The buffer, safe to use in work issued on the current stream from now on (raw: its handle, when the caller has it).
+        The first use on a stream other than the writer's makes that stream wait for the writer's event and tells the caching
+        allocator about the second user; later uses are one set lookup on the raw handle - no torch Stream object is built.
+        Capture rule: an event recorded BEFORE a hipGraph capture began is not waited for inside the capture.  That work has
+        completed (a capture starts behind a device synchronisation, tools/graph_replay_experiment.py), and a captured wait on an
+        un-captured event is not a graph edge.  An event recorded inside the capture is waited for: that is the edge."""
+        if raw is None:
+            raw = _stream()
+        if raw not in self.streams:
+            cur = torch.cuda.current_stream()
+            if self.in_capture or not torch.cuda.is_current_stream_capturing():
+                cur.wait_event(self.event)
+            self.tensor.record_stream(cur)
+            self.streams.add(raw)
+        return self.tensor
+
+
 # --------------------------------------------------------------------------------------------
 # deferred, batched weight-gradient finish
 # --------------------------------------------------------------------------------------------
@@ -338,6 +372,20 @@ class _WgradJob(ctypes.Structure):
                 ("grad_w", ctypes.c_void_p), ("grad_b", ctypes.c_void_p),
                 ("Cout", ctypes.c_int32), ("Cin", ctypes.c_int32), ("K", ctypes.c_int32), ("fold", ctypes.c_int32),
                 ("n_chunks", ctypes.c_int32), ("exclusive", ctypes.c_int32)]
+
+
+class _ArenaPage(_StreamReady):
+    """One zero-filled page of a WgradQueue arena; its first `used` floats are handed out."""
+    __slots__ = ("used",)
+
+    def __init__(self, n, device):
+        super().__init__(torch.zeros(n, device=device, dtype=torch.float32))
+        self.used = 0
+
+    def rezero(self):
+        self.tensor[:self.used].zero_()
+        self.used = 0
+        self.rewritten()
 
 
 class WgradQueue:
@@ -350,7 +398,7 @@ class WgradQueue:
     PAGE = 32 << 20  # floats
 
     def __init__(self):
-        self.pages = []       # [tensor, used]
+        self.pages = []       # _ArenaPage
         self.jobs = []        # tuples of ints (the job table signature)
         self.keep = []        # tensors that must outlive the flush
         self.streams = set()
@@ -359,30 +407,15 @@ class WgradQueue:
         self.cache = collections.OrderedDict()   # job-table signature -> device tables (G / D backward, buffer parities)
         self.enabled = os.environ.get("GIM_WGRAD_IMMEDIATE") is None
 
-    @staticmethod
-    def _zeroed_mark():
-        """[event after the zero-fill just issued on the current stream, streams ordered behind it, recorded inside a capture]."""
-        return [torch.cuda.current_stream().record_event(), {_stream()}, torch.cuda.is_current_stream_capturing()]
-
     def take(self, n, device):
         """n zeroed floats (64-float aligned) that stay valid until the flush."""
         n = (n + 63) & ~63
-        raw = _stream()
-        if not self.pages or self.pages[-1][1] + n > self.pages[-1][0].numel():
+        if not self.pages or self.pages[-1].used + n > self.pages[-1].tensor.numel():
             # the zero-fill runs on the allocating stream; every OTHER stream that later adds into this page first waits for it
-            page = torch.zeros(max(n, self.PAGE), device=device, dtype=torch.float32)
-            self.pages.append([page, 0] + self._zeroed_mark())
+            self.pages.append(_ArenaPage(max(n, self.PAGE), device))
         pg = self.pages[-1]
-        if raw not in pg[3]:
-            cur = torch.cuda.current_stream()
-            # (an event recorded BEFORE a hipGraph capture began is not waited for inside the capture: that work has completed -
-            # GraphedGimStep synchronizes before it captures - and a captured wait on an un-captured event is not a graph edge)
-            if pg[4] or not torch.cuda.is_current_stream_capturing():
-                cur.wait_event(pg[2])
-            pg[0].record_stream(cur)
-            pg[3].add(raw)
-        ptr = pg[0].data_ptr() + 4 * pg[1]
-        pg[1] += n
+        ptr = pg.use_on_current_stream().data_ptr() + 4 * pg.used
+        pg.used += n
         return ptr
 
     def add(self, job, keep):
@@ -403,7 +436,7 @@ class WgradQueue:
         cur = torch.cuda.current_stream()
         for st in self.streams:   # slots were written on the encoders' side streams too
             stream_wait(cur, st)
-        device = self.pages[0][0].device
+        device = self.pages[0].tensor.device
         sig = tuple(self.jobs)
         dev_tabs = self.cache.get(sig)
         if dev_tabs is None:
@@ -436,15 +469,12 @@ class WgradQueue:
         check(_lib.load().gim_wgrad_finish_batched(dj.data_ptr(), len(sig), dt.data_ptr(), nb, dsn.data_ptr(), nbs, _stream()),
               "wgrad_finish_batched")
         if len(self.pages) > 1:  # first backward of a new shape: merge into one page for the next pass
-            total = sum(pg[1] for pg in self.pages)
-            self.pages = [[torch.zeros(total + (total >> 3), device=device, dtype=torch.float32), 0] + self._zeroed_mark()]
+            total = sum(pg.used for pg in self.pages)
+            self.pages = [_ArenaPage(total + (total >> 3), device)]
             self.cache.clear()
         else:
-            pg = self.pages[0]
-            pg[0][:pg[1]].zero_()
-            pg[1] = 0
             # the re-zeroing runs on the flushing stream; the next pass's first user on every other stream waits for it
-            pg[2:] = self._zeroed_mark()
+            self.pages[0].rezero()
         self.jobs, self.keep, self.streams = [], [], set()
 
 
@@ -461,10 +491,8 @@ def reset_wgrad_queues():
     for q in _QUEUES.values():
         if q.jobs or q.cb_queued:
             for pg in q.pages:
-                if pg[1]:
-                    pg[0][:pg[1]].zero_()
-                    pg[1] = 0
-                    pg[2:] = q._zeroed_mark()
+                if pg.used:
+                    pg.rezero()
             q.jobs, q.keep, q.streams, q.cb_queued = [], [], set(), False
 
 
@@ -483,9 +511,23 @@ def stream_wait(waiter, other):
     """waiter.wait_stream(other), skipped when both are the same HIP stream.  The role -> stream map of gim_img_models aliases
     roles onto shared streams (lane 1's first encoder runs on lane 1's own stream): a stream "waiting for itself" is a no-op in
     eager execution, but inside a hipGraph capture it records an event on the capturing stream and then makes that same stream
-    wait for it - a self-edge in the captured graph (see graph.GraphedGimStep)."""
+    wait for it - a self-edge in the captured graph (tools/graph_replay_experiment.py captures the two-lane step)."""
     if waiter.cuda_stream != other.cuda_stream:
         waiter.wait_stream(other)
+
+
+# Backward's Python on the CALLING thread.  torch's autograd engine hands a backward pass to a per-device worker thread; every node
+# of this engine is a Python Function, and with the hand-off the host needs 31-37 ms to enqueue one training step where it needs 26-28 ms
+# when the calling thread runs the nodes itself (64x64x3, 16 episodes: the device needs 37 ms, so with the worker thread the host IS the
+# bound in part of the runs - 418-426 episodes/s instead of 429-431; at 1 / 4 episodes per step: 31 -> 42 / 132 -> 159 episodes/s;
+# profiles/r04_m_host_enqueue.txt).  Same graph, same kernels, same streams (the engine sets each node's forward stream either way).
+# GIM_MT_AUTOGRAD=1 restores torch's default.
+_CALLER_THREAD_BACKWARD = os.environ.get("GIM_MT_AUTOGRAD") is None
+
+
+def caller_thread_backward():
+    """Context for .backward() / autograd.grad() calls of the training step: autograd's nodes run on the calling thread."""
+    return torch.autograd.set_multithreading_enabled(not _CALLER_THREAD_BACKWARD)
 
 
 _PENDING_JOIN = []   # streams of lane-1 work the caller's stream has not waited for yet (gim_step(defer_join=True))
@@ -522,191 +564,64 @@ class lane:
 # --------------------------------------------------------------------------------------------
 # convolution / linear
 # --------------------------------------------------------------------------------------------
-class ConvFn(Function):
-    """y = [avgpool2]( conv(up2^ups(lrelu(x, pre_slope)), w) ) / sigma + bias + res   (NHWC; linear when x is 2-D).
+class ConvGeom(collections.namedtuple("ConvGeom", "N H W Cin Cout KH ups pre_slope has_bias has_res pool fold res_ups x_act linear key")):
+    """One convolution call (a linear: H = W = KH = 1), as every launch of its forward and backward reads it; ConvFn keeps it as
+    ctx.cfg.  (H, W): the resolution the unfused conv would run at (after the nearest upsample, before the average pool).
+    fold: the launches read the (KH+1)^2-tap folded weights (the pool / sub-pixel forms).  x_act: x is stored ACTIVATED (its
+    producer applied this conv's LeakyReLU in its epilogue): forward and wgrad then run without the per-tap activation; dgrad
+    keeps the slope - its mask only needs the sign, which is the same.  key = (N, H, W, Cin, Cout, KH, ups, pool, fold): what the
+    launch-plan cache, _TUNE_OVERRIDE and count_flops are keyed by."""
+    __slots__ = ()
 
-    pool: the 2x2 average pool behind the conv is folded into ONE stride-2 convolution; ups with a KxK kernel
-    (K > 1) runs in its sub-pixel form on the low-resolution input: neither pooling nor upsampling costs conv FLOPs.
-    res_ups: the residual is stored at half the output resolution."""
+    @classmethod
+    def make(cls, N, H, W, Cin, Cout, KH, ups=0, pre_slope=1.0, pool=False, res_ups=False, has_bias=False, has_res=False, x_act=False, linear=False):
+        fold = 1 if (pool or (ups and KH > 1)) else 0
+        return cls(N, H, W, Cin, Cout, KH, ups, pre_slope, has_bias, has_res, bool(pool), fold, bool(res_ups), bool(x_act), linear,
+                   (N, H, W, Cin, Cout, KH, ups, 1 if pool else 0, fold))
 
-    @staticmethod
-    def forward(ctx, x, w, bias, res, sigma, u_s, v_s, ups, pre_slope, pool, res_ups, wf=None, guard=None, post_slope=1.0, x_act=False):
-        lib = _lib.load()
-        x = _req(x, "x")
-        wp = weight_phys(_req_w(w))
-        if x.dim() == 2:
-            N, Hs, Ws, Cin = x.shape[0], 1, 1, x.shape[1]
-        else:
-            N, Hs, Ws, Cin = x.shape
-        Cout = w.shape[0]
-        KH = w.shape[2] if w.dim() == 4 else 1
+    @classmethod
+    def of(cls, x, w, ups, pre_slope, pool, res_ups, bias, res, x_act):
+        """The call ConvFn.forward(x, w, ...) describes (x NHWC [N, Hs, Ws, Cin], or [N, Cin] with a 2-D weight: a linear)."""
+        N, Hs, Ws, Cin = (x.shape[0], 1, 1, x.shape[1]) if x.dim() == 2 else x.shape
         if w.shape[1] != Cin:
             raise RuntimeError("conv: weight expects %d input channels, got %d" % (w.shape[1], Cin))
-        H, W = Hs << ups, Ws << ups
-        fold = 1 if (pool or (ups and KH > 1)) else 0
-        # x_act: x is stored ACTIVATED (its producer applied this conv's LeakyReLU in its epilogue, post_slope below): forward and
-        # wgrad then run without the per-tap activation; dgrad keeps the slope - its mask only needs the sign, which is the same
-        sh = _shape(N, H, W, Cin, Cout, KH, ups, 1.0 if x_act else pre_slope, 1 if pool else 0, fold, 1 if res_ups else 0)
-        Ho, Wo = (H >> 1, W >> 1) if pool else (H, W)
-        key = (N, H, W, Cin, Cout, KH, ups, 1 if pool else 0, fold)
-        _tuned(sh, "fwd", key)
-        # post_slope != 1: store lrelu(y) for a consumer that is the ONLY reader of y and runs with x_act.  conv2d_post_act has
-        # resolved it (1.0 when the launch splits K: the slices combine by addition); a split-K launch refuses it here
-        merged = bool(ups) and _merged_subpixel(x, w, ups, res, sh)
-        if post_slope != 1.0 and not merged:
-            if x.dim() != 4 or _splits_k(sh, 0, key):
-                raise RuntimeError("conv: an activated output (post_slope) cannot be combined with a split-K launch or a linear layer")
-            sh.post_slope = post_slope
-        if res is not None:
-            res = _req(res, "res")
-        xp = None
-        if _ROWS_FORM and x.dim() == 4 and KH >= 3 and Cin <= 8 and KH * Cin <= 64 and Cout >= 16 and Cout % 4 == 0 and not (ups or pool or res_ups) \
-                and sh.tune_tile == 0:
-            # image layers: row-contiguous K on a zero-padded, activated copy of the image (include/gim_hip.h gim_conv2d_fwd_rows)
-            pad = (KH - 1) // 2
-            xp = torch.empty((N, H + 2 * pad, W + 2 * pad, Cin), device=x.device, dtype=torch.float32)
-            check(lib.gim_pad_image(_p(x), _p(xp), N, H, W, Cin, pad, 1.0 if x_act else pre_slope, _stream()), "pad_image")
-            wrows = _transposed(lib, w, wp, Cout, Cin, KH, rows=True)
-            sh.tune_ksplit = 1      # one K slice: these layers have >= 10^5 output pixels; keeps an activated output (post_slope) legal
-            y = torch.empty((N, Ho, Wo, Cout), device=x.device, dtype=torch.float32)
-            check(lib.gim_conv2d_fwd_rows(_p(xp), _p(wrows), _p(bias), _p(sigma), _p(res), _p(y), sh, _stream()), "conv2d_fwd_rows")
-        elif merged:
-            # the generator's last layer (9x9 64->3 behind the upsample): the four output-parity classes as ONE plain 5-tap convolution
-            # to 4 * Cout channels + a depth-to-space copy (include/gim_hip.h gim_conv2d_pack_subpixel_weights); gradients: the sub-pixel forms
-            if wf is None:
-                wf = _folded(wp, Cout, Cin, KH)
-            wm = _transposed(lib, w, wf, Cout, Cin, KH, subpix=True)
-            shm = _shape(N, Hs, Ws, Cin, 4 * Cout, (KH + 1) // 2, 0, 1.0 if x_act else pre_slope, 0, 0, 0)
-            keym = (N, Hs, Ws, Cin, 4 * Cout, (KH + 1) // 2, 0, 0, 0)
-            _tuned(shm, "fwd", keym)
-            y4 = _conv_out(shm, 0, keym, (N, Hs, Ws, 4 * Cout), x.device)
-            check(lib.gim_conv2d_fwd(_p(x), _p(wm), None, _p(sigma), None, _p(y4), shm, _stream()), "conv2d_fwd")
-            y = torch.empty((N, H, W, Cout), device=x.device, dtype=torch.float32)
-            check(lib.gim_depth_to_space2(_p(y4), _p(bias), _p(y), N, Hs, Ws, Cout, post_slope, _stream()), "depth_to_space2")
-        else:
-            y = _conv_out(sh, 0, key, (N, Cout) if x.dim() == 2 else (N, Ho, Wo, Cout), x.device)
-            if fold and wf is None:
-                wf = _folded(wp, Cout, Cin, KH)
-            wk = wf if fold else wp
-            check(lib.gim_conv2d_fwd(_p(x), _p(wk), _p(bias), _p(sigma), _p(res), _p(y), sh, _stream()), "conv2d_fwd")
-        ctx.save_for_backward(x, w, sigma, u_s, v_s, wf if fold else None, bias, xp)
-        ctx.cfg = (N, H, W, Cin, Cout, KH, ups, pre_slope, bias is not None, res is not None, bool(pool), fold, bool(res_ups))
-        ctx.guard = guard
-        ctx.x_act = bool(x_act)
-        if _FLOPS is not None:
-            _note_conv("fwd", ctx.cfg, sh, 0)
-        return y
+        return cls.make(N, Hs << ups, Ws << ups, Cin, w.shape[0], w.shape[2] if w.dim() == 4 else 1, ups, pre_slope, pool, res_ups,
+                        bias is not None, res is not None, x_act, x.dim() == 2)
 
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        x, w, sigma, u_s, v_s, wf, bias, xp = ctx.saved_tensors
-        N, H, W, Cin, Cout, KH, ups, pre_slope, has_bias, has_res, pool, fold, res_ups = ctx.cfg
-        dy = _req(dy, "dy")
-        if ctx.guard is not None and ctx.guard[0].stale(ctx.guard[1]):
-            raise RuntimeError("the spectral-norm state (sigma, u, v) of this forward pass was overwritten by later forward "
-                               "passes of the same model: run backward before the third forward")
-        if _second_order():
-            if ups or res_ups:
-                raise NotImplementedError("second-order backward of an upsampling convolution is not on the R1 path")
-            dx = ConvDgradFn.apply(dy, w, x, sigma, u_s, v_s, wf, ctx.cfg) if ctx.needs_input_grad[0] else None
-            return dx, None, None, (dy if has_res and ctx.needs_input_grad[3] else None), None, None, None, None, None, None, None, None, None, None, None
-        wp = weight_phys(w)
-        sh = _shape(N, H, W, Cin, Cout, KH, ups, pre_slope, 1 if pool else 0, fold, 1 if res_ups else 0)
-        st = _stream()
-        dev = dy.device
-        dx = dw = db = dres = None
-        if ctx.needs_input_grad[0]:
-            sh_d = sh
-            if _TUNE_OVERRIDE:
-                sh_d = _tuned(_shape(N, H, W, Cin, Cout, KH, ups, pre_slope, 1 if pool else 0, fold, 1 if res_ups else 0), "dgrad",
-                              (N, H, W, Cin, Cout, KH, ups, 1 if pool else 0, fold))
-            dx = _conv_dgrad(lib, dy, x, wp, wf, sigma, sh_d, ctx.cfg, st, w, getattr(ctx, "dgrad_res", None))
-        want_w = ctx.needs_input_grad[1]
-        want_b = has_bias and ctx.needs_input_grad[2]
-        Mo = N * (H >> 1) * (W >> 1) if pool else N * H * W  # pixels of dy
-        if want_w:
-            sh_w = sh
-            if ctx.x_act or _TUNE_OVERRIDE:   # x_act: the stored x is already lrelu(x): no activation on the wgrad operand
-                sh_w = _tuned(_shape(N, H, W, Cin, Cout, KH, ups, 1.0 if ctx.x_act else pre_slope, 1 if pool else 0, fold, 1 if res_ups else 0),
-                              "wgrad", (N, H, W, Cin, Cout, KH, ups, 1 if pool else 0, fold))
-            dw, db = _conv_wgrad(lib, dy, x, w, wp, bias, sigma, u_s, v_s, sh_w, ctx.cfg, want_b, st, xp)
-        elif want_b:
-            db = torch.empty(Cout, device=dev, dtype=torch.float32)
-            scratch = torch.empty(256 * Cout, device=dev, dtype=torch.float32)
-            check(lib.gim_colsum(_p(dy), _p(db), _p(scratch), Mo, Cout, st), "colsum")
-        if has_res and ctx.needs_input_grad[3]:
-            if res_ups:
-                dres = torch.empty((N, H >> 1, W >> 1, Cout), device=dev, dtype=torch.float32)
-                check(lib.gim_upsample2x_bwd(_p(dy), None, 1.0, _p(dres), N, H >> 1, W >> 1, Cout, st), "upsample2x_bwd")
-            else:
-                dres = dy
-        return dx, dw, db, dres, None, None, None, None, None, None, None, None, None, None, None
+    out_pixels = property(lambda s: s.N * (s.H >> s.pool) * (s.W >> s.pool))     # pixels of y / dy
+    out_shape = property(lambda s: (s.N, s.Cout) if s.linear else (s.N, s.H >> s.pool, s.W >> s.pool, s.Cout))
+    K = property(lambda s: s.KH * s.KH * s.Cin)
+    KFF = property(lambda s: (s.KH + 1) * (s.KH + 1) * s.Cin if s.fold else s.K)   # per output channel, in the form the launches read
+
+    def shape(self, kind, pre_slope=None):
+        """The caller's own gim_conv_shape for a launch of `kind` ("fwd" / "dgrad" / "wgrad" of _TUNE_OVERRIDE; None: no override)."""
+        return _tuned(_shape(self.N, self.H, self.W, self.Cin, self.Cout, self.KH, self.ups, self.pre_slope if pre_slope is None else pre_slope,
+                             1 if self.pool else 0, self.fold, 1 if self.res_ups else 0), kind, self.key)
+
+    def linear_map(self):
+        """The conv as a linear map of its input: no prologue, bias or residual (ConvDgradFn's adjoints)."""
+        return ConvGeom.make(self.N, self.H, self.W, self.Cin, self.Cout, self.KH, 0, 1.0, self.pool, linear=self.linear)
 
 
-# Backward's Python on the CALLING thread.  torch's autograd engine hands a backward pass to a per-device worker thread; every node
-# of this engine is a Python Function, and with the hand-off the host needs 31-37 ms to enqueue one training step where it needs 26-28 ms
-# when the calling thread runs the nodes itself (64x64x3, 16 episodes: the device needs 37 ms, so with the worker thread the host IS the
-# bound in part of the runs - 418-426 episodes/s instead of 429-431; at 1 / 4 episodes per step: 31 -> 42 / 132 -> 159 episodes/s;
-# profiles/r04_m_host_enqueue.txt).  Same graph, same kernels, same streams (the engine sets each node's forward stream either way).
-# GIM_MT_AUTOGRAD=1 restores torch's default.
-_CALLER_THREAD_BACKWARD = os.environ.get("GIM_MT_AUTOGRAD") is None
-
-
-def caller_thread_backward():
-    """Context for .backward() / autograd.grad() calls of the training step: autograd's nodes run on the calling thread."""
-    return torch.autograd.set_multithreading_enabled(not _CALLER_THREAD_BACKWARD)
-
-
+# The _*_route functions decide which kernel a launch takes (DESIGN.md section 4), for the product and the tools; only they read the switches
 _ACT_STORAGE = os.environ.get("GIM_NO_ACT_STORAGE") is None   # A/B switch (host side)
-_ROWS_FORM = os.environ.get("GIM_NO_ROWS_FORM") is None   # A/B switch (host side): row-contiguous K for the image layers
-_MERGED_SUBPIXEL = os.environ.get("GIM_NO_MERGED_SUBPIXEL") is None   # A/B switch (host side): stacked parity classes for the 9x9 64->3 layer
+_ROWS_FORM = os.environ.get("GIM_NO_ROWS_FORM") is None   # row-contiguous K for the image layers
+_MERGED_SUBPIXEL = os.environ.get("GIM_NO_MERGED_SUBPIXEL") is None   # stacked parity classes for the 9x9 64->3 layer
+_NARROW_DGRAD_T = os.environ.get("GIM_NO_NARROW_DGRAD_T") is None
+_NARROW_XFOLD = os.environ.get("GIM_NO_NARROW_XFOLD") is None
 
 
-def _merged_subpixel(x, w, ups, res, sh):
-    """Does this forward run as the stacked-parity-class convolution (ConvFn.forward; include/gim_hip.h gim_conv2d_pack_subpixel_weights)?"""
-    KH = w.shape[2] if w.dim() == 4 else 1
-    return bool(_MERGED_SUBPIXEL and ups and KH >= 5 and (KH & 3) == 1 and w.shape[0] <= 4 and x.dim() == 4 and res is None and sh.tune_tile == 0)
-
-_NARROW_DGRAD_T = os.environ.get("GIM_NO_NARROW_DGRAD_T") is None   # A/B switch (host side)
-_NARROW_XFOLD = os.environ.get("GIM_NO_NARROW_XFOLD") is None   # A/B switch (host side)
-_WT_CACHE = {}   # (weight data_ptr, taps per dim) -> (version key, WT, ready event, stream, weakref to the parameter)
-
-
-def _transposed(lib, w, wk, Cout, Cin, KF, xfold=0, rows=False, subpix=False):
-    """WT[Cin][KF][KF][Cout] of the (plain or folded) weights `wk` of parameter `w` - or, xfold = J, the x-folded
-    WX[J * Cin][KF][KF + J - 1][Cout] of gim_conv2d_xfold_weights; or, rows, the row-padded WP[Cout][KF][KF * Cin -> 16] of
-    gim_conv2d_pack_rows_weights; or, subpix (wk = the folded taps, KF = the conv's K), the stacked parity classes
-    WM[4 Cout][(KF+1)/2][(KF+1)/2][Cin] of gim_conv2d_pack_subpixel_weights - recomputed only when the weights changed (autograd version
-    counter for torch-side writes, optim.weights_epoch for the fused Adam kernel)."""
-    from . import optim
-    key = (w._version, optim.weights_epoch(w))
-    slot = (w.data_ptr(), KF, "rows" if rows else ("subpix" if subpix else xfold))
-    ent = _WT_CACHE.get(slot)
-    raw = _stream()
-    if ent is None or ent[0] != key or ent[4]() is not w:
-        cur = torch.cuda.current_stream()
-        if rows:
-            wt = torch.empty(Cout * KF * ((KF * Cin + 15) & ~15), device=wk.device, dtype=torch.float32)
-            check(lib.gim_conv2d_pack_rows_weights(_p(wk), _p(wt), Cout, Cin, KF, raw), "pack_rows_weights")
-        elif subpix:
-            wt = torch.empty(4 * Cout * ((KF + 1) // 2) ** 2 * Cin, device=wk.device, dtype=torch.float32)
-            check(lib.gim_conv2d_pack_subpixel_weights(_p(wk), _p(wt), Cout, Cin, KF, raw), "pack_subpixel_weights")
-        elif xfold:
-            wt = torch.empty(xfold * Cin * KF * (KF + xfold - 1) * Cout, device=wk.device, dtype=torch.float32)
-            check(lib.gim_conv2d_xfold_weights(_p(wk), _p(wt), Cout, Cin, KF, xfold, raw), "xfold_weights")
-        else:
-            wt = torch.empty(Cin * KF * KF * Cout, device=wk.device, dtype=torch.float32)
-            check(lib.gim_conv2d_transpose_weights(_p(wk), _p(wt), Cout, Cin, KF, raw), "transpose_weights")
-        ent = (key, wt, cur.record_event(), raw, weakref.ref(w, lambda _r, slot=slot: _WT_CACHE.pop(slot, None)),
-               torch.cuda.is_current_stream_capturing())
-        _WT_CACHE[slot] = ent
-    elif ent[3] != raw:
-        cur = torch.cuda.current_stream()
-        if ent[5] or not torch.cuda.is_current_stream_capturing():   # see WgradQueue.take
-            cur.wait_event(ent[2])
-        ent[1].record_stream(cur)
-    return ent[1]
+def _fwd_route(g, tune_tile):
+    """"rows" (image layers: row-contiguous K on a zero-padded, activated copy of the image, gim_conv2d_fwd_rows), "subpixel" (the
+    generator's 9x9 64->3 layer behind the upsample: the four output-parity classes as ONE plain 5-tap convolution to 4 * Cout channels
+    + a depth-to-space copy) or "plain" (gim_conv2d_fwd).  tune_tile: of the launch's gim_conv_shape - an override keeps "plain"."""
+    if g.linear or tune_tile != 0:
+        return "plain"
+    if _ROWS_FORM and g.KH >= 3 and g.Cin <= 8 and g.KH * g.Cin <= 64 and g.Cout >= 16 and g.Cout % 4 == 0 and not (g.ups or g.pool or g.res_ups):
+        return "rows"
+    if _MERGED_SUBPIXEL and g.ups and g.KH >= 5 and (g.KH & 3) == 1 and g.Cout <= 4 and not g.has_res:
+        return "subpixel"
+    return "plain"
 
 
 def _xfold_factor(Cin, W):
@@ -719,90 +634,251 @@ def _xfold_factor(Cin, W):
     return J if (Cin <= 8 and W % J == 0 and W // J >= 1) else 0
 
 
-def _conv_dgrad(lib, dy, x, wp, wf, sigma, sh, cfg, st, w=None, res_half=None):
-    """dx = lrelu'(x) * dgrad(dy, w) / sigma  (through the pool / sub-pixel folds when the forward used them).
-    res_half [N, H/2, W/2, Cin]: the gradient w.r.t. avgpool2(x) of a second reader of x (ConvForkPoolFn): 0.25 * up2(res_half) is added -
-    in the dgrad kernel's epilogue where the launch form allows it (gim_conv2d_dgrad_res), by gim_add_avgpool2_bwd otherwise.
-    With the parameter `w` given, the gradient w.r.t. IMAGES (Cin <= 8, Cout % 16 == 0) runs the k-contiguous kernel on cached
-    transposed weights (gim_conv2d_dgrad_t)."""
-    N, H, W, Cin, Cout, KH, ups, pre_slope, has_bias, has_res, pool, fold, res_ups = cfg
-    if res_half is not None:
-        plain = not (ups or pool or fold) and pre_slope != 1.0 and not (w is not None and Cout % 16 == 0 and Cin <= 8 and _NARROW_DGRAD_T) \
-            and not (sh.prec == 1 and Cout % 32 == 0 and Cin >= 32)
-        if plain:
-            if _FLOPS is not None:
-                _note_conv("dgrad", cfg, sh, 1)
-            key = (N, H, W, Cin, Cout, KH, ups, 0, 0)
-            dx = _conv_out(sh, 1, key, tuple(x.shape), x.device)
-            check(lib.gim_conv2d_dgrad_res(_p(dy), _p(wp), _p(sigma), _p(x), _p(_req(res_half, "res_half")), 0.25, _p(dx), sh, st), "conv2d_dgrad_res")
-            return dx
-        g = _conv_dgrad(lib, dy, x, wp, wf, sigma, sh, cfg, st, w)
-        out = torch.empty_like(g)
-        check(lib.gim_add_avgpool2_bwd(_p(g), _p(_req(res_half, "res_half")), _p(out), N, H, W, Cin, st), "add_avgpool2_bwd")
-        return out
+def _dgrad_route(g, prec, has_w, has_res_half=False):
+    """-> (route, J, add_res) on matrix path `prec` (gim_conv_shape.prec); has_w: the caller has the weight PARAMETER, whose cached
+    re-laid-out copies the first two routes read.  "t": gim_conv2d_dgrad_t on transposed weights (rows k-contiguous: vector weight loads)
+    for the gradient w.r.t. IMAGES (<= 8 input channels), where the k-major kernel loads weights as scalars - and EVERY eligible dgrad
+    of the fp16 path, whose kernel exists in this form only; "xfold": those image layers when plain, J adjacent dx pixels as the output
+    columns of one stride-(1, J) convolution; "ups": 1x1 behind up2; "plain".  has_res_half (0.25 * up2(res_half) is to be added):
+    "res", the plain form with the addition in its epilogue - or the launch's own route and add_res (gim_add_avgpool2_bwd follows)."""
+    f16_t = prec == 1 and g.Cout % 32 == 0 and g.Cin >= 32
+    J = 0
+    if has_w and g.Cout % 16 == 0 and not (g.ups and not g.fold) and ((g.Cin <= 8 and _NARROW_DGRAD_T) or f16_t):
+        if g.KH >= 3 and not (g.ups or g.pool or g.fold) and _NARROW_XFOLD and not f16_t:
+            J = _xfold_factor(g.Cin, g.W)
+        route = "xfold" if J else "t"
+    else:
+        route = "ups" if (g.ups and not g.fold) else "plain"
+    if not has_res_half:
+        return route, J, False
+    if route == "plain" and not (g.pool or g.fold) and g.pre_slope != 1.0 and not f16_t:
+        return "res", 0, False
+    return route, J, True
+
+
+def _wgrad_route(g, sh, has_target, has_sigma, bias_untargeted=False, rows_copy=False):
+    """-> (route, slabs).  has_target: the parameter's .grad can be added into (_grad_target); bias_untargeted: a bias gradient is
+    wanted from the same launch but has no such buffer; rows_copy: the "rows" forward left its padded copy and dy is contiguous.
+    "queued" / "queued_rows": raw gradient into an arena slot now, all convs finished by two launches when backward ends (WgradQueue);
+    "direct": one gim_conv2d_wgrad writes the gradient; "slabs": `slabs` slabs (GIM_WGRAD_SLABS / deterministic mode: as many as the
+    library says, added in a fixed order) + gim_wgrad_finish."""
+    if has_target and wgrad_queue.enabled and not _DETERMINISTIC[0] and not bias_untargeted:
+        return ("queued_rows" if rows_copy else "queued"), 1
+    ns = 1
+    if _WGRAD_SLABS or _DETERMINISTIC[0]:
+        ns = _lib.load().gim_conv2d_wgrad_slabs(sh)
+        if ns <= 0:
+            check(ns, "conv2d_wgrad_slabs")
+    return ("direct" if (ns == 1 and not has_sigma and not g.fold and not has_target) else "slabs"), ns
+
+
+def _stores_activated(g, post_slope):
+    """Does the forward of g write lrelu(y, post_slope)?  (Not a split-K launch; "subpixel" activates in its depth-to-space copy.)"""
+    if not (_ACT_STORAGE and post_slope != 1.0) or g.linear:
+        return False
+    sh = g.shape("fwd")
+    return _fwd_route(g, sh.tune_tile) == "subpixel" or _launch_plan(sh, 0, g.key).ksplit == 1
+
+
+def _merged_subpixel(x, w, ups, res, sh):
+    """Does this forward run as the stacked-parity-class convolution ("subpixel" of _fwd_route)?"""
+    return _fwd_route(ConvGeom.of(x, w, ups, 1.0, False, False, None, res, False), sh.tune_tile) == "subpixel"
+
+
+class ConvFn(Function):
+    """y = [avgpool2]( conv(up2^ups(lrelu(x, pre_slope)), w) ) / sigma + bias + res   (NHWC; linear when x is 2-D).
+    pool: the 2x2 average pool behind the conv is folded into ONE stride-2 convolution; ups with a KxK kernel
+    (K > 1) runs in its sub-pixel form on the low-resolution input: neither pooling nor upsampling costs conv FLOPs.
+    res_ups: the residual is stored at half the output resolution."""
+    N_EXTRA = 11    # forward's inputs behind (x, w, bias, res): backward hands None back for each
+
+    @staticmethod
+    def forward(ctx, x, w, bias, res, sigma, u_s, v_s, ups, pre_slope, pool, res_ups, wf=None, guard=None, post_slope=1.0, x_act=False):
+        lib = _lib.load()
+        x = _req(x, "x")
+        wp = weight_phys(_req_w(w))
+        g = ConvGeom.of(x, w, ups, pre_slope, pool, res_ups, bias, res, x_act)
+        N, H, W, Cin, Cout, KH = g.N, g.H, g.W, g.Cin, g.Cout, g.KH
+        tap_slope = 1.0 if x_act else pre_slope
+        sh = g.shape("fwd", tap_slope)
+        route = _fwd_route(g, sh.tune_tile)
+        # post_slope != 1: store lrelu(y) for the ONLY reader of y, which runs with x_act (callers ask _stores_activated; refused here otherwise)
+        if post_slope != 1.0 and route != "subpixel":
+            if g.linear or _launch_plan(sh, 0, g.key).ksplit > 1:
+                raise RuntimeError("conv: an activated output (post_slope) cannot be combined with a split-K launch or a linear layer")
+            sh.post_slope = post_slope
+        if res is not None:
+            res = _req(res, "res")
+        xp = None
+        if route == "rows":
+            pad = (KH - 1) // 2
+            xp = torch.empty((N, H + 2 * pad, W + 2 * pad, Cin), device=x.device, dtype=torch.float32)
+            check(lib.gim_pad_image(_p(x), _p(xp), N, H, W, Cin, pad, tap_slope, _stream()), "pad_image")
+            wrows = _transposed(lib, w, wp, Cout, Cin, KH, rows=True)
+            sh.tune_ksplit = 1      # one K slice: these layers have >= 10^5 output pixels; keeps an activated output (post_slope) legal
+            y = torch.empty(g.out_shape, device=x.device, dtype=torch.float32)
+            check(lib.gim_conv2d_fwd_rows(_p(xp), _p(wrows), _p(bias), _p(sigma), _p(res), _p(y), sh, _stream()), "conv2d_fwd_rows")
+        elif route == "subpixel":    # (gradients: the sub-pixel forms on the folded weights)
+            if wf is None:
+                wf = _folded(wp, Cout, Cin, KH)
+            wm = _transposed(lib, w, wf, Cout, Cin, KH, subpix=True)
+            gm = ConvGeom.make(N, H >> 1, W >> 1, Cin, 4 * Cout, (KH + 1) // 2)
+            shm = gm.shape("fwd", tap_slope)
+            y4 = _conv_out(shm, 0, gm.key, gm.out_shape, x.device)
+            check(lib.gim_conv2d_fwd(_p(x), _p(wm), None, _p(sigma), None, _p(y4), shm, _stream()), "conv2d_fwd")
+            y = torch.empty(g.out_shape, device=x.device, dtype=torch.float32)
+            check(lib.gim_depth_to_space2(_p(y4), _p(bias), _p(y), N, H >> 1, W >> 1, Cout, post_slope, _stream()), "depth_to_space2")
+        else:
+            y = _conv_out(sh, 0, g.key, g.out_shape, x.device)
+            if g.fold and wf is None:
+                wf = _folded(wp, Cout, Cin, KH)
+            check(lib.gim_conv2d_fwd(_p(x), _p(wf if g.fold else wp), _p(bias), _p(sigma), _p(res), _p(y), sh, _stream()), "conv2d_fwd")
+        ctx.save_for_backward(x, w, sigma, u_s, v_s, wf if g.fold else None, bias, xp)
+        ctx.cfg = g
+        ctx.guard = guard
+        if _FLOPS is not None:
+            _note_conv("fwd", g, sh, 0)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, w, sigma, u_s, v_s, wf, bias, xp = ctx.saved_tensors
+        g = ctx.cfg
+        dy = _req(dy, "dy")
+        if ctx.guard is not None and ctx.guard[0].stale(ctx.guard[1]):
+            raise RuntimeError("the spectral-norm state (sigma, u, v) of this forward pass was overwritten by later forward "
+                               "passes of the same model: run backward before the third forward")
+        need = ctx.needs_input_grad
+        if _second_order():
+            if g.ups or g.res_ups:
+                raise NotImplementedError("second-order backward of an upsampling convolution is not on the R1 path")
+            dx = ConvDgradFn.apply(dy, w, x, sigma, u_s, v_s, wf, g) if need[0] else None
+            return (dx, None, None, dy if g.has_res and need[3] else None) + (None,) * ConvFn.N_EXTRA
+        wp = weight_phys(w)
+        st = _stream()
+        dev = dy.device
+        dx = dw = db = dres = None
+        if need[0]:
+            dx = _conv_dgrad(lib, dy, x, wp, wf, sigma, g.shape("dgrad"), g, st, w, getattr(ctx, "dgrad_res", None))
+        want_b = g.has_bias and need[2]
+        if need[1]:     # (x_act: the stored x is already lrelu(x): no activation on the wgrad operand)
+            dw, db = _conv_wgrad(lib, dy, x, w, wp, bias, sigma, u_s, v_s, g.shape("wgrad", 1.0 if g.x_act else None), g, want_b, st, xp)
+        elif want_b:
+            db = torch.empty(g.Cout, device=dev, dtype=torch.float32)
+            scratch = torch.empty(256 * g.Cout, device=dev, dtype=torch.float32)
+            check(lib.gim_colsum(_p(dy), _p(db), _p(scratch), g.out_pixels, g.Cout, st), "colsum")
+        if g.has_res and need[3]:
+            if g.res_ups:
+                dres = torch.empty((g.N, g.H >> 1, g.W >> 1, g.Cout), device=dev, dtype=torch.float32)
+                check(lib.gim_upsample2x_bwd(_p(dy), None, 1.0, _p(dres), g.N, g.H >> 1, g.W >> 1, g.Cout, st), "upsample2x_bwd")
+            else:
+                dres = dy
+        return (dx, dw, db, dres) + (None,) * ConvFn.N_EXTRA
+
+
+_WT_CACHE = {}   # (weight data_ptr, taps per dim, layout) -> _DerivedWeights
+
+
+class _DerivedWeights(_StreamReady):
+    """A re-laid-out copy of a parameter's weights (_transposed, SNConv2d.folded); version: of the weights it was made from."""
+    __slots__ = ("version", "param")
+
+    def __init__(self, tensor, version, param=None):
+        super().__init__(tensor)
+        self.version, self.param = version, param     # param: weak reference to the owner, where a cache needs one
+
+
+def _transposed(lib, w, wk, Cout, Cin, KF, xfold=0, rows=False, subpix=False):
+    """WT[Cin][KF][KF][Cout] of the (plain or folded) weights `wk` of parameter `w` - or, xfold = J, the x-folded
+    WX[J * Cin][KF][KF + J - 1][Cout] of gim_conv2d_xfold_weights; or, rows, the row-padded WP[Cout][KF][KF * Cin -> 16] of
+    gim_conv2d_pack_rows_weights; or, subpix (wk = the folded taps, KF = the conv's K), the stacked parity classes
+    WM[4 Cout][(KF+1)/2][(KF+1)/2][Cin] of gim_conv2d_pack_subpixel_weights - recomputed only when the weights changed (autograd version
+    counter for torch-side writes, optim.weights_epoch for the fused Adam kernel)."""
+    from . import optim
+    version = (w._version, optim.weights_epoch(w))
+    slot = (w.data_ptr(), KF, "rows" if rows else ("subpix" if subpix else xfold))
+    ent = _WT_CACHE.get(slot)
+    raw = _stream()
+    if ent is None or ent.version != version or ent.param() is not w:
+        if rows:
+            wt = torch.empty(Cout * KF * ((KF * Cin + 15) & ~15), device=wk.device, dtype=torch.float32)
+            check(lib.gim_conv2d_pack_rows_weights(_p(wk), _p(wt), Cout, Cin, KF, raw), "pack_rows_weights")
+        elif subpix:
+            wt = torch.empty(4 * Cout * ((KF + 1) // 2) ** 2 * Cin, device=wk.device, dtype=torch.float32)
+            check(lib.gim_conv2d_pack_subpixel_weights(_p(wk), _p(wt), Cout, Cin, KF, raw), "pack_subpixel_weights")
+        elif xfold:
+            wt = torch.empty(xfold * Cin * KF * (KF + xfold - 1) * Cout, device=wk.device, dtype=torch.float32)
+            check(lib.gim_conv2d_xfold_weights(_p(wk), _p(wt), Cout, Cin, KF, xfold, raw), "xfold_weights")
+        else:
+            wt = torch.empty(Cin * KF * KF * Cout, device=wk.device, dtype=torch.float32)
+            check(lib.gim_conv2d_transpose_weights(_p(wk), _p(wt), Cout, Cin, KF, raw), "transpose_weights")
+        ent = _WT_CACHE[slot] = _DerivedWeights(wt, version, weakref.ref(w, lambda _r, slot=slot: _WT_CACHE.pop(slot, None)))
+    return ent.use_on_current_stream(raw)
+
+
+def _conv_dgrad(lib, dy, x, wp, wf, sigma, sh, g, st, w=None, res_half=None):
+    """dx = lrelu'(x) * dgrad(dy, w) / sigma  (through the pool / sub-pixel folds when the forward used them), by the route
+    _dgrad_route names.  w: the weight parameter, where the caller has it.
+    res_half [N, H/2, W/2, Cin]: the gradient w.r.t. avgpool2(x) of a second reader of x (ConvForkPoolFn): 0.25 * up2(res_half) is added."""
+    route, J, add_res = _dgrad_route(g, sh.prec, w is not None, res_half is not None)
     if _FLOPS is not None:
-        _note_conv("dgrad", cfg, sh, 1)
-    mask = x if pre_slope != 1.0 else None
-    key = (N, H, W, Cin, Cout, KH, ups, 1 if pool else 0, fold)
-    wk = wf if fold else wp
-    # dgrad on cached transposed weights WT[Cin][KF][KF][Cout] (rows k-contiguous: the forward kernel's operand path, vector weight
-    # loads) for the gradient w.r.t. IMAGES (<= 8 input
-    # channels: 3 / 6 / 1), where the k-major kernel falls back to scalar weight loads (output channels not a multiple of 4)
-    # (fp16 matrix path: EVERY eligible dgrad goes this way - the fp16 kernel exists in the k-contiguous operand form only)
-    f16_t = sh.prec == 1 and Cout % 32 == 0 and Cin >= 32
-    if w is not None and Cout % 16 == 0 and not (ups and not fold) and ((Cin <= 8 and _NARROW_DGRAD_T) or f16_t):
-        J = _xfold_factor(Cin, W) if KH >= 3 and not (ups or pool or fold) and _NARROW_XFOLD and not f16_t else 0
-        if J:   # J adjacent dx pixels as the output columns of one stride-(1, J) convolution: 12 of 16 MFMA columns carry data
-            wx = _transposed(lib, w, wk, Cout, Cin, KH, xfold=J)
-            dx = torch.empty(tuple(x.shape), device=x.device, dtype=torch.float32)
-            check(lib.gim_conv2d_dgrad_xfold(_p(dy), _p(wx), _p(sigma), _p(mask), _p(dx), sh, J, st), "conv2d_dgrad_xfold")
-            return dx
-        wt = _transposed(lib, w, wk, Cout, Cin, KH + 1 if fold else KH)
-        dx = _conv_out(sh, 2, key, tuple(x.shape), x.device)
+        _note_conv("dgrad", g, sh, 1)
+    N, H, W, Cin, Cout, KH = g.N, g.H, g.W, g.Cin, g.Cout, g.KH
+    mask = x if g.pre_slope != 1.0 else None
+    wk = wf if g.fold else wp
+    if route == "xfold":
+        wx = _transposed(lib, w, wk, Cout, Cin, KH, xfold=J)
+        dx = torch.empty(tuple(x.shape), device=x.device, dtype=torch.float32)
+        check(lib.gim_conv2d_dgrad_xfold(_p(dy), _p(wx), _p(sigma), _p(mask), _p(dx), sh, J, st), "conv2d_dgrad_xfold")
+    elif route == "t":
+        wt = _transposed(lib, w, wk, Cout, Cin, KH + 1 if g.fold else KH)
+        dx = _conv_out(sh, 2, g.key, tuple(x.shape), x.device)
         check(lib.gim_conv2d_dgrad_t(_p(dy), _p(wt), _p(sigma), _p(mask), _p(dx), sh, st), "conv2d_dgrad_t")
-        return dx
-    if ups and not fold:
-        dxu = _conv_out(sh, 1, key, (N, H, W, Cin), dy.device)
+    elif route == "ups":
+        dxu = _conv_out(sh, 1, g.key, (N, H, W, Cin), dy.device)
         dx = torch.empty_like(x)
         check(lib.gim_conv2d_dgrad(_p(dy), _p(wk), _p(sigma), None, _p(dxu), sh, st), "conv2d_dgrad")
-        check(lib.gim_upsample2x_bwd(_p(dxu), _p(mask), pre_slope, _p(dx), N, H >> 1, W >> 1, Cin, st), "upsample2x_bwd")
+        check(lib.gim_upsample2x_bwd(_p(dxu), _p(mask), g.pre_slope, _p(dx), N, H >> 1, W >> 1, Cin, st), "upsample2x_bwd")
     else:
-        dx = _conv_out(sh, 1, key, tuple(x.shape), x.device)
-        check(lib.gim_conv2d_dgrad(_p(dy), _p(wk), _p(sigma), _p(mask), _p(dx), sh, st), "conv2d_dgrad")
+        dx = _conv_out(sh, 1, g.key, tuple(x.shape), x.device)
+        if route == "res":
+            check(lib.gim_conv2d_dgrad_res(_p(dy), _p(wk), _p(sigma), _p(mask), _p(_req(res_half, "res_half")), 0.25, _p(dx), sh, st), "conv2d_dgrad_res")
+        else:
+            check(lib.gim_conv2d_dgrad(_p(dy), _p(wk), _p(sigma), _p(mask), _p(dx), sh, st), "conv2d_dgrad")
+    if add_res:
+        out = torch.empty_like(dx)
+        check(lib.gim_add_avgpool2_bwd(_p(dx), _p(_req(res_half, "res_half")), _p(out), N, H, W, Cin, st), "add_avgpool2_bwd")
+        return out
     return dx
 
 
-def _conv_wgrad(lib, dy, x, w, wp, bias, sigma, u_s, v_s, sh, cfg, want_b, st, xp=None):
-    """(dw, db) of one convolution; either may come back None because it was ADDED into the parameter's .grad.
-    xp: the padded, activated copy of x that a forward in the row-contiguous form made (image layers): the queued path then takes
-    the weight gradient from it (gim_conv2d_wgrad_rows_acc)."""
-    N, H, W, Cin, Cout, KH, ups, pre_slope, has_bias, has_res, pool, fold, res_ups = cfg
+def _conv_wgrad(lib, dy, x, w, wp, bias, sigma, u_s, v_s, sh, g, want_b, st, xp=None):
+    """(dw, db) of one convolution, by the route _wgrad_route names; either may come back None because it was ADDED into the
+    parameter's .grad.  xp: the padded, activated copy of x that a forward in the row-contiguous form made (image layers)."""
     if _FLOPS is not None:
-        _note_conv("wgrad", cfg)
+        _note_conv("wgrad", g)
+    Cin, Cout, KH, ups, fold = g.Cin, g.Cout, g.KH, g.ups, g.fold
     dev = dy.device
     dw = db = None
-    Mo = N * (H >> 1) * (W >> 1) if pool else N * H * W  # pixels of dy
-    ns = 1   # pixel slices combined with float atomics; GIM_WGRAD_SLABS=1: deterministic slabs (non-queued path only)
-    if _WGRAD_SLABS or _DETERMINISTIC[0]:
-        ns = lib.gim_conv2d_wgrad_slabs(sh)
-        if ns <= 0:
-            check(ns, "conv2d_wgrad_slabs")
-    K = KH * KH * Cin
-    KFF = (KH + 1) * (KH + 1) * Cin if fold else K
+    Mo, K, KFF = g.out_pixels, g.K, g.KFF
     slab_bias = want_b and not (fold and ups)  # the role-swapped sub-pixel wgrad does not stream dy as its A operand
     # Megatron-style direct accumulation: when the parameter's .grad already exists as a dense buffer in the
     # weight's own memory order (FusedAdam's flat gradient bucket) and no higher-order graph is being built,
     # the finish kernels ADD into it and autograd gets None (no AccumulateGrad add kernel per parameter).
     acc_w = _grad_target(w) if (sigma is not None or not fold) and not torch.is_grad_enabled() else None
     acc_b = _grad_target(bias) if (slab_bias and acc_w is not None) else None
-    if acc_w is not None and wgrad_queue.enabled and not _DETERMINISTIC[0] and not (want_b and slab_bias and acc_b is None):
+    route, ns = _wgrad_route(g, sh, acc_w is not None, sigma is not None, want_b and slab_bias and acc_b is None,
+                             xp is not None and dy.is_contiguous())
+    fold_code = (2 if ups else 1) if fold else 0    # gim_wgrad_finish*: how the finish un-folds the raw gradient
+    queued = route in ("queued", "queued_rows")
+    if queued:
         q = _queue()
-        # deferred: raw gradient into an arena slot now, finish of all convs in two launches when backward ends
         n = Cout * K
         if Cout * KFF >= 1 << 31:
             raise RuntimeError("weight gradient of more than 2^31 elements (gim_wgrad_finish_batched indexes with 32 bits)")
         n_chunks = (n + q.CHUNK - 1) // q.CHUNK
-        rows = xp is not None and dy.is_contiguous()
+        rows = route == "queued_rows"
         src = q.take(Cout * KH * ((KH * Cin + 15) & ~15) if rows else Cout * KFF, dev)
         bsrc = q.take(Cout, dev) if slab_bias else None
         sn = sigma is not None
@@ -813,34 +889,32 @@ def _conv_wgrad(lib, dy, x, w, wp, bias, sigma, u_s, v_s, sh, cfg, want_b, st, x
         else:
             check(lib.gim_conv2d_wgrad_acc(_p(dy), _p(x), src, bsrc, sh, st), "conv2d_wgrad_acc")
         q.add((src, bsrc or 0, _p(wp) if sn else 0, _p(sigma) or 0, _p(u_s) or 0, _p(v_s) or 0, tmp or 0, part or 0,
-               _p(acc_w), _p(acc_b) or 0, Cout, Cin, KH, 3 if rows else ((2 if ups else 1) if fold else 0), n_chunks), (sigma, u_s, v_s))
-        if want_b and not slab_bias:
-            scr = torch.empty(256 * Cout, device=dev, dtype=torch.float32)
-            tgt_b = _grad_target(bias)
-            if tgt_b is not None:
-                check(lib.gim_colsum_acc(_p(dy), _p(tgt_b), _p(scr), Mo, Cout, st), "colsum_acc")
-            else:
-                db = torch.empty(Cout, device=dev, dtype=torch.float32)
-                check(lib.gim_colsum(_p(dy), _p(db), _p(scr), Mo, Cout, st), "colsum")
-        return None, db
-    dwp = torch.empty(Cout * K, device=dev, dtype=torch.float32)
-    if want_b and acc_b is None:
-        db = torch.empty(Cout, device=dev, dtype=torch.float32)
-    if ns == 1 and sigma is None and not fold and acc_w is None:
-        check(lib.gim_conv2d_wgrad(_p(dy), _p(x), _p(dwp), _p(db) if slab_bias else None, 1, sh, st), "conv2d_wgrad")
+               _p(acc_w), _p(acc_b) or 0, Cout, Cin, KH, 3 if rows else fold_code, n_chunks), (sigma, u_s, v_s))
     else:
-        slabs = torch.empty(ns * Cout * KFF, device=dev, dtype=torch.float32)
-        bslabs = torch.empty(ns * Cout, device=dev, dtype=torch.float32) if slab_bias else None
-        scratch = torch.empty(512 + (Cout * KFF if fold else 0), device=dev, dtype=torch.float32)
-        check(lib.gim_conv2d_wgrad(_p(dy), _p(x), _p(slabs), _p(bslabs), ns, sh, st), "conv2d_wgrad")
-        check(lib.gim_wgrad_finish(_p(slabs), _p(bslabs), ns, _p(wp), _p(sigma), _p(u_s), _p(v_s), _p(dwp),
-                                   _p(db) if (slab_bias and acc_b is None) else None, _p(scratch), Cout, Cin, KH,
-                                   (2 if ups else 1) if fold else 0, _p(acc_w), _p(acc_b), st), "wgrad_finish")
-    if want_b and not slab_bias:
+        dwp = torch.empty(Cout * K, device=dev, dtype=torch.float32)
+        if want_b and acc_b is None:
+            db = torch.empty(Cout, device=dev, dtype=torch.float32)
+        if route == "direct":
+            check(lib.gim_conv2d_wgrad(_p(dy), _p(x), _p(dwp), _p(db) if slab_bias else None, 1, sh, st), "conv2d_wgrad")
+        else:
+            slabs = torch.empty(ns * Cout * KFF, device=dev, dtype=torch.float32)
+            bslabs = torch.empty(ns * Cout, device=dev, dtype=torch.float32) if slab_bias else None
+            scratch = torch.empty(512 + (Cout * KFF if fold else 0), device=dev, dtype=torch.float32)
+            check(lib.gim_conv2d_wgrad(_p(dy), _p(x), _p(slabs), _p(bslabs), ns, sh, st), "conv2d_wgrad")
+            check(lib.gim_wgrad_finish(_p(slabs), _p(bslabs), ns, _p(wp), _p(sigma), _p(u_s), _p(v_s), _p(dwp),
+                                       _p(db) if (slab_bias and acc_b is None) else None, _p(scratch), Cout, Cin, KH,
+                                       fold_code, _p(acc_w), _p(acc_b), st), "wgrad_finish")
+        if acc_w is None:
+            dw = dwp.view(Cout, KH, KH, Cin).permute(0, 3, 1, 2) if w.dim() == 4 else dwp.view(Cout, Cin)
+    if want_b and not slab_bias:    # the bias gradient as a column sum of dy of its own (queued: into .grad where that exists)
         scr = torch.empty(256 * Cout, device=dev, dtype=torch.float32)
-        check(lib.gim_colsum(_p(dy), _p(db), _p(scr), Mo, Cout, st), "colsum")
-    if acc_w is None:
-        dw = dwp.view(Cout, KH, KH, Cin).permute(0, 3, 1, 2) if w.dim() == 4 else dwp.view(Cout, Cin)
+        tgt_b = _grad_target(bias) if queued else None
+        if tgt_b is not None:
+            check(lib.gim_colsum_acc(_p(dy), _p(tgt_b), _p(scr), Mo, Cout, st), "colsum_acc")
+        else:
+            if db is None:
+                db = torch.empty(Cout, device=dev, dtype=torch.float32)
+            check(lib.gim_colsum(_p(dy), _p(db), _p(scr), Mo, Cout, st), "colsum")
     return dw, db
 
 
@@ -848,44 +922,42 @@ class ConvDgradFn(Function):
     """The first-order input gradient of ConvFn as an operator of (dy, w):  dx = lrelu'(x) * conv^T(dy, w / sigma(w)).
     It is bilinear in (dy, w/sigma), so its own adjoints are the other two kernels of the same convolution:
     d/d(dy) is the FORWARD conv of the masked cotangent and d/dw is the WGRAD with that cotangent in the role of
-    the layer input (followed by the same spectral-norm chain rule).  The mask is piecewise constant in x."""
+    the layer input (followed by the same spectral-norm chain rule).  The mask is piecewise constant in x.  (geom: ConvFn's, never upsampling.)"""
+    N_EXTRA = 6    # forward's inputs behind (dy, w)
 
     @staticmethod
-    def forward(ctx, dy, w, x, sigma, u_s, v_s, wf, cfg):
-        lib = _lib.load()
-        N, H, W, Cin, Cout, KH, ups, pre_slope, has_bias, has_res, pool, fold, res_ups = cfg
-        sh = _shape(N, H, W, Cin, Cout, KH, 0, pre_slope, 1 if pool else 0, fold, 0)
-        dx = _conv_dgrad(lib, dy, x, weight_phys(w), wf, sigma, sh, cfg, _stream(), w)
+    def forward(ctx, dy, w, x, sigma, u_s, v_s, wf, geom):
+        dx = _conv_dgrad(_lib.load(), dy, x, weight_phys(w), wf, sigma, geom.shape(None), geom, _stream(), w)
         ctx.save_for_backward(dy, w, x, sigma, u_s, v_s, wf)
-        ctx.cfg = cfg
+        ctx.cfg = geom
         return dx
 
     @staticmethod
     def backward(ctx, g):
         lib = _lib.load()
         dy, w, x, sigma, u_s, v_s, wf = ctx.saved_tensors
-        N, H, W, Cin, Cout, KH, ups, pre_slope, has_bias, has_res, pool, fold, res_ups = ctx.cfg
+        geom = ctx.cfg
         if torch.is_grad_enabled():
             raise NotImplementedError("third-order gradients are not supported")
         g = _req(g, "g")
         st = _stream()
         wp = weight_phys(w)
-        if pre_slope != 1.0:
+        if geom.pre_slope != 1.0:
             gm = torch.empty_like(g)
-            check(lib.gim_lrelu_mask_mul(_p(g), _p(x), pre_slope, _p(gm), g.numel(), st), "lrelu_mask_mul")
+            check(lib.gim_lrelu_mask_mul(_p(g), _p(x), geom.pre_slope, _p(gm), g.numel(), st), "lrelu_mask_mul")
         else:
             gm = g
-        lin = (N, H, W, Cin, Cout, KH, 0, 1.0, False, False, pool, fold, False)   # the conv as a linear map: no prologue, bias, residual
-        sh = _shape(N, H, W, Cin, Cout, KH, 0, 1.0, 1 if pool else 0, fold, 0)
+        lin = geom.linear_map()
+        sh = lin.shape(None)
         g_dy = g_w = None
         if ctx.needs_input_grad[0]:
             g_dy = torch.empty_like(dy)
-            check(lib.gim_conv2d_fwd(_p(gm), _p(wf if fold else wp), None, _p(sigma), None, _p(g_dy), sh, st), "conv2d_fwd")
+            check(lib.gim_conv2d_fwd(_p(gm), _p(wf if lin.fold else wp), None, _p(sigma), None, _p(g_dy), sh, st), "conv2d_fwd")
             if _FLOPS is not None:
                 _note_conv("fwd", lin, sh, 0)
         if ctx.needs_input_grad[1]:
             g_w, _ = _conv_wgrad(lib, dy, gm, w, wp, None, sigma, u_s, v_s, sh, lin, False, st)
-        return g_dy, g_w, None, None, None, None, None, None
+        return (g_dy, g_w) + (None,) * ConvDgradFn.N_EXTRA
 
 
 def _grad_target(p):
@@ -927,18 +999,10 @@ def conv2d_post_act(x, w, bias=None, res=None, sigma=None, u_s=None, v_s=None, u
     """conv2d whose output may be stored ACTIVATED, y_stored = lrelu(y, post_slope), for a consumer conv that is the only reader
     of y and is then called with x_act=True (it skips its per-tap LeakyReLU in forward and wgrad; its dgrad masks by the sign,
     which activation does not change, and hands back the gradient w.r.t. the RAW y - so this conv's backward is unchanged).
-    Returns (y_stored, activated): launches that split K cannot activate (their slices combine by addition) and return raw y."""
-    act = False
-    if _ACT_STORAGE and post_slope != 1.0 and x.dim() == 4:
-        # decided HERE, for this call's own shape, and handed to ConvFn as the resolved slope: nothing about the stored form of y
-        # travels through module state (another conv running in between could not change what this call reports)
-        N, Hs, Ws, Cin = x.shape
-        Cout, KH = w.shape[0], (w.shape[2] if w.dim() == 4 else 1)
-        H, W = Hs << ups, Ws << ups
-        fold = 1 if (pool or (ups and KH > 1)) else 0
-        key = (N, H, W, Cin, Cout, KH, ups, 1 if pool else 0, fold)
-        sh = _tuned(_shape(N, H, W, Cin, Cout, KH, ups, pre_slope, 1 if pool else 0, fold, 1 if res_ups else 0), "fwd", key)
-        act = _merged_subpixel(x, w, ups, res, sh) or not _splits_k(sh, 0, key)   # (the stacked form activates in its depth-to-space copy)
+    Returns (y_stored, activated): launches that split K cannot activate (their slices combine by addition) and return raw y.
+    Decided HERE, for this call's own shape, and handed to ConvFn as the resolved slope: nothing about the stored form of y
+    travels through module state (another conv running in between could not change what this call reports)."""
+    act = post_slope != 1.0 and _stores_activated(ConvGeom.of(x, w, ups, pre_slope, pool, res_ups, bias, res, x_act), post_slope)
     y = ConvFn.apply(x, w, bias, res, sigma, u_s, v_s, ups, pre_slope, pool, res_ups, wf, guard, post_slope if act else 1.0, x_act)
     return y, act
 
@@ -953,34 +1017,27 @@ class ConvForkPoolFn(Function):
 
     @staticmethod
     def forward(ctx, x, w, bias, res, sigma, u_s, v_s, ups, pre_slope, pool, res_ups, wf, guard, post_slope, x_act, in_slope):
-        lib = _lib.load()
-        x = _req(x, "x")
-        N, H, W, C = x.shape
-        pooled = torch.empty((N, H // 2, W // 2, C), device=x.device, dtype=torch.float32)
-        if in_slope != 1.0:
-            check(lib.gim_avgpool2_fwd_act(_p(x), _p(pooled), N, H, W, C, in_slope, _stream()), "avgpool2_fwd_act")
-        else:
-            check(lib.gim_avgpool2_fwd(_p(x), _p(pooled), N, H, W, C, _stream()), "avgpool2_fwd")
+        x, pooled = _avgpool2(x, in_slope)
         y = ConvFn.forward(ctx, x, w, bias, None, sigma, u_s, v_s, 0, pre_slope, False, False, None, guard, post_slope, x_act)
         return y, pooled
 
     @staticmethod
     def backward(ctx, dy, dpooled):
-        N, H, W, Cin = ctx.cfg[0], ctx.cfg[1], ctx.cfg[2], ctx.cfg[3]
+        x_shape = (ctx.cfg.N, ctx.cfg.H, ctx.cfg.W, ctx.cfg.Cin)
         if dy is None:      # the conv branch is unused: only the pool's backward
-            return (AvgPool2BwdFn.apply(dpooled, (N, H, W, Cin)) if dpooled is not None else None,) + (None,) * 15
+            return (AvgPool2BwdFn.apply(dpooled, x_shape) if dpooled is not None else None,) + (None,) * (3 + ConvFn.N_EXTRA + 1)
         if dpooled is not None and (torch.is_grad_enabled() or not ctx.needs_input_grad[0]):
             # second-order pass (R1) - or no input gradient wanted at all: the unfused sum of differentiable pieces
             grads = ConvFn.backward(ctx, dy)
-            gp = AvgPool2BwdFn.apply(dpooled, (N, H, W, Cin)) if ctx.needs_input_grad[0] else None
+            gp = AvgPool2BwdFn.apply(dpooled, x_shape) if ctx.needs_input_grad[0] else None
             dx = gp if grads[0] is None else (grads[0] if gp is None else grads[0] + gp)
-            return (dx,) + tuple(grads[1:]) + (None,)
+            return (dx,) + grads[1:] + (None,)
         ctx.dgrad_res = dpooled
         try:
             grads = ConvFn.backward(ctx, dy)
         finally:
             ctx.dgrad_res = None
-        return tuple(grads) + (None,)
+        return grads + (None,)
 
 
 _FUSED_FORKPOOL = os.environ.get("GIM_NO_FUSED_FORKPOOL") is None   # A/B switch (host side)
@@ -989,13 +1046,7 @@ _FUSED_FORKPOOL = os.environ.get("GIM_NO_FUSED_FORKPOOL") is None   # A/B switch
 def conv2d_forkpool(x, w, bias, sigma, u_s, v_s, pre_slope, guard, post_slope, x_act, in_slope):
     """-> (y_stored, activated, pooled): conv2d_post_act of a plain convolution plus avgpool2 of its (raw) input, as ONE autograd node
     whose backward folds the pooled branch's gradient into the dgrad epilogue (ConvForkPoolFn)."""
-    act = False
-    N, H, W, Cin = x.shape
-    Cout, KH = w.shape[0], w.shape[2]
-    if _ACT_STORAGE and post_slope != 1.0:
-        key = (N, H, W, Cin, Cout, KH, 0, 0, 0)
-        sh = _tuned(_shape(N, H, W, Cin, Cout, KH, 0, pre_slope), "fwd", key)
-        act = not _splits_k(sh, 0, key)
+    act = post_slope != 1.0 and _stores_activated(ConvGeom.of(x, w, 0, pre_slope, False, False, bias, None, x_act), post_slope)
     ps = post_slope if act else 1.0
     if _FUSED_FORKPOOL and x.requires_grad and torch.is_grad_enabled():
         y, pooled = ConvForkPoolFn.apply(x, w, bias, None, sigma, u_s, v_s, 0, pre_slope, False, False, None, guard, ps, x_act, in_slope)
@@ -1076,10 +1127,8 @@ class GroupedLinearFn(Function):
         jobs = [(_p(x), _p(w), _p(y), _p(b) or 0, M, n_, K, n_, K, 1, 1, K, 0) for w, b, y, n_ in zip(ws, bs, ys, sizes)]
         dj, dt, nt, _ = _gemm_tables(jobs)
         check(lib.gim_bgemm_grouped(dj.data_ptr(), dt.data_ptr(), nt, _stream()), "bgemm_grouped")
-        if _FLOPS is not None:
-            for n_ in sizes:
-                ent = _FLOPS.setdefault(("bgemm", (1, M, n_, K)), [0, 2.0 * M * n_ * K])
-                ent[0] += 1
+        for n_ in sizes:
+            _note_bgemm(1, M, n_, K)
         ctx.save_for_backward(x, *wb)
         return tuple(ys)
 
@@ -1111,9 +1160,7 @@ class GroupedLinearFn(Function):
                     if tgt is None:
                         gb = torch.empty_like(b)
                     cjobs.append((_p(dy), 0, _p(tgt if tgt is not None else gb), 0, M, n_, 0, 0, n_, 1, 0, 0, 1 if tgt is not None else 0))
-                if _FLOPS is not None:
-                    ent = _FLOPS.setdefault(("bgemm", (1, M, n_, K)), [0, 2.0 * M * n_ * K])
-                    ent[0] += 2
+                _note_bgemm(1, M, n_, K, 2)
             grads += [gw, gb]
         if jobs:
             dj, dt, nt, _ = _gemm_tables(jobs)
@@ -1210,6 +1257,19 @@ def act_storage():
 # --------------------------------------------------------------------------------------------
 # pooling / pointwise
 # --------------------------------------------------------------------------------------------
+def _avgpool2(x, in_slope):
+    """-> (x checked, avgpool2 of the raw x); in_slope != 1: x is stored activated and the kernel inverts that on the fly."""
+    lib = _lib.load()
+    x = _req(x, "x")
+    N, H, W, C = x.shape
+    y = torch.empty((N, H // 2, W // 2, C), device=x.device, dtype=torch.float32)
+    if in_slope != 1.0:
+        check(lib.gim_avgpool2_fwd_act(_p(x), _p(y), N, H, W, C, in_slope, _stream()), "avgpool2_fwd_act")
+    else:
+        check(lib.gim_avgpool2_fwd(_p(x), _p(y), N, H, W, C, _stream()), "avgpool2_fwd")
+    return x, y
+
+
 class AvgPool2Fn(Function):
     """2x2 average pool.  in_slope != 1: x is stored ACTIVATED (lrelu(x, in_slope) written by its producer for the conv that reads
     it next to this pool); the kernel inverts the activation on the fly.  The gradient handed back is w.r.t. the RAW x - what
@@ -1217,15 +1277,8 @@ class AvgPool2Fn(Function):
 
     @staticmethod
     def forward(ctx, x, in_slope=1.0):
-        lib = _lib.load()
-        x = _req(x, "x")
-        N, H, W, C = x.shape
-        y = torch.empty((N, H // 2, W // 2, C), device=x.device, dtype=torch.float32)
-        if in_slope != 1.0:
-            check(lib.gim_avgpool2_fwd_act(_p(x), _p(y), N, H, W, C, in_slope, _stream()), "avgpool2_fwd_act")
-        else:
-            check(lib.gim_avgpool2_fwd(_p(x), _p(y), N, H, W, C, _stream()), "avgpool2_fwd")
-        ctx.cfg = (N, H, W, C)
+        x, y = _avgpool2(x, in_slope)
+        ctx.cfg = tuple(x.shape)
         return y
 
     @staticmethod
@@ -1293,15 +1346,8 @@ class ForkPoolFn(Function):
 
     @staticmethod
     def forward(ctx, x, in_slope):
-        lib = _lib.load()
-        x = _req(x, "x")
-        N, H, W, C = x.shape
-        y = torch.empty((N, H // 2, W // 2, C), device=x.device, dtype=torch.float32)
-        if in_slope != 1.0:
-            check(lib.gim_avgpool2_fwd_act(_p(x), _p(y), N, H, W, C, in_slope, _stream()), "avgpool2_fwd_act")
-        else:
-            check(lib.gim_avgpool2_fwd(_p(x), _p(y), N, H, W, C, _stream()), "avgpool2_fwd")
-        ctx.cfg = (N, H, W, C)
+        x, y = _avgpool2(x, in_slope)
+        ctx.cfg = tuple(x.shape)
         return x.view_as(x), y
 
     @staticmethod
@@ -1495,9 +1541,7 @@ class ToNCHWFn(Function):
 # self-attention core
 # --------------------------------------------------------------------------------------------
 def _bgemm(A, B, C, batch, M, N, K, sA, sB):
-    if _FLOPS is not None:
-        ent = _FLOPS.setdefault(("bgemm", (batch, M, N, K)), [0, 2.0 * batch * M * N * K])
-        ent[0] += 1
+    _note_bgemm(batch, M, N, K)
     check(_lib.load().gim_bgemm(_p(A), _p(B), _p(C), batch, M, N, K, sA[0], sA[1], sA[2], sB[0], sB[1], sB[2], _stream()), "bgemm")
 
 
@@ -1594,9 +1638,7 @@ class AttnProbFn(Function):
         f, g = _req(f, "f"), _req(g, "g")
         nb, T, K = f.shape
         A = torch.empty((nb, T, T), device=f.device, dtype=torch.float32)
-        if _FLOPS is not None:
-            ent = _FLOPS.setdefault(("bgemm", (nb, T, T, K)), [0, 2.0 * nb * T * T * K])
-            ent[0] += 1
+        _note_bgemm(nb, T, T, K)
         check(_lib.load().gim_attn_prob_fwd(_p(f), _p(g), _p(A), nb, T, K, _stream()), "attn_prob_fwd")
         ctx.save_for_backward(f, g, A)
         return A
@@ -1766,39 +1808,15 @@ class HeadCatFn(Function):
 
     @staticmethod
     def backward(ctx, dout):
-        lib = _lib.load()
         ts, te, ss, se, ft, fs = ctx.saved_tensors
         dout = _req(dout, "dout")
-        B, n, Ds = ts.shape
-        k = ss.shape[1]
-        De, Df = te.shape[2], ft.shape[2]
-        L = dout.shape[1]
-        st = _stream()
+        Ds, De, Df = ts.shape[2], te.shape[2], ft.shape[2]
         o_te = 2 * Ds
         o_se = o_te + 2 * De + Df
-        need = ctx.needs_input_grad
-        grads = [None] * 6
-
         second = _second_order()
-
-        def bwd(i, x, t, D, o_mean, o_std):
-            if not need[i]:
-                return
-            if second:
-                grads[i] = SetStatsBwdFn.apply(dout, x, o_mean, o_std)
-                return
-            dx = torch.empty_like(x)
-            check(lib.gim_set_stats_bwd(_p(x), _p(dout, o_mean), (_p(dout, o_std) if o_std is not None else None), _p(dx),
-                                        B, t, D, L, L, st), "set_stats_bwd")
-            grads[i] = dx
-
-        bwd(0, ts, n, Ds, 0, None)
-        bwd(1, te, n, De, o_te, o_te + De)
-        bwd(2, ss, k, Ds, Ds, None)
-        bwd(3, se, k, De, o_se, o_se + De)
-        bwd(4, ft, n, Df, o_te + 2 * De, None)
-        bwd(5, fs, k, Df, o_se + 2 * De, None)
-        return tuple(grads)
+        slots = ((ts, 0, None), (te, o_te, o_te + De), (ss, Ds, None), (se, o_se, o_se + De), (ft, o_te + 2 * De, None), (fs, o_se + 2 * De, None))
+        return tuple(_set_stats_bwd(dout, x, o_mean, o_std, second) if need else None
+                     for (x, o_mean, o_std), need in zip(slots, ctx.needs_input_grad))
 
 
 class StatCatFn(Function):
@@ -1822,29 +1840,28 @@ class StatCatFn(Function):
 
     @staticmethod
     def backward(ctx, dout):
-        lib = _lib.load()
         x, fc = ctx.saved_tensors
         dout = _req(dout, "dout")
-        B, t, D = x.shape
-        Df = fc.shape[2]
-        L = dout.shape[1]
-        st = _stream()
+        D = x.shape[2]
         second = _second_order()
-        grads = [None, None]
-        for i, (src, Dn, o_mean, o_std) in enumerate(((x, D, 0, D), (fc, Df, 2 * D, None))):
-            if not ctx.needs_input_grad[i]:
-                continue
-            if second:
-                grads[i] = SetStatsBwdFn.apply(dout, src, o_mean, o_std)
-                continue
-            dx = torch.empty_like(src)
-            check(lib.gim_set_stats_bwd(_p(src), _p(dout, o_mean), (_p(dout, o_std) if o_std is not None else None), _p(dx),
-                                        B, t, Dn, L, L, st), "set_stats_bwd")
-            grads[i] = dx
-        return tuple(grads)
+        return tuple(_set_stats_bwd(dout, src, o_mean, o_std, second) if need else None
+                     for (src, o_mean, o_std), need in zip(((x, 0, D), (fc, 2 * D, None)), ctx.needs_input_grad))
 
 
 stat_cat = StatCatFn.apply
+
+
+def _set_stats_bwd(dout, x, o_mean, o_std, second):
+    """Gradient w.r.t. x [B, t, D] of one mean (o_std None) / [mean, custom_std] slot at columns o_mean / o_std of the row dout
+    [B, L] (gim_set_stats_bwd); second: as the differentiable operator SetStatsBwdFn (R1)."""
+    if second:
+        return SetStatsBwdFn.apply(dout, x, o_mean, o_std)
+    B, t, D = x.shape
+    L = dout.shape[1]
+    dx = torch.empty_like(x)
+    check(_lib.load().gim_set_stats_bwd(_p(x), _p(dout, o_mean), (_p(dout, o_std) if o_std is not None else None), _p(dx),
+                                        B, t, D, L, L, _stream()), "set_stats_bwd")
+    return dx
 
 
 class SetStatsBwdFn(Function):
@@ -1854,11 +1871,7 @@ class SetStatsBwdFn(Function):
     @staticmethod
     def forward(ctx, dout, x, o_mean, o_std):
         dout, x = _req(dout, "dout"), _req(x, "x")
-        B, t, D = x.shape
-        L = dout.shape[1]
-        dx = torch.empty_like(x)
-        check(_lib.load().gim_set_stats_bwd(_p(x), _p(dout, o_mean), (_p(dout, o_std) if o_std is not None else None), _p(dx),
-                                            B, t, D, L, L, _stream()), "set_stats_bwd")
+        dx = _set_stats_bwd(dout, x, o_mean, o_std, False)
         ctx.save_for_backward(dout, x)
         ctx.o = (o_mean, o_std)
         return dx
@@ -1965,25 +1978,12 @@ class MeanStdCatFn(Function):
 
     @staticmethod
     def backward(ctx, dout):
-        lib = _lib.load()
         xs = ctx.saved_tensors
         dout = _req(dout, "dout")
-        B, _, D = xs[0].shape
-        L = dout.shape[1]
-        st = _stream()
-        grads = []
+        D = xs[0].shape[2]
         second = _second_order()
-        for i, x in enumerate(xs):
-            if not ctx.needs_input_grad[i]:
-                grads.append(None)
-                continue
-            if second:
-                grads.append(SetStatsBwdFn.apply(dout, x, 2 * D * i, 2 * D * i + D))
-                continue
-            dx = torch.empty_like(x)
-            check(lib.gim_set_stats_bwd(_p(x), _p(dout, 2 * D * i), _p(dout, 2 * D * i + D), _p(dx), B, x.shape[1], D, L, L, st), "set_stats_bwd")
-            grads.append(dx)
-        return tuple(grads)
+        return tuple(_set_stats_bwd(dout, x, 2 * D * i, 2 * D * i + D, second) if ctx.needs_input_grad[i] else None
+                     for i, x in enumerate(xs))
 
 
 def mean_std_cat(*xs):

@@ -540,3 +540,141 @@ def test_model_train_eval_switch_every_submodule():
         assert not any(m.training for m in net.modules())
         with pytest.raises(ValueError):
             net.train("yes")
+
+
+# The conv calls of the benchmark networks (vox64 at 16 episodes, om32 at 32) and their neighbours just across each predicate.
+#  name, (N, H, W, Cin, Cout, KH, ups, pre_slope, pool, res_ups, has_res, linear),
+#  expected: fwd (tune_tile 0), fwd (tune_tile -1), dgrad, dgrad without the parameter, dgrad + res_half, dgrad fp16, dgrad fp16 + res_half,
+#            wgrad into .grad, wgrad with an untargeted bias, wgrad without a target, wgrad without target and spectral norm
+_X4, _X2, _T, _P, _U, _R = ("xfold", 4), ("xfold", 2), ("t", 0), ("plain", 0), ("ups", 0), ("res", 0)
+_Q, _QR, _S, _D = ("queued", 1), ("queued_rows", 1), ("slabs", 1), ("direct", 1)
+_ROUTE_ROWS = [
+    ("img 9x9 3->64", (240, 64, 64, 3, 64, 9, 0, 1.0, False, False, False, False),             ("rows", "plain", _X4, _P, _X4 + (True,), _X4, _X4 + (True,), _QR, _S, _S, _D)),
+    ("img 9x9 6->64", (80, 64, 64, 6, 64, 9, 0, 1.0, False, False, False, False),              ("rows", "plain", _X4, _P, _X4 + (True,), _X4, _X4 + (True,), _QR, _S, _S, _D)),
+    ("img 9x9 1->64 (om32)", (480, 32, 32, 1, 64, 9, 0, 1.0, False, False, False, False),      ("rows", "plain", _X4, _P, _X4 + (True,), _X4, _X4 + (True,), _QR, _S, _S, _D)),
+    ("img 9x9 2->64 (om32)", (160, 32, 32, 2, 64, 9, 0, 1.0, False, False, False, False),      ("rows", "plain", _X4, _P, _X4 + (True,), _X4, _X4 + (True,), _QR, _S, _S, _D)),
+    ("img 9x9 8->64", (16, 64, 64, 8, 64, 9, 0, 1.0, False, False, False, False),              ("plain", "plain", _X2, _P, _X2 + (True,), _X2, _X2 + (True,), _Q, _S, _S, _D)),
+    ("img 3x3 7->64 lrelu", (16, 64, 64, 7, 64, 3, 0, 0.2, False, False, False, False),        ("rows", "plain", _X2, _P, _X2 + (True,), _X2, _X2 + (True,), _QR, _S, _S, _D)),
+    ("img 3x3 3->64 W=2 lrelu", (16, 2, 2, 3, 64, 3, 0, 0.2, False, False, False, False),      ("rows", "plain", _T, _P, _T + (True,), _T, _T + (True,), _QR, _S, _S, _D)),
+    ("img 3x3 3->3", (16, 64, 64, 3, 3, 3, 0, 1.0, False, False, False, False),                ("plain", "plain", _P, _P, _P + (True,), _P, _P + (True,), _Q, _S, _S, _D)),
+    ("img 1x1 3->64", (240, 64, 64, 3, 64, 1, 0, 1.0, False, False, False, False),             ("plain", "plain", _T, _P, _T + (True,), _T, _T + (True,), _Q, _S, _S, _D)),
+    ("out 9x9 64->3 ups", (80, 64, 64, 64, 3, 9, 1, 0.2, False, False, False, False),          ("subpixel", "plain", _P, _P, _P + (True,), _P, _P + (True,), _Q, _S, _S, _S)),
+    ("out 9x9 64->1 ups (om32)", (160, 32, 32, 64, 1, 9, 1, 0.2, False, False, False, False),  ("subpixel", "plain", _P, _P, _P + (True,), _P, _P + (True,), _Q, _S, _S, _S)),
+    ("out 9x9 64->3 ups + res", (80, 64, 64, 64, 3, 9, 1, 0.2, False, False, True, False),     ("plain", "plain", _P, _P, _P + (True,), _P, _P + (True,), _Q, _S, _S, _S)),
+    ("out 7x7 64->3 ups", (80, 64, 64, 64, 3, 7, 1, 0.2, False, False, False, False),          ("plain", "plain", _P, _P, _P + (True,), _P, _P + (True,), _Q, _S, _S, _S)),
+    ("pool 3x3 64->128 + res", (240, 64, 64, 64, 128, 3, 0, 0.2, True, False, True, False),    ("plain", "plain", _P, _P, _P + (True,), _T, _T + (True,), _Q, _S, _S, _S)),
+    ("subpixel 3x3 512->256", (80, 16, 16, 512, 256, 3, 1, 0.2, False, False, False, False),   ("plain", "plain", _P, _P, _P + (True,), _T, _T + (True,), _Q, _S, _S, _S)),
+    ("ups 1x1 512->256", (80, 16, 16, 512, 256, 1, 1, 1.0, False, False, False, False),        ("plain", "plain", _U, _U, _U + (True,), _U, _U + (True,), _Q, _S, _S, _D)),
+    ("skip 1x1 64->128", (240, 32, 32, 64, 128, 1, 0, 1.0, False, False, False, False),        ("plain", "plain", _P, _P, _P + (True,), _T, _T + (True,), _Q, _S, _S, _D)),
+    ("plain 3x3 64->64 lrelu", (240, 64, 64, 64, 64, 3, 0, 0.2, False, False, False, False),   ("plain", "plain", _P, _P, _R + (False,), _T, _T + (True,), _Q, _S, _S, _D)),
+    ("plain 3x3 128->128", (240, 32, 32, 128, 128, 3, 0, 1.0, False, False, False, False),     ("plain", "plain", _P, _P, _P + (True,), _T, _T + (True,), _Q, _S, _S, _D)),
+    ("res_ups 3x3 256->256", (80, 32, 32, 256, 256, 3, 0, 0.2, False, True, True, False),      ("plain", "plain", _P, _P, _R + (False,), _T, _T + (True,), _Q, _S, _S, _D)),
+    ("small map 3x3 512->512", (240, 4, 4, 512, 512, 3, 0, 0.2, False, False, False, False),   ("plain", "plain", _P, _P, _R + (False,), _T, _T + (True,), _Q, _S, _S, _D)),
+    ("plain 3x3 64->40 lrelu", (16, 16, 16, 64, 40, 3, 0, 0.2, False, False, False, False),    ("plain", "plain", _P, _P, _R + (False,), _P, _R + (False,), _Q, _S, _S, _D)),
+    ("linear 512->512", (16, 1, 1, 512, 512, 1, 0, 1.0, False, False, False, True),            ("plain", "plain", _P, _P, _P + (True,), _T, _T + (True,), _Q, _S, _S, _D)),
+    ("linear 8192->512 lrelu", (16, 1, 1, 8192, 512, 1, 0, 0.2, False, False, False, True),    ("plain", "plain", _P, _P, _R + (False,), _T, _T + (True,), _Q, _S, _S, _D)),
+]
+# gim_conv2d_wgrad_slabs of each row's shape (the library's answer on the parent commit; it is the same in deterministic mode)
+_ROUTE_SLABS = [512, 512, 960, 320, 128, 512, 1, 512, 1024, 205, 320, 205, 160, 128, 8, 40, 480, 205, 114, 29, 8, 32, 1, 1]
+
+
+def _route_table(ops):
+    out = []
+    for name, (N, H, W, Cin, Cout, KH, ups, slope, pool, res_ups, has_res, linear), _ in _ROUTE_ROWS:
+        g = ops.ConvGeom.make(N, H, W, Cin, Cout, KH, ups, slope, pool, res_ups, has_res=has_res, linear=linear)
+        assert g.key == (N, H, W, Cin, Cout, KH, ups, int(pool), g.fold) and g.fold == int(bool(pool or (ups and KH > 1))), name
+        sh = g.shape("wgrad")
+        rows_copy = ops._fwd_route(g, 0) == "rows"      # the padded copy exists where the forward made it
+        dg = [ops._dgrad_route(g, 0, True), ops._dgrad_route(g, 0, False), ops._dgrad_route(g, 0, True, True),
+              ops._dgrad_route(g, 1, True), ops._dgrad_route(g, 1, True, True)]
+        out.append((ops._fwd_route(g, 0), ops._fwd_route(g, -1), dg[0][:2], dg[1][:2], dg[2], dg[3][:2], dg[4],
+                    ops._wgrad_route(g, sh, True, True, False, rows_copy), ops._wgrad_route(g, sh, True, True, True, rows_copy),
+                    ops._wgrad_route(g, sh, False, True), ops._wgrad_route(g, sh, False, False)))
+        assert not (dg[0][2] or dg[1][2] or dg[3][2]), name      # nothing to add without a res_half
+    return out
+
+
+def test_conv_routes_are_the_parent_commits_inline_dispatch():
+    """ops._fwd_route / _dgrad_route / _wgrad_route on the conv calls of the benchmark networks.  The expected tags are literals:
+    they were obtained by evaluating the inline conditions of ConvFn.forward, _conv_dgrad and _conv_wgrad of the commit before the
+    route functions existed on these rows (not by running the functions under test).  Then every A/B switch, deterministic mode and
+    the queue switch: each moves exactly the routes it names - the expectations under a switch are the same literals with that one
+    substitution, which is what the parent's conditions gave, row by row."""
+    from optimalstrategiesagainstgenerativeattacks_amd import ops
+    assert not ops.deterministic() and ops.matrix_path() == "fp32" and ops.wgrad_queue.enabled and not ops._WGRAD_SLABS
+    assert ops._ROWS_FORM and ops._MERGED_SUBPIXEL and ops._NARROW_DGRAD_T and ops._NARROW_XFOLD
+    base = [e for _, _, e in _ROUTE_ROWS]
+    got = _route_table(ops)
+    for (name, _, want), have in zip(_ROUTE_ROWS, got):
+        assert have == want, (name, have, want)
+
+    def flipped(setter, restore, expect):
+        setter()
+        try:
+            have = _route_table(ops)
+        finally:
+            restore()
+        want = [expect(i, e) for i, e in enumerate(base)]
+        for (name, _, _), h, w_ in zip(_ROUTE_ROWS, have, want):
+            assert h == w_, (name, h, w_)
+        assert have != base      # the switch does move something on this table
+        assert _route_table(ops) == base
+
+    def module_switch(name, value, expect):
+        old = getattr(ops, name)
+        flipped(lambda: setattr(ops, name, value), lambda: setattr(ops, name, old), expect)
+
+    def sub(e, cols, fn):
+        return tuple(fn(v) if c in cols else v for c, v in enumerate(e))
+    FWD, DGRAD, WGRAD = (0, 1), (2, 3, 4, 5, 6), (7, 8, 9, 10)
+    # the row-contiguous forward, and with it the padded copy the queued weight gradient reads
+    module_switch("_ROWS_FORM", False, lambda i, e: sub(sub(e, FWD, lambda v: "plain" if v == "rows" else v), WGRAD, lambda v: _Q if v == _QR else v))
+    module_switch("_MERGED_SUBPIXEL", False, lambda i, e: sub(e, FWD, lambda v: "plain" if v == "subpixel" else v))
+    module_switch("_NARROW_XFOLD", False, lambda i, e: sub(e, DGRAD, lambda v: _T + v[2:] if v[0] == "xfold" else v))
+    # the k-contiguous dgrad of the image layers (rows 0-6 and 8: <= 8 input channels, 64 output channels) goes back to the plain
+    # kernel - with a res_half, to its fused form where there is a LeakyReLU mask (rows 5, 6); the fp16 path's own "t" stays
+    narrow = {0, 1, 2, 3, 4, 5, 6, 8}
+    module_switch("_NARROW_DGRAD_T", False, lambda i, e: e if i not in narrow else sub(sub(e, (2, 5), lambda v: _P), (4, 6), lambda v: _R + (False,) if i in (5, 6) else _P + (True,)))
+
+    def slabbed(i, e, also_queued):      # the non-queued forms ask the library for the slab count; one launch stays "direct" only for 1 slab
+        ns = _ROUTE_SLABS[i]
+        e = sub(e, (8, 9) + ((7,) if also_queued else ()), lambda v: ("slabs", ns))
+        return sub(e, (10,), lambda v: v if (v == _D and ns == 1) else ("slabs", ns))
+    module_switch("_WGRAD_SLABS", True, lambda i, e: slabbed(i, e, False))
+    flipped(lambda: ops.set_deterministic(True), lambda: ops.set_deterministic(False), lambda i, e: slabbed(i, e, True))
+    flipped(lambda: setattr(ops.wgrad_queue, "enabled", False), lambda: setattr(ops.wgrad_queue, "enabled", True), lambda i, e: sub(e, (7,), lambda v: _S))
+
+
+def test_conv_geom_derived_values_and_activated_storage():
+    """ops.ConvGeom: the derived sizes of the pool / sub-pixel folds and of a linear, the record ConvDgradFn differentiates, the shape
+    struct per launch kind with its _TUNE_OVERRIDE entry, and the one activated-storage decision (not for a split-K launch)."""
+    from optimalstrategiesagainstgenerativeattacks_amd import ops
+    pool = ops.ConvGeom.make(240, 64, 64, 64, 128, 3, 0, 0.2, True, has_bias=True, has_res=True)
+    assert (pool.fold, pool.out_shape, pool.out_pixels, pool.K, pool.KFF) == (1, (240, 32, 32, 128), 240 * 32 * 32, 576, 1024)
+    assert pool.key == (240, 64, 64, 64, 128, 3, 0, 1, 1)
+    lin = pool.linear_map()
+    assert (lin.pre_slope, lin.has_bias, lin.has_res, lin.res_ups, lin.x_act, lin.pool, lin.fold, lin.key) == (1.0, False, False, False, False, True, 1, pool.key)
+    fc = ops.ConvGeom.make(16, 1, 1, 512, 10, 1, linear=True)
+    assert (fc.fold, fc.out_shape, fc.out_pixels, fc.K, fc.KFF) == (0, (16, 10), 16, 512, 512)
+    sh = pool.shape("wgrad", 1.0)
+    assert (sh.N, sh.H, sh.Cin, sh.Cout, sh.KH, sh.pool, sh.wfold, sh.res_ups, sh.pre_slope, sh.tune_tile) == (240, 64, 64, 128, 3, 1, 1, 0, 1.0, 0)
+    assert abs(pool.shape("dgrad").pre_slope - 0.2) < 1e-7
+    ops._TUNE_OVERRIDE[("dgrad", pool.key)] = (7, 3)
+    try:
+        assert (pool.shape("dgrad").tune_tile, pool.shape("dgrad").tune_ksplit) == (7, 3)
+        assert pool.shape("fwd").tune_tile == 0 and pool.shape(None).tune_tile == 0
+    finally:
+        ops._TUNE_OVERRIDE.clear()
+    split = ops.ConvGeom.make(80, 4, 4, 512, 512, 3, 0, 0.2)        # splits K (test_deterministic_switch_...): stores raw y
+    whole = ops.ConvGeom.make(240, 64, 64, 64, 64, 3, 0, 0.2)
+    last = ops.ConvGeom.make(80, 64, 64, 64, 3, 9, 1, 0.2)           # stacked sub-pixel form: activates in its depth-to-space copy
+    assert ops._launch_plan(split.shape("fwd"), 0, split.key).ksplit > 1 and ops._launch_plan(whole.shape("fwd"), 0, whole.key).ksplit == 1
+    assert [ops._stores_activated(g, 0.2) for g in (split, whole, last, fc)] == [False, True, True, False]
+    assert not ops._stores_activated(whole, 1.0)
+    n = len(ops._SPLITS_K)
+    assert n >= 2 and ops._launch_plan(whole.shape("fwd"), 0, whole.key) is ops._launch_plan(whole.shape("fwd"), 0, whole.key) and len(ops._SPLITS_K) == n
+    prev = ops.set_deterministic(not ops.deterministic())           # the cached plans were made for the other mode
+    try:
+        assert not ops._SPLITS_K
+    finally:
+        ops.set_deterministic(prev)

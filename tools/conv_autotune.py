@@ -30,6 +30,11 @@ def time_ms(fn, reps=12):
     return e0.elapsed_time(e1) / reps
 
 
+def layer(g):
+    """What the tuning table's rows are keyed by, of a ConvFn's ops.ConvGeom."""
+    return (g.N, g.H, g.W, g.Cin, g.Cout, g.KH, g.ups, g.pre_slope, int(g.pool), g.fold)
+
+
 def record_shapes(workload, B):
     dev = torch.device("cuda:0")
     u = bench.UNIT[workload]
@@ -42,11 +47,11 @@ def record_shapes(workload, B):
 
     def rec_f(ctx, *a):
         y = orig_f(ctx, *a)
-        fwd[ctx.cfg[:8] + (int(ctx.cfg[10]), int(ctx.cfg[11]))] += 1
+        fwd[layer(ctx.cfg)] += 1
         return y
 
     def rec_b(ctx, dy):
-        bwd[(ctx.cfg[:8] + (int(ctx.cfg[10]), int(ctx.cfg[11])), bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1]))] += 1
+        bwd[(layer(ctx.cfg), bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1]))] += 1
         return orig_b(ctx, dy)
     ops.ConvFn.forward, ops.ConvFn.backward = staticmethod(rec_f), staticmethod(rec_b)
     G.gim_step(trainer, leaked, real, si, overlap=False)

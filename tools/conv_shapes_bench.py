@@ -30,6 +30,11 @@ def time_ms(fn, reps=5):
     return e0.elapsed_time(e1) / reps
 
 
+def layer(g):
+    """What the table is keyed by, of a ConvFn's ops.ConvGeom."""
+    return (g.N, g.H, g.W, g.Cin, g.Cout, g.KH, g.ups, g.pre_slope, int(g.pool), g.fold)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="vox64")
@@ -47,11 +52,11 @@ def main():
 
     def rec_f(ctx, *a):
         y = orig_f(ctx, *a)
-        fwd_calls[ctx.cfg[:8] + (int(ctx.cfg[10]), int(ctx.cfg[11]))] += 1
+        fwd_calls[layer(ctx.cfg)] += 1
         return y
 
     def rec_b(ctx, dy):
-        bwd_calls[(ctx.cfg[:8] + (int(ctx.cfg[10]), int(ctx.cfg[11])), bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1]))] += 1
+        bwd_calls[(layer(ctx.cfg), bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1]))] += 1
         return orig_b(ctx, dy)
 
     ops.ConvFn.forward, ops.ConvFn.backward = staticmethod(rec_f), staticmethod(rec_b)
@@ -68,6 +73,8 @@ def main():
         n_dx = sum(c for (cf, dx, dw), c in bwd_calls.items() if cf == cfg and dx)
         n_dw = sum(c for (cf, dx, dw), c in bwd_calls.items() if cf == cfg and dw)
         sh = _lib.GimConvShape(N, H, W, Cin, Cout, KH, ups, slope, pool, fold, 0)
+        g = ops.ConvGeom.make(N, H, W, Cin, Cout, KH, ups, slope, bool(pool))    # the launch forms are the product's: ops._*_route
+        fwd_route, (dgrad_route, J, _) = ops._fwd_route(g, sh.tune_tile), ops._dgrad_route(g, sh.prec, True)
         x = torch.randn(N, H >> ups, W >> ups, Cin, device=dev)
         KF = KH + 1 if fold else KH
         w = torch.randn(Cout, KF, KF, Cin, device=dev) * 0.05   # folded layout when fold
@@ -78,8 +85,8 @@ def main():
         slabs = torch.zeros(ns * Cout * KF * KF * Cin, device=dev)
         flops = ops.conv_executed_flops(N, H, W, Cin, Cout, KH, ups, pool, fold)      # what the kernels execute (folds!)
         algo = ops.conv_algorithmic_flops(N, H, W, Cin, Cout, KH)                      # the unfused reference op
-        rows_form = ops._ROWS_FORM and KH >= 3 and Cin <= 8 and KH * Cin <= 64 and Cout >= 16 and Cout % 4 == 0 and not (ups or pool)
-        if rows_form:   # as ops.ConvFn: padded + activated image copy, row-contiguous K (the copy is part of the forward's time)
+        rows_form = fwd_route == "rows"
+        if rows_form:   # padded + activated image copy, row-contiguous K (the copy is part of the forward's time)
             pad = (KH - 1) // 2
             CaP = (KH * Cin + 15) & ~15
             xp = torch.empty(N, H + 2 * pad, W + 2 * pad, Cin, device=dev)
@@ -91,8 +98,8 @@ def main():
                 lib.gim_pad_image(x.data_ptr(), xp.data_ptr(), N, H, W, Cin, pad, slope, st)
                 lib.gim_conv2d_fwd_rows(xp.data_ptr(), wr.data_ptr(), None, None, None, y.data_ptr(), shr, st)
             t_f = time_ms(fwd_rows)
-        elif ops._MERGED_SUBPIXEL and ups and fold and KH >= 5 and (KH & 3) == 1 and Cout <= 4:
-            # as ops.ConvFn: the four parity classes stacked into one plain convolution + the depth-to-space copy
+        elif fwd_route == "subpixel":
+            # the four parity classes stacked into one plain convolution + the depth-to-space copy
             T = (KH + 1) // 2
             wm = torch.empty(4 * Cout * T * T * Cin, device=dev)
             lib.gim_conv2d_pack_subpixel_weights(w.data_ptr(), wm.data_ptr(), Cout, Cin, KH, st)
@@ -105,12 +112,11 @@ def main():
             t_f = time_ms(fwd_stacked)
         else:
             t_f = time_ms(lambda: lib.gim_conv2d_fwd(x.data_ptr(), w.data_ptr(), None, None, None, y.data_ptr(), sh, st))
-        J = ops._xfold_factor(Cin, W) if (KH >= 3 and not (ups or pool or fold) and Cout % 16 == 0 and ops._NARROW_XFOLD) else 0
-        if J:   # as ops._conv_dgrad: x-folded gradient w.r.t. images
+        if dgrad_route == "xfold":   # x-folded gradient w.r.t. images
             wx = torch.empty(J * Cin * KH * (KH + J - 1) * Cout, device=dev)
             lib.gim_conv2d_xfold_weights(w.data_ptr(), wx.data_ptr(), Cout, Cin, KH, J, st)
             t_d = time_ms(lambda: lib.gim_conv2d_dgrad_xfold(y.data_ptr(), wx.data_ptr(), None, None, dx.data_ptr(), sh, J, st)) if n_dx else 0.0
-        elif Cout % 16 == 0 and not (ups and not fold) and Cin <= 8:
+        elif dgrad_route == "t":
             wt = torch.empty(Cin * KF * KF * Cout, device=dev)
             lib.gim_conv2d_transpose_weights(w.data_ptr(), wt.data_ptr(), Cout, Cin, KF, st)
             t_d = time_ms(lambda: lib.gim_conv2d_dgrad_t(y.data_ptr(), wt.data_ptr(), None, None, dx.data_ptr(), sh, st)) if n_dx else 0.0

@@ -2,7 +2,8 @@
 
     python tools/kernel_probe.py fwd|dgrad|wgrad N H Cin Cout K [ups] [reps] [pool] [0] [tile] [ksplit|wgrad target]
 
-pool = 1 (or ups = 1 with K > 1): the folded form the engine launches for that layer.  (argument 10 is unused: it selected the removed bf16x3 path).  tile / ksplit:
+pool = 1 (or ups = 1 with K > 1): the folded form the engine launches for that layer.  Which kernel a kind takes is what the
+engine's own dispatch says (ops._fwd_route / ops._dgrad_route: rows, stacked sub-pixel, transposed, x-folded ...).  (argument 10 is unused: it selected the removed bf16x3 path).  tile / ksplit:
 launch overrides (gim_conv_shape.tune_*; 0 = table / heuristic, tile < 0 = heuristic only).
 """
 import ctypes
@@ -36,21 +37,31 @@ def main():
     st = torch.cuda.current_stream().cuda_stream
     dgrad = lambda: lib.gim_conv2d_dgrad(y.data_ptr(), w.data_ptr(), None, None, dx.data_ptr(), sh, st)   # noqa: E731
     plan_kind = {"fwd": 0, "dgrad": 1, "wgrad": 3}[kind]
-    if Cin <= 8 and Cout % 16 == 0 and not (ups and not fold):   # image gradient: dgrad on transposed weights (ops._conv_dgrad)
+    g = ops.ConvGeom.make(N, H, H, Cin, Cout, K, ups, slope, bool(pool))
+    fwd_route, (dgrad_route, J, _) = ops._fwd_route(g, tile), ops._dgrad_route(g, sh.prec, True)
+    if dgrad_route == "t":   # image gradient: dgrad on transposed weights
         wt = torch.empty(Cin * KF * KF * Cout, device=dev)
         lib.gim_conv2d_transpose_weights(w.data_ptr(), wt.data_ptr(), Cout, Cin, KF, st)
         dgrad = lambda: lib.gim_conv2d_dgrad_t(y.data_ptr(), wt.data_ptr(), None, None, dx.data_ptr(), sh, st)   # noqa: E731
         plan_kind = 2 if kind == "dgrad" else plan_kind
-    fwd = lambda: lib.gim_conv2d_fwd(x.data_ptr(), w.data_ptr(), None, None, None, y.data_ptr(), sh, st)   # noqa: E731
-    wgrad = lambda: lib.gim_conv2d_wgrad_acc(y.data_ptr(), x.data_ptr(), acc.data_ptr(), None, sh, st)   # noqa: E731
-    plain = not (ups or pool or fold)
-    J = ops._xfold_factor(Cin, H) if (K >= 3 and plain and Cout % 16 == 0 and ops._NARROW_XFOLD) else 0
-    if J:   # as ops._conv_dgrad: the x-folded gradient w.r.t. images
+    elif dgrad_route == "xfold":   # the x-folded gradient w.r.t. images
         wx = torch.empty(J * Cin * K * (K + J - 1) * Cout, device=dev)
         lib.gim_conv2d_xfold_weights(w.data_ptr(), wx.data_ptr(), Cout, Cin, K, J, st)
         dgrad = lambda: lib.gim_conv2d_dgrad_xfold(y.data_ptr(), wx.data_ptr(), None, None, dx.data_ptr(), sh, J, st)   # noqa: E731
-    if ops._ROWS_FORM and K >= 3 and Cin <= 8 and K * Cin <= 64 and Cout >= 16 and Cout % 4 == 0 and plain and tile == 0:
-        # as ops.ConvFn: row-contiguous K on a zero-padded, activated copy of the image (the copy is part of the forward)
+    fwd = lambda: lib.gim_conv2d_fwd(x.data_ptr(), w.data_ptr(), None, None, None, y.data_ptr(), sh, st)   # noqa: E731
+    wgrad = lambda: lib.gim_conv2d_wgrad_acc(y.data_ptr(), x.data_ptr(), acc.data_ptr(), None, sh, st)   # noqa: E731
+    if fwd_route == "subpixel":   # the four parity classes stacked into one plain convolution + the depth-to-space copy
+        T = (K + 1) // 2
+        wm = torch.empty(4 * Cout * T * T * Cin, device=dev)
+        lib.gim_conv2d_pack_subpixel_weights(w.data_ptr(), wm.data_ptr(), Cout, Cin, K, st)
+        y4 = torch.empty(N, H >> 1, H >> 1, 4 * Cout, device=dev)
+        shm = _lib.GimConvShape(N, H >> 1, H >> 1, Cin, 4 * Cout, T, 0, slope, 0, 0, 0)
+
+        def fwd():
+            lib.gim_conv2d_fwd(x.data_ptr(), wm.data_ptr(), None, None, None, y4.data_ptr(), shm, st)
+            lib.gim_depth_to_space2(y4.data_ptr(), None, y.data_ptr(), N, H >> 1, H >> 1, Cout, 1.0, st)
+    if fwd_route == "rows":
+        # row-contiguous K on a zero-padded, activated copy of the image (the copy is part of the forward)
         pad, CaP = (K - 1) // 2, (K * Cin + 15) & ~15
         xp = torch.empty(N, H + 2 * pad, H + 2 * pad, Cin, device=dev)
         wr = torch.empty(Cout * K * CaP, device=dev)
