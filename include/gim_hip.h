@@ -399,6 +399,44 @@ int gim_img_att_mix_bwd(const float* dout, const float* q1, const float* k1, con
 int gim_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_end, const float* lr,
                   int n_seg, float beta1, float beta2, float eps, float grad_scale, int32_t* step, void* stream);
 
+/* ---- Inference of the baseline authenticators (baselines/siamese/models.py:14-56,97-114, baselines/arcface/models.py:16-164,214-237
+ * as authentication_eval/eval_gim_on_authentication.py:47-72,109-128 runs them: eval mode, no_grad).  Forward only. ----
+ *
+ * Strided convolution with a per-channel epilogue - nn.Conv2d(k, stride, padding = (k - 1) / 2) + a folded BatchNorm's bias + nn.PReLU /
+ * nn.ReLU (arcface/models.py:26-28,48,52-53,69,74-76,139-141; siamese/models.py:52-54) and the SE module's 1x1 convolutions on a 1x1 map:
+ *   y[n,oy,ox,co] = act_co( sum_{a,b,ci} w[co][a][b][ci] * x[n][oy*stride+a-pad][ox*stride+b-pad][ci] + bias[co] ),
+ *   act_co(v) = v >= 0 ? v : slope[co] * v.     bias [Cout] (NULL = 0), slope [Cout] (NULL = no activation; zeros = ReLU).
+ * H, W: the INPUT size (powers of two); y is [N][H/stride][W/stride][Cout]; KH in {1, 3}; stride in {1, 2}; pad = (KH - 1) / 2.
+ * The implicit-GEMM forward kernels with an epilogue mode of their own; a launch never splits K (small launches run with fewer
+ * workgroups), so results do not depend on atomics: bitwise reproducible. */
+typedef struct {
+    int32_t N, H, W, Cin, Cout, KH, stride;
+} gim_infer_conv;
+int gim_conv2d_infer(const float* x, const float* w, const float* bias, const float* slope, float* y, const gim_infer_conv* shape,
+                     void* stream);
+
+/* Bandwidth-bound passes of the same networks (16-byte accesses: C % 4 == 0, 16-byte aligned pointers).
+ *   gim_maxpool2_act  : nn.MaxPool2d(2) of an NHWC map, H and W the INPUT size; relu != 0: max(., 0) on the result - the
+ *                       ReLU in front of the pool (siamese/models.py:54-55) commutes with the maximum.
+ *   gim_channel_affine: y = x * scale[c] + shift[c] over `rows` pixels - inference nn.BatchNorm2d in front of a zero-padded
+ *                       convolution (arcface/models.py:73,144), which cannot be folded into that convolution's weights.
+ *   gim_se_tail       : the end of a bottleneck_IR_SE unit (arcface/models.py:37-38,81-84) in one pass:
+ *                       out = res * sigmoid(gate[n][c]) + shortcut[n][oy * sstride][ox * sstride][c], res and out [N][Ho][Wo][C],
+ *                       shortcut [N][Ho * sstride][Wo * sstride][C] (sstride 2: the MaxPool2d(1, 2) shortcut is a subsample);
+ *                       with out_bn != NULL also out_bn = out * scale[c] + shift[c], the NEXT unit's leading BatchNorm
+ *                       (out_bn, scale and shift are given together or not at all).
+ *   gim_pair_score    : out[b] = -|| a[b] / |a[b]| - b[b] / |b[b]| ||^2 for rows of two [B][D] matrices (l2_norm + ArcFace.predict,
+ *                       arcface/models.py:16-19,231-237).
+ *   gim_l2norm_rows   : y[b] = x[b] / |x[b]| (l2_norm at the end of Backbone.forward, arcface/models.py:16-19,164).
+ *   gim_absdiff       : y = |a - b| (SiameseNet.classify, siamese/models.py:107). */
+int gim_maxpool2_act(const float* x, float* y, int N, int H, int W, int C, int relu, void* stream);
+int gim_channel_affine(const float* x, const float* scale, const float* shift, float* y, int64_t rows, int C, void* stream);
+int gim_se_tail(const float* res, const float* gate, const float* shortcut, const float* scale, const float* shift, float* out,
+                float* out_bn, int N, int Ho, int Wo, int C, int sstride, void* stream);
+int gim_pair_score(const float* a, const float* b, float* out, int B, int D, void* stream);
+int gim_l2norm_rows(const float* x, float* y, int B, int D, void* stream);
+int gim_absdiff(const float* a, const float* b, float* y, int64_t n, void* stream);
+
 /* Stream self-check: one wave busy for `usec` microseconds (1 .. 5000, constant 100 MHz wall clock) on `stream`.  The host
  * launches one per engine stream at the same moment and event-times the total: streams that share a HIP hardware queue serialize
  * (nn.DataParallel's one-thread-per-device streams of training/gim_img_training.py:406-411 have no such aliasing to check). */

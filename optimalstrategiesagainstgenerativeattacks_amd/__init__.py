@@ -43,6 +43,7 @@ from .gim_img_trainer import GIMImgTrainer
 from .data import EpisodeBank, OmniglotEpisodeBank, synthetic_bank
 from .gim_img_training import (au_eval_step, au_train_step, eval_step, gim_step, im_eval_step, im_train_step, train_epoch,
                                train_gim_imgs)
+from .baselines import ArcFace, Backbone, ProtonetEmbeddingNet, SiameseNet
 from .training_logger import Logger
 from .optim import FusedAdam
 from .training_utils import CheckpointIO, DataParallelMock, EpisodeParallel, GlobalStep, adjust_batch_size, pin_rank_to_cores
@@ -51,5 +52,5 @@ __all__ = [
     "get_au", "get_im", "Encoder", "EnvDecoder", "AdaInImage2Image", "GIMFaceDis", "GIMFaceAuthenticator",
     "GIMFaceImpersonator", "GIMImgTrainer", "GIMGaussianTrainer", "im_train_step", "au_train_step", "im_eval_step", "au_eval_step",
     "gim_step", "train_epoch", "eval_step", "train_gim_imgs", "train_gim_gaussian", "EpisodeBank", "OmniglotEpisodeBank", "synthetic_bank", "Logger", "FusedAdam", "DataParallelMock", "EpisodeParallel", "GlobalStep", "CheckpointIO", "adjust_batch_size",
-    "pin_rank_to_cores", "stream_concurrency_check", "hw_queues_state",
+    "pin_rank_to_cores", "stream_concurrency_check", "hw_queues_state", "ProtonetEmbeddingNet", "SiameseNet", "Backbone", "ArcFace",
 ]

@@ -20,6 +20,11 @@ class GimConvShape(ctypes.Structure):
                 ("out_zeroed", c_int32), ("post_slope", c_float), ("prec", c_int32)]
 
 
+class GimInferConv(ctypes.Structure):
+    _fields_ = [("N", c_int32), ("H", c_int32), ("W", c_int32), ("Cin", c_int32), ("Cout", c_int32),
+                ("KH", c_int32), ("stride", c_int32)]
+
+
 P = c_void_p
 SP = POINTER(GimConvShape)
 
@@ -95,6 +100,13 @@ SIGNATURES = {
     "gim_depth_to_space2": [P, P, P, c_int, c_int, c_int, c_int, c_float, P],
     "gim_conv2d_fwd_rows": [P, P, P, P, P, P, SP, P],
     "gim_conv2d_wgrad_rows_acc": [P, P, P, P, SP, P],
+    "gim_conv2d_infer": [P, P, P, P, P, POINTER(GimInferConv), P],
+    "gim_maxpool2_act": [P, P, c_int, c_int, c_int, c_int, c_int, P],
+    "gim_channel_affine": [P, P, P, P, c_int64, c_int, P],
+    "gim_se_tail": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P],
+    "gim_pair_score": [P, P, P, c_int, c_int, P],
+    "gim_l2norm_rows": [P, P, c_int, c_int, P],
+    "gim_absdiff": [P, P, P, c_int64, P],
     "gim_version": [],
 }
 

@@ -2,15 +2,23 @@
 ``eval_gim_on_authentication.py:25-44,75-106`` (model -> agent wrappers), ``agents.py:16-58`` (Authenticator / Impersonator
 agents, replay impersonator) and ``authentication_score.py:32-97`` (accuracy / ROC-AUC over a dataset).  Host-side glue
 over the same modules: both networks run in eval mode under ``torch.no_grad()`` (no power iteration, sigma from the stored
-u, v); batches come from ``data.EpisodeBank.gpu_batches`` or a DataLoader, and per-batch statistics stay on the device."""
+u, v); batches come from ``data.EpisodeBank.gpu_batches`` or a DataLoader, and per-batch statistics stay on the device.
+
+The baseline rows of the result table (``eval_gim_on_authentication.py:47-72,109-252``, ``agents.py:53-62``): siamese / ArcFace
+authenticators (``baselines.py``), the random-source impersonator, the dispatchers by type name and ``eval_authentication_task``,
+which writes the reference's CSV columns with the ``csv`` module."""
+import csv
 import itertools
+import os
 import random
 
 import numpy as np
 import torch
 from tqdm import tqdm
 
+from . import ops
 from .gim_img_training import _batches, _world
+from .training_utils import get_latest_ckpt, load_args
 
 
 def get_au_function(au):
@@ -110,3 +118,147 @@ def eval_authenticator_and_impersonator(device, ds, batch_size, num_workers, aut
     y_true = torch.cat([torch.ones_like(out_on_real), torch.zeros_like(out_on_fake)]).cpu().numpy()
     y_score = torch.cat([out_on_real, out_on_fake]).cpu().numpy()
     return acc, acc_on_fake, acc_on_real, roc_auc(y_true, y_score)
+
+
+# ------------------------------------------------------------------------------------------------------
+# baseline authenticators, random-source impersonator, the result table
+# ------------------------------------------------------------------------------------------------------
+def _flat_sets(sample):
+    """[B, t, C, H, W] -> ([B * t, C, H, W], B, t)."""
+    B, t = sample.shape[:2]
+    return sample.reshape(B * t, *sample.shape[2:]), B, t
+
+
+def get_siamese_au_function(model):
+    """Mean embedding of the test set against mean embedding of the source-information set; both sets go through the embedding
+    net in ONE pass."""
+    def au_model_func(test_sample, si_sample):
+        model.train(mode=False)
+        with torch.no_grad():
+            si, B, k = _flat_sets(si_sample)
+            test, _, n = _flat_sets(test_sample)
+            emb = model.encode(torch.cat([si, test], 0))
+            si_emb = ops.mean_dim1(emb[:B * k].view(B, k, -1))
+            test_emb = ops.mean_dim1(emb[B * k:].view(B, n, -1))
+            logits = model.classify(si_emb, test_emb)
+        return logits.squeeze().detach()
+    return au_model_func
+
+
+def get_arcface_au_function(arcface):
+    """ArcFace score of the MEAN IMAGE of the test set against the mean image of the source-information set."""
+    def au_model_func(test_sample, si_sample):
+        arcface.train(mode=False)
+        with torch.no_grad():
+            img = test_sample.shape[2:]
+            x1 = ops.mean_dim1(ops._req(test_sample, "test_sample").flatten(2)).view(-1, *img)
+            x2 = ops.mean_dim1(ops._req(si_sample, "si_sample").flatten(2)).view(-1, *img)
+            score, _ = arcface.predict(x1=x1, x2=x2)
+        return score.detach()
+    return au_model_func
+
+
+def rand_source_impersonator(leaked_sample, n, gim_ds):
+    """Per batch element the real sample of a randomly drawn example of the dataset (another source, most of the time)."""
+    rows = [gim_ds[random.randint(0, len(gim_ds) - 1)]["real_sample"] for _ in range(leaked_sample.size(0))]
+    fake = torch.stack([torch.as_tensor(r) for r in rows], dim=0)
+    assert fake.size(1) == n, "the dataset's real sets have %d elements, %d asked for" % (fake.size(1), n)
+    return fake.to(leaked_sample.device)
+
+
+def get_siamese_authenticator(device, ckpt_path, args_dict):
+    from .baselines import ProtonetEmbeddingNet, SiameseNet
+    net = ProtonetEmbeddingNet(inp_n_channels=1, inp_img_size=32)      # the reference evaluates the siamese baseline on Omniglot only
+    siamese = SiameseNet(net, net.embedding_dim)
+    siamese.load_state_dict(torch.load(ckpt_path, map_location='cpu')['model'], strict=True)
+    return Authenticator(get_siamese_au_function(siamese.to(device)))
+
+
+def get_arcface_authenticator(device, ckpt_path, args_dict):
+    from .baselines import ArcFace, Backbone
+    sd = torch.load(ckpt_path, map_location='cpu')['arcface']
+    a = args_dict
+    backbone = Backbone(a['num_layers'], a['dropout'], 'ir_se', a['img_size'], a['img_channels'])
+    arcface = ArcFace(backbone, a['emb_dim'], n_classes=sd['head.kernel'].size(-1), th=a['th'])   # the class count is the head's width
+    arcface.load_state_dict(sd, strict=True)
+    return Authenticator(get_arcface_au_function(arcface.to(device)), th=arcface.th)
+
+
+def _gim_authenticator_from_ckpt(device, ckpt_path, args_dict):
+    from .gim_img_models import get_au
+    au = get_au(img_size=args_dict['img_size'], img_channels=args_dict['img_channels'], style_dim=args_dict['style_dim'])
+    au.load_state_dict(torch.load(ckpt_path, map_location='cpu')['authenticator'])
+    return get_gim_authenticator(au.to(device))
+
+
+def _gim_impersonator_from_ckpt(device, ckpt_path, args_dict):
+    from .gim_img_models import get_im
+    im = get_im(img_size=args_dict['img_size'], img_channels=args_dict['img_channels'], style_dim=args_dict['style_dim'],
+                use_img_att=args_dict['use_img_att'], num_env_noise_layers=args_dict['num_env_noise_layers'])
+    im.load_state_dict(torch.load(ckpt_path, map_location='cpu')['impersonator'])
+    return get_gim_impersonator(im.to(device), args_dict)
+
+
+def get_authenticator(device, au_type, ckpt_path, args_dict):
+    makers = {'gim': _gim_authenticator_from_ckpt, 'siamese': get_siamese_authenticator, 'arcface': get_arcface_authenticator}
+    if au_type not in makers:
+        raise ValueError("unsupported authenticator type %r (gim | siamese | arcface)" % (au_type,))
+    return makers[au_type](device, ckpt_path, args_dict)
+
+
+def get_impersonator(device, im_type, ckpt_path, ds, args_dict):
+    if im_type == 'gim':
+        return _gim_impersonator_from_ckpt(device, ckpt_path, args_dict)
+    if im_type == 'replay':
+        return Impersonator(replay_impersonator)
+    if im_type == 'rnd_src':
+        return Impersonator(lambda leaked_sample, n: rand_source_impersonator(leaked_sample, n, ds))
+    raise ValueError("unsupported impersonator type %r (gim | replay | rnd_src)" % (im_type,))
+
+
+def get_exp_args_from_dir(outdir, ckpt_dir, specific_model=None):
+    """(checkpoint path, args dict) of an experiment directory: its latest checkpoint unless one is named."""
+    ckpt_dir_path = os.path.join(outdir, ckpt_dir)
+    path = get_latest_ckpt(ckpt_dir_path) if specific_model is None else os.path.join(ckpt_dir_path, specific_model)
+    args_dict = load_args(outdir)
+    if 'img_size' not in args_dict:
+        args_dict['img_size'] = args_dict['target_img_size']
+    return path, args_dict
+
+
+def eval_game_for_pair(device, au_type, im_type, au_outdir, im_outdir, ds, batch_size, num_workers, ckpt_dir='ckpts',
+                       specific_model=None):
+    au_ckpt_path, au_args_dict = get_exp_args_from_dir(au_outdir, ckpt_dir, specific_model=specific_model)
+    im_ckpt_path, im_args_dict = get_exp_args_from_dir(im_outdir, ckpt_dir, specific_model=specific_model)
+    au_agent = get_authenticator(device=device, au_type=au_type, ckpt_path=au_ckpt_path, args_dict=au_args_dict)
+    im_agent = get_impersonator(device=device, im_type=im_type, ckpt_path=im_ckpt_path, ds=ds, args_dict=im_args_dict)
+    acc, acc_on_fake, acc_on_real, auc = eval_authenticator_and_impersonator(
+        device=device, ds=ds, batch_size=batch_size, num_workers=num_workers, authenticator=au_agent, impersonator=im_agent)
+    return float(acc), float(acc_on_fake), float(acc_on_real), float(auc)
+
+
+TABLE_COLUMNS = ('au_type', 'im_type', 'ds_root', 'gim_exp_dir', 'm', 'n', 'k', 'acc', 'acc_on_fake', 'acc_on_real', 'auc')
+
+
+def eval_authentication_task(device, ds, m, n, k, batch_size, num_workers, gim_exp_dir, csv_file_path, specific_model=None,
+                             baseline_exp_dir=None, baseline_type=None):
+    """The result table: authenticator gim (and the baseline, if one is named) against impersonators gim, replay, rnd_src -
+    one CSV row each, in that order.  Returns the rows."""
+    out_dir = os.path.dirname(csv_file_path)
+    if out_dir and not os.path.isdir(out_dir):
+        os.makedirs(out_dir)
+    rows = []
+    for au_type in (['gim'] if baseline_type is None else ['gim', baseline_type]):
+        for im_type in ('gim', 'replay', 'rnd_src'):
+            print("running {} vs. {}".format(au_type, im_type))
+            acc, acc_on_fake, acc_on_real, auc = eval_game_for_pair(
+                device=device, au_type=au_type, im_type=im_type, au_outdir=gim_exp_dir if au_type == 'gim' else baseline_exp_dir,
+                im_outdir=gim_exp_dir, ds=ds, batch_size=batch_size, num_workers=num_workers, specific_model=specific_model)
+            rows.append(dict(zip(TABLE_COLUMNS, (au_type, im_type, getattr(ds, "root", ""), gim_exp_dir, m, n, k,
+                                                 acc, acc_on_fake, acc_on_real, auc))))
+            print({c: rows[-1][c] for c in ('au_type', 'im_type', 'acc', 'acc_on_fake', 'acc_on_real')})
+    with open(csv_file_path, 'w', newline='') as f:
+        wr = csv.DictWriter(f, fieldnames=TABLE_COLUMNS)
+        wr.writeheader()
+        wr.writerows(rows)
+    return rows

@@ -125,6 +125,10 @@ struct ConvP {
     int pix;      // floats between consecutive PIXELS of the gathered tensor: = Ca, except in the row-contiguous form of the <= 8-channel
                   // image layers (gim_conv2d_fwd_rows: Ca = the padded length of one tap ROW, K * Cin rounded up to 16, pix = Cin)
     int f16;      // host only: gim_conv_shape.prec == 1 - fp16 operands on v_mfma_f32_32x32x16_f16 where the launch is eligible (conv_f16.inc)
+    const float* slope;   // gim_conv2d_infer (kernels with EPI = 1): per-output-channel PReLU slope [Cb] (NULL = no activation)
+    int epi;      // host only: 1 = the launch runs the EPI = 1 instantiation of its kernel (epilogue MODE 5)
+    int no_split; // host only: the launch never splits K (a per-channel activation cannot follow partial sums): every launcher clamps
+                  // ksplit to 1, table rows included (a row measured on another geometry may share this launch's key)
 };
 
 // GENF bit 0: generic K (channel count of the gathered tensor not a multiple of 16, or unaligned base)
@@ -166,7 +170,8 @@ __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned vo
 
 // Epilogue of one accumulator block: NE values of ONE output channel `co` on rows mbase + (e & 3) + 8 * (e >> 2) (the C/D layout of
 // the 32x32 and, for NE = 4, of the 16x16 MFMA).  MODE 0: y = a * scale + bias; 1: + residual; 2: + residual stored at half
-// resolution (nearest-upsampled on the fly); 3: * leaky_relu'(mask).  All loads of the block are issued before the first is used
+// resolution (nearest-upsampled on the fly); 3: * leaky_relu'(mask); 5 (inference entry): y = prelu(a * scale + bias, slope of this
+// channel `sv`), nothing loaded.  All loads of the block are issued before the first is used
 // (a load - wait - store chain per element made the epilogue of a short-K workgroup as long as its K loop), every offset is a
 // per-lane VGPR offset (the SGPR offset of a raw buffer access is not bounds-checked: rows beyond a ragged tile edge must be
 // dropped by the lane offset), and nothing in the element loops branches.
@@ -191,7 +196,7 @@ __device__ __forceinline__ void epi_elem_off(const EpiCtx& c, int m, int co, uns
 }
 
 template <int NE, int MODE>
-__device__ __forceinline__ void epi_block(const EpiCtx& c, const float (&a)[NE], int mbase, int co, bool cok, float bv) {
+__device__ __forceinline__ void epi_block(const EpiCtx& c, const float (&a)[NE], int mbase, int co, bool cok, float bv, float sv = 1.f) {
     constexpr int CH = NE < 8 ? NE : 8;   // elements in flight: 8 loads per lane cover the latency, more would cost occupancy
     const unsigned rowb = (unsigned)c.Cb * 4u;
 #pragma unroll
@@ -242,7 +247,7 @@ __device__ __forceinline__ void epi_block(const EpiCtx& c, const float (&a)[NE],
             off[q] |= bad;
             if constexpr (MODE == 2 || MODE == 4) roff[q] |= bad;
         }
-        float ld[MODE == 0 ? 1 : CH], ld2[MODE == 4 ? CH : 1];
+        float ld[(MODE == 0 || MODE == 5) ? 1 : CH], ld2[MODE == 4 ? CH : 1];
         if constexpr (MODE == 4) {   // the input-gradient fan-in of a ResBlockDown: mask (full resolution) and the pooled skip gradient (half)
 #pragma unroll
             for (int q = 0; q < CH; ++q) ld[q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(c.rm, off[q], 0, 0));
@@ -262,7 +267,8 @@ __device__ __forceinline__ void epi_block(const EpiCtx& c, const float (&a)[NE],
             if constexpr (MODE == 1 || MODE == 2) v[q] += ld[q];
             if constexpr (MODE == 3 || MODE == 4) v[q] *= (ld[q] > 0.f ? 1.0f : c.mask_slope);
             if constexpr (MODE == 4) v[q] += c.res_scale * ld2[q];
-            if constexpr (MODE != 3 && MODE != 4) v[q] = fmaxf(v[q], v[q] * c.post_slope);   // post_slope = 1: identity (0 < slope <= 1)
+            if constexpr (MODE == 5) v[q] = v[q] >= 0.f ? v[q] : v[q] * sv;                   // per-channel PReLU (any slope; 0 = ReLU, 1 = none)
+            else if constexpr (MODE != 3 && MODE != 4) v[q] = fmaxf(v[q], v[q] * c.post_slope);   // post_slope = 1: identity (0 < slope <= 1)
         }
         if (c.atom) {
 #pragma unroll
@@ -280,7 +286,9 @@ constexpr int igemm_lds_bytes(int BM, int BN, int KB, int BMODE) {
     return 2 * (BM * (KB + 4) + (BMODE == 0 ? BN * (KB + 4) : KB * BN)) * 4;
 }
 
-template <int BM, int BN, int TM, int TN, int BMODE, int GENF, int KB>
+// EPI: compile-time epilogue family.  0 = the training paths (modes 0-4, chosen per launch from the operands); 1 = the inference
+// entry gim_conv2d_infer (mode 5 only) - instantiations of their own, so that the EPI = 0 kernels are what they were before it existed.
+template <int BM, int BN, int TM, int TN, int BMODE, int GENF, int KB, int EPI = 0>
 __global__ __launch_bounds__(256, igemm_lds_bytes(BM, BN, KB, BMODE) <= 40960 ? 4 : 2) void conv_igemm_kernel(const ConvP p) {
     constexpr bool GEN = (GENF & 1) != 0;
     constexpr bool BSCALAR = (GENF & 2) != 0;
@@ -726,7 +734,8 @@ __global__ __launch_bounds__(256, igemm_lds_bytes(BM, BN, KB, BMODE) <= 40960 ? 
 #pragma unroll
             for (int i = 0; i < NB16; ++i) {
                 const float a[4] = {acc16[i][0], acc16[i][1], acc16[i][2], acc16[i][3]};
-                epi_block<4, MODE>(ec, a, m0 + wm0 + 16 * i + 4 * q16, co, cok, bv);
+                if constexpr (MODE == 5) epi_block<4, MODE>(ec, a, m0 + wm0 + 16 * i + 4 * q16, co, cok, bv, (p.slope && cok) ? p.slope[co] : 1.f);
+                else epi_block<4, MODE>(ec, a, m0 + wm0 + 16 * i + 4 * q16, co, cok, bv);
             }
         } else {               // block (i, j), register e: row 32*i + (e & 3) + 8*(e >> 2) + 4*h, column 32*j + r
 #pragma unroll
@@ -739,11 +748,14 @@ __global__ __launch_bounds__(256, igemm_lds_bytes(BM, BN, KB, BMODE) <= 40960 ? 
                     float a[16];
 #pragma unroll
                     for (int e = 0; e < 16; ++e) a[e] = acc[i][j][e];
-                    epi_block<16, MODE>(ec, a, m0 + wm0 + 32 * i + 4 * h, co, cok, bv);
+                    if constexpr (MODE == 5) epi_block<16, MODE>(ec, a, m0 + wm0 + 32 * i + 4 * h, co, cok, bv, (p.slope && cok) ? p.slope[co] : 1.f);
+                    else epi_block<16, MODE>(ec, a, m0 + wm0 + 32 * i + 4 * h, co, cok, bv);
                 }
         }
     };
-    if (has_res && has_mask) {     // dgrad with the pooled skip gradient folded in (gim_conv2d_dgrad_res): mask, then + res_scale * up2(res)
+    if constexpr (EPI == 1) {      // gim_conv2d_infer: bias + per-channel PReLU, never split
+        run(std::integral_constant<int, 5>());
+    } else if (has_res && has_mask) {     // dgrad with the pooled skip gradient folded in (gim_conv2d_dgrad_res): mask, then + res_scale * up2(res)
         run(std::integral_constant<int, 4>());
     } else if (has_res) {
         if (p.res_ups) run(std::integral_constant<int, 2>());
@@ -767,7 +779,7 @@ __global__ __launch_bounds__(256, igemm_lds_bytes(BM, BN, KB, BMODE) <= 40960 ? 
 // Host guarantees: plain geometry (stride 1, no upsample, no parity classes), 3x3 taps, Ca % 16 == 0, H * W >= BM (a tile never
 // crosses an image), vector weight loads, split-K in whole chunks (kper = chunks per slice * 9).
 // -------------------------------------------------------------------------------------------------
-template <int BM, int BN, int TM, int TN, int BMODE>
+template <int BM, int BN, int TM, int TN, int BMODE, int EPI = 0>
 __global__ __launch_bounds__(256, TM * TN <= 2 ? 3 : 2) void conv_igemm_patch_kernel(const ConvP p) {
     constexpr int KB = 16, LDK = KB + 4;
     constexpr int WAVES_N = BN / (32 * TN), WAVES_M = BM / (32 * TM);
@@ -986,10 +998,13 @@ __global__ __launch_bounds__(256, TM * TN <= 2 ? 3 : 2) void conv_igemm_patch_ke
                 float a[16];
 #pragma unroll
                 for (int e = 0; e < 16; ++e) a[e] = acc[i][j][e];
-                epi_block<16, MODE>(ec, a, m0 + wm0 + 32 * i + 4 * h, co, cok, bv);
+                if constexpr (MODE == 5) epi_block<16, MODE>(ec, a, m0 + wm0 + 32 * i + 4 * h, co, cok, bv, (p.slope && cok) ? p.slope[co] : 1.f);
+                else epi_block<16, MODE>(ec, a, m0 + wm0 + 32 * i + 4 * h, co, cok, bv);
             }
     };
-    if (has_res && has_mask) {     // dgrad with the pooled skip gradient folded in (gim_conv2d_dgrad_res): mask, then + res_scale * up2(res)
+    if constexpr (EPI == 1) {      // gim_conv2d_infer: bias + per-channel PReLU, never split
+        run(std::integral_constant<int, 5>());
+    } else if (has_res && has_mask) {     // dgrad with the pooled skip gradient folded in (gim_conv2d_dgrad_res): mask, then + res_scale * up2(res)
         run(std::integral_constant<int, 4>());
     } else if (has_res) {
         if (p.res_ups) run(std::integral_constant<int, 2>());
@@ -1776,7 +1791,7 @@ static void launch_cfg_kb(ConvP p, size_t y_elems, hipStream_t st, bool table_hi
         if (p.g.pm) pm_make_perms(p.g);
     }
 #endif
-    p.ksplit = plan_ksplit((long long)gx * gy * ncls, nk, BM * BN, p.tune_ks);
+    p.ksplit = p.no_split ? 1 : plan_ksplit((long long)gx * gy * ncls, nk, BM * BN, p.tune_ks);
     p.kper = (nk + p.ksplit - 1) / p.ksplit;
     p.ksplit = (nk + p.kper - 1) / p.kper;
     if (t_plan_out) {
@@ -1791,6 +1806,12 @@ static void launch_cfg_kb(ConvP p, size_t y_elems, hipStream_t st, bool table_hi
         return;
     }
     if (p.ksplit > 1 && !p.y_zeroed) (void)hipMemsetAsync(p.y, 0, y_elems * sizeof(float), st);
+    if constexpr (BMODE == 0 && (GEN & 2) == 0) {   // the inference epilogue exists for the forward operand path only
+        if (p.epi) {
+            hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, TM, TN, BMODE, GEN, KB, 1>), dim3(gx, gy, ncls), dim3(256), 0, st, p);
+            return;
+        }
+    }
     hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, TM, TN, BMODE, GEN, KB>), dim3(gx, gy, p.ksplit * ncls), dim3(256), 0, st, p);
 }
 
@@ -1820,7 +1841,7 @@ template <int BM, int BN, int TM, int TN, int BMODE>
 static void launch_patch_cfg(ConvP p, size_t y_elems, hipStream_t st, bool table_hit) {
     const int gx = (p.M + BM - 1) / BM, gy = (p.Cb + BN - 1) / BN;
     const int chunks = p.Ca / 16, T = 9;
-    int ks = plan_ksplit((long long)gx * gy, chunks * T, BM * BN, p.tune_ks);
+    int ks = p.no_split ? 1 : plan_ksplit((long long)gx * gy, chunks * T, BM * BN, p.tune_ks);
     if (ks > chunks) ks = chunks;
     const int cps = (chunks + ks - 1) / ks;
     p.ksplit = (chunks + cps - 1) / cps;
@@ -1841,6 +1862,12 @@ static void launch_patch_cfg(ConvP p, size_t y_elems, hipStream_t st, bool table
     const int P_SZ = (PP * 20 + 3) & ~3;
     const int B_SZ = (BMODE == 0) ? BN * 20 : 16 * BN;
     const size_t lds = (size_t)(2 * P_SZ + 2 * B_SZ) * sizeof(float);
+    if constexpr (BMODE == 0) {
+        if (p.epi) {
+            hipLaunchKernelGGL((conv_igemm_patch_kernel<BM, BN, TM, TN, BMODE, 1>), dim3(gx, gy, 1), dim3(256), lds, st, p);
+            return;
+        }
+    }
     hipLaunchKernelGGL((conv_igemm_patch_kernel<BM, BN, TM, TN, BMODE>), dim3(gx, gy, p.ksplit), dim3(256), lds, st, p);
 }
 
@@ -1881,7 +1908,7 @@ static void launch_f16_cfg(ConvP p, size_t y_elems, hipStream_t st) {
     const int gx = (p.M + BM - 1) / BM, gy = (p.Cb + BN - 1) / BN;
     const int ncls = p.g.pc ? 4 : 1;
     const int nk = p.Ktot / 32;
-    p.ksplit = plan_ksplit((long long)gx * gy * ncls, nk, BM * BN, p.tune_ks);
+    p.ksplit = p.no_split ? 1 : plan_ksplit((long long)gx * gy * ncls, nk, BM * BN, p.tune_ks);
     p.kper = (nk + p.ksplit - 1) / p.ksplit;
     p.ksplit = (nk + p.kper - 1) / p.kper;
     if (t_plan_out) {
@@ -1903,7 +1930,7 @@ template <int BM, int BN, int TM, int TN>
 static void launch_patch_f16_cfg(ConvP p, size_t y_elems, hipStream_t st) {
     const int gx = (p.M + BM - 1) / BM, gy = (p.Cb + BN - 1) / BN;
     const int chunks = p.Ca / 32, T = 9;
-    int ks = plan_ksplit((long long)gx * gy, chunks * T, BM * BN, p.tune_ks);
+    int ks = p.no_split ? 1 : plan_ksplit((long long)gx * gy, chunks * T, BM * BN, p.tune_ks);
     if (ks > chunks) ks = chunks;
     const int cps = (chunks + ks - 1) / ks;
     p.ksplit = (chunks + cps - 1) / cps;
@@ -2047,6 +2074,58 @@ extern "C" int gim_conv2d_fwd(const float* x, const float* w, const float* bias,
     if (t_launch_refused) return GIM_E_BADARG;
     if (t_plan_out) return GIM_OK;
     return gim_check_launch("gim_conv2d_fwd");
+}
+
+// Forward-only strided convolution with a per-channel epilogue (inference of the baseline authenticators, baselines.py): the plain
+// geometry with a gather stride - what geo_s2 is for the pool fold, with the convolution's own KH x KH taps - on the EPI = 1
+// instantiations of the forward kernels.  Never splits K; stride-1 3x3 launches reach the patch-resident kernel as training launches do.
+static Geo geo_strided(const gim_infer_conv* s) {
+    Geo g{};
+    const int pad = (s->KH - 1) / 2;
+    geo_grid(g, s->N, s->H / s->stride, s->W / s->stride);
+    g.Hin = s->H; g.Win = s->W; g.ups = 0;
+    g.s_in = g.s_in_x = s->stride; g.off_y = g.off_x = -pad; g.Th = g.Tw = g.KF = g.KFw = s->KH;
+    g.wa_base = g.wb_base = 0;
+    g.wa_step = g.wb_step = 1;
+    g.os = 1;
+    return g;
+}
+
+extern "C" int gim_conv2d_infer(const float* x, const float* w, const float* bias, const float* slope, float* y,
+                                const gim_infer_conv* s, void* stream) {
+    GIM_CHECK_ARG(s != nullptr, "conv infer: null shape");
+    GIM_CHECK_ARG(x && w && y, "conv infer: null pointer");
+    GIM_CHECK_ARG(s->N > 0 && s->Cin > 0 && s->Cout > 0, "conv infer: non-positive dims");
+    GIM_CHECK_ARG(s->KH == 1 || s->KH == 3, "conv infer: KH must be 1 or 3");
+    GIM_CHECK_ARG(s->stride == 1 || s->stride == 2, "conv infer: stride must be 1 or 2");
+    GIM_CHECK_ARG(ilog2_exact(s->H) >= 0 && ilog2_exact(s->W) >= 0, "conv infer: H and W must be powers of two");
+    GIM_CHECK_ARG(s->H >= s->stride && s->W >= s->stride, "conv infer: stride 2 needs H, W >= 2");
+    GIM_CHECK_ARG((long long)s->N * s->H * s->W < (1ll << 31), "conv infer: too many pixels");
+    const int Ho = s->H / s->stride, Wo = s->W / s->stride;
+    const size_t xi = (size_t)s->H * s->W * s->Cin, yi = (size_t)Ho * Wo * s->Cout;   // elements per image
+    GIM_CHECK_ARG((xi > yi ? xi : yi) * sizeof(float) <= BUF_MAX_BYTES, "conv infer: one image exceeds 2 GiB (32-bit buffer offsets)");
+    if (s->N > 1 && (xi > yi ? xi : yi) * s->N * sizeof(float) > BUF_MAX_BYTES) {   // halve the batch (images are independent)
+        gim_infer_conv a = *s, b = *s;
+        a.N = s->N / 2; b.N = s->N - a.N;
+        const int rc = gim_conv2d_infer(x, w, bias, slope, y, &a, stream);
+        if (rc) return rc;
+        return gim_conv2d_infer(x + a.N * xi, w, bias, slope, y + a.N * yi, &b, stream);
+    }
+    ConvP p{};
+    p.zero = zero_page();
+    p.pos_inf = __builtin_inff();
+    p.g = geo_strided(s);
+    p.x = x; p.w = w; p.bias = bias; p.slope = slope; p.y = y;
+    p.Ca = s->Cin; p.Cb = s->Cout; p.Cin_w = s->Cin; p.pix = s->Cin;
+    p.M = p.g.N * p.g.H * p.g.W; p.Ktot = p.g.Th * p.g.Tw * s->Cin;
+    p.x_bytes = (unsigned)(xi * s->N * 4ull);
+    p.pre_slope = 1.f; p.mask_slope = 1.f; p.out_scale = 1.f; p.post_slope = 1.f;
+    p.tune_kind = 0;
+    p.epi = 1; p.no_split = 1;
+    const bool gen = (s->Cin % BK) != 0 || ((uintptr_t)x & 15) || ((uintptr_t)w & 15);
+    if (gen) launch_igemm<0, 1>(p, yi * s->N, (hipStream_t)stream);
+    else launch_igemm<0, 0>(p, yi * s->N, (hipStream_t)stream);
+    return gim_check_launch("gim_conv2d_infer");
 }
 
 static int dgrad_impl(const float* dy, const float* w, const float* sigma, const float* mask_x, float* dx,

@@ -2018,3 +2018,116 @@ class ImgAttMixFn(Function):
 
 
 img_att_mix = ImgAttMixFn.apply
+
+
+# --------------------------------------------------------------------------------------------
+# inference-only operators of the baseline authenticators (baselines.py): no autograd
+# --------------------------------------------------------------------------------------------
+def _no_grad_inputs(what, *ts):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
+        raise RuntimeError("ops.%s is an inference operator (no backward): call it under torch.no_grad()" % what)
+
+
+def conv2d_infer(x, w, bias=None, slope=None, stride=1):
+    """y = prelu_c(conv(x, w, stride, padding=(KH-1)/2) + bias).  x [N, H, W, Cin] NHWC, w [Cout, KH, KH, Cin] (the library's storage
+    order), bias / slope [Cout] or None (slope None: no activation, zeros: ReLU).  Returns [N, H/stride, W/stride, Cout]."""
+    lib = _lib.load()
+    _no_grad_inputs("conv2d_infer", x, w, bias, slope)
+    x, w = _req(x, "x"), _req(w, "w")
+    N, H, W, Cin = x.shape
+    Cout, KH = w.shape[0], w.shape[1]
+    if tuple(w.shape) != (Cout, KH, KH, Cin):
+        raise RuntimeError("conv2d_infer: weight %s does not match [Cout, KH, KH, Cin = %d]" % (tuple(w.shape), Cin))
+    for name, v in (("bias", bias), ("slope", slope)):
+        if v is not None and tuple(_req(v, name).shape) != (Cout,):
+            raise RuntimeError("conv2d_infer: %s must be [Cout]" % name)
+    bias = None if bias is None else _req(bias, "bias")
+    slope = None if slope is None else _req(slope, "slope")
+    sh = _lib.GimInferConv(N, H, W, Cin, Cout, KH, stride)
+    y = torch.empty((N, H // stride, W // stride, Cout), device=x.device, dtype=torch.float32)
+    if _FLOPS is not None:
+        key = ("infer", (N, H // stride, W // stride, Cin, Cout, KH, stride))
+        _FLOPS.setdefault(key, [0, 2.0 * N * (H // stride) * (W // stride) * Cin * Cout * KH * KH])[0] += 1
+    check(lib.gim_conv2d_infer(_p(x), _p(w), _p(bias), _p(slope), _p(y), ctypes.byref(sh), _stream()), "conv2d_infer")
+    return y
+
+
+def linear_infer(x, w, bias=None, slope=None):
+    """[rows, in] x [out, in]^T (+ bias, + per-output PReLU): conv2d_infer on a 1x1 map."""
+    return conv2d_infer(x.view(x.shape[0], 1, 1, x.shape[1]), w.view(w.shape[0], 1, 1, w.shape[1]), bias, slope).view(x.shape[0], w.shape[0])
+
+
+def maxpool2(x, relu=False):
+    """nn.MaxPool2d(2) of an NHWC map; relu: max(., 0) on the pooled value (= pooling the ReLU of the map)."""
+    lib = _lib.load()
+    _no_grad_inputs("maxpool2", x)
+    x = _req(x, "x")
+    N, H, W, C = x.shape
+    y = torch.empty((N, H // 2, W // 2, C), device=x.device, dtype=torch.float32)
+    check(lib.gim_maxpool2_act(_p(x), _p(y), N, H, W, C, 1 if relu else 0, _stream()), "maxpool2_act")
+    return y
+
+
+def channel_affine(x, scale, shift):
+    """y = x * scale[c] + shift[c] over the last dim (inference BatchNorm)."""
+    lib = _lib.load()
+    _no_grad_inputs("channel_affine", x, scale, shift)
+    x, scale, shift = _req(x, "x"), _req(scale, "scale"), _req(shift, "shift")
+    C = x.shape[-1]
+    y = torch.empty_like(x)
+    check(lib.gim_channel_affine(_p(x), _p(scale), _p(shift), _p(y), x.numel() // C, C, _stream()), "channel_affine")
+    return y
+
+
+def se_tail(res, gate, shortcut, sstride=1, scale=None, shift=None):
+    """out = res * sigmoid(gate[n, c]) + shortcut[n, ::sstride, ::sstride, c]; with scale / shift also out * scale[c] + shift[c].
+    Returns out, or (out, out_bn)."""
+    lib = _lib.load()
+    _no_grad_inputs("se_tail", res, gate, shortcut, scale, shift)
+    res, gate, shortcut = _req(res, "res"), _req(gate, "gate"), _req(shortcut, "shortcut")
+    N, Ho, Wo, C = res.shape
+    if tuple(shortcut.shape) != (N, Ho * sstride, Wo * sstride, C) or tuple(gate.shape) != (N, C):
+        raise RuntimeError("se_tail: shortcut %s / gate %s do not match res %s at sstride %d"
+                           % (tuple(shortcut.shape), tuple(gate.shape), tuple(res.shape), sstride))
+    out = torch.empty_like(res)
+    out_bn = None
+    if scale is not None:
+        scale, shift = _req(scale, "scale"), _req(shift, "shift")
+        out_bn = torch.empty_like(res)
+    check(lib.gim_se_tail(_p(res), _p(gate), _p(shortcut), _p(scale), _p(shift), _p(out), _p(out_bn), N, Ho, Wo, C, sstride, _stream()),
+          "se_tail")
+    return out if out_bn is None else (out, out_bn)
+
+
+def pair_score(a, b):
+    """-(|| a / |a| - b / |b| ||^2) per row of two [B, D] matrices."""
+    lib = _lib.load()
+    _no_grad_inputs("pair_score", a, b)
+    a, b = _req(a, "a"), _req(b, "b")
+    if a.shape != b.shape or a.dim() != 2:
+        raise RuntimeError("pair_score: two [B, D] matrices of one shape")
+    out = torch.empty((a.shape[0],), device=a.device, dtype=torch.float32)
+    check(lib.gim_pair_score(_p(a), _p(b), _p(out), a.shape[0], a.shape[1], _stream()), "pair_score")
+    return out
+
+
+def absdiff(a, b):
+    """|a - b|, elementwise."""
+    lib = _lib.load()
+    _no_grad_inputs("absdiff", a, b)
+    a, b = _req(a, "a"), _req(b, "b")
+    if a.shape != b.shape:
+        raise RuntimeError("absdiff: shapes differ")
+    y = torch.empty_like(a)
+    check(lib.gim_absdiff(_p(a), _p(b), _p(y), a.numel(), _stream()), "absdiff")
+    return y
+
+
+def l2norm_rows(x):
+    """x / |x| per row of a [B, D] matrix."""
+    lib = _lib.load()
+    _no_grad_inputs("l2norm_rows", x)
+    x = _req(x, "x")
+    y = torch.empty_like(x)
+    check(lib.gim_l2norm_rows(_p(x), _p(y), x.shape[0], x.shape[1], _stream()), "l2norm_rows")
+    return y

@@ -2,6 +2,7 @@
 trainer protocol needs (GlobalStep :15-33, DataParallelMock :36-42, adjust_batch_size :167-171,
 CheckpointIO training/checkpoints.py:9-44), plus ``EpisodeParallel``: the one-process-per-GPU replacement of
 ``nn.DataParallel`` (training/gim_img_training.py:406-411)."""
+import json
 import math
 import os
 
@@ -167,3 +168,17 @@ class CheckpointIO:
             else:
                 print("Warning: Could not find %s in checkpoint!" % name)
         return payload["global_step"], payload["last_epoch"]
+
+
+def load_args(outdir):
+    """The experiment's ``args.json`` as a dict (training/utils.py:153-157)."""
+    with open(os.path.join(outdir, "args.json")) as f:
+        return json.load(f)
+
+
+def get_latest_ckpt(ckpt_dir_path, prefix='model_', suffix='.pt'):
+    """Path of the checkpoint with the largest step number in its name (training/utils.py:160-164)."""
+    names = [f for f in os.listdir(ckpt_dir_path) if f.startswith(prefix) and f.endswith(suffix) and f[len(prefix):-len(suffix)].isdigit()]
+    if not names:
+        raise FileNotFoundError("no %s*%s checkpoint in %s" % (prefix, suffix, ckpt_dir_path))
+    return os.path.join(ckpt_dir_path, max(names, key=lambda f: int(f[len(prefix):-len(suffix)])))
