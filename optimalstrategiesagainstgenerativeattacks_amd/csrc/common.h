@@ -54,12 +54,14 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
 
 __device__ __forceinline__ float lrelu_f(float v, float slope) { return v > 0.f ? v : v * slope; }
 
-// conv_tiny.hip: direct convolution of the 3 -> 3 / 1 -> 1 image layers (3x3, 9x9; plain geometry).  Each returns false when the
-// shape is not one of them (the implicit-GEMM kernels run); plan_out != nullptr: record the launch plan, launch nothing.
+// conv_tiny.hip: direct convolution of the 3 -> 3 / 1 -> 1 image layers (3x3, 9x9; plain geometry): one workgroup per
+// GIM_TINY_TILE x GIM_TINY_TILE output tile of one image.  gim_tiny_shape is the eligibility test and gim_tiny_grid the launch grid
+// of all three directions (the planners in conv_igemm.hip report them); the launchers run eligible shapes only.
+constexpr int GIM_TINY_TILE = 16;
 bool gim_tiny_shape(const gim_conv_shape* s);
-bool gim_tiny_fwd(const float* x, const float* w, const float* bias, const float* sigma, const float* res, float* y,
-                  const gim_conv_shape* s, hipStream_t st, int32_t* plan_out);
-bool gim_tiny_dgrad(const float* dy, const float* w, const float* sigma, const float* mask_x, float* dx, const gim_conv_shape* s,
-                    hipStream_t st, int32_t* plan_out);
-bool gim_tiny_wgrad_acc(const float* dy, const float* x, float* acc, float* bias_acc, const gim_conv_shape* s, hipStream_t st,
-                        int32_t* plan_out);
+dim3 gim_tiny_grid(const gim_conv_shape* s);
+void gim_tiny_fwd(const float* x, const float* w, const float* bias, const float* sigma, const float* res, float* y,
+                  const gim_conv_shape* s, hipStream_t st);
+void gim_tiny_dgrad(const float* dy, const float* w, const float* sigma, const float* mask_x, float* dx, const gim_conv_shape* s,
+                    hipStream_t st);
+void gim_tiny_wgrad_acc(const float* dy, const float* x, float* acc, float* bias_acc, const gim_conv_shape* s, hipStream_t st);

@@ -1772,258 +1772,251 @@ static int plan_ksplit(long long wgs, int nk, int tile_area, int want_ks) {
     return ks < 1 ? 1 : (int)ks;
 }
 
-// gim_conv_launch_plan: when this thread-local pointer is set, the launchers below record what they WOULD launch
-// ({table row found, BM, BN, split-K | wgrad slices, grid x, y, z, matrix path}) and launch nothing.
-static thread_local int32_t* t_plan_out = nullptr;
-// an argument error found only once the launch configuration is known (set by the launcher, returned by the entry point)
-static thread_local bool t_launch_refused = false;
+// Forward-style launches (fwd, infer, dgrad, dgrad_t, dgrad_res, x-fold, rows form): plan_igemm decides, run_igemm launches.  The plan is a
+// function of the filled ConvP and the operand path alone; the entry points and gim_conv_launch_plan call the same planner.
+enum IgemmFamily { IGEMM_TAP = 0, IGEMM_PATCH = 1, IGEMM_F16 = 2, IGEMM_PATCH_F16 = 3 };   // conv_igemm_kernel, _patch_kernel, _f16_kernel, _patch_f16_kernel
+struct IgemmPlan {
+    int family;
+    int BM, BN, KB;       // output tile; channels per K step
+    int ksplit, kper;     // K slices over grid.z, K steps per slice (the kernels read them from ConvP: plan_igemm writes both)
+    int gx, gy, gz;
+    int lds_bytes;        // dynamic LDS (the patch-resident kernels)
+    int table_hit;        // a row of the launch table chose tile and split
+};   // (position-major rows are part of the decision too: plan_igemm writes Geo.pm and its perms into the ConvP)
 
-template <int BM, int BN, int TM, int TN, int BMODE, int GEN, int KB = 16>
-static void launch_cfg_kb(ConvP p, size_t y_elems, hipStream_t st, bool table_hit) {
-    const int gx = (p.M + BM - 1) / BM, gy = (p.Cb + BN - 1) / BN;
-    const int ncls = p.g.pc ? 4 : 1;
-    const int nk = (p.Ktot + KB - 1) / KB;
+// the output tiles of the forward-style kernels by tile code (gim_conv_shape.tune_tile, launch-table rows); the two narrow ones have
+// no code of their own: <= 32 output channels always take them (tap-major kernel only)
+struct TileCfg { int code, BM, BN; };
+static const TileCfg g_tiles[] = {{128, 128, 128}, {641, 64, 128}, {1264, 128, 64}, {64, 64, 64}, {12832, 128, 32}, {12816, 128, 16}};
+
+// tile by shape, for > 32 output channels: the largest accumulator block the channel count fills; parallelism for small M comes from
+// split-K.  t128 = 128x128 tiles of the launch; rows128 = a 128-row patch tile holds whole image rows (patch-resident kernels).
+// The fp16 kernels are bound by operand traffic: the largest tile that still fills the chip.
+static int heuristic_tile(int family, int M, int Cb, long long t128, bool rows128) {
+    if (family == IGEMM_TAP || family == IGEMM_PATCH) {
+        if (Cb > 64) return M <= 64 ? 641 : (t128 < GIM_SMALL_TILES ? 64 : 641);
+        return M <= 64 ? 64 : 1264;
+    }
+    if (family == IGEMM_F16) {
+        if (M <= 64 || t128 < GIM_SMALL_TILES) return 64;
+        return Cb > 64 ? (t128 < 256 ? 641 : 128) : 1264;
+    }
+    if (Cb > 64) {   // patch-resident fp16; 128-row tiles: whole image rows, enough of them to fill the chip
+        if (rows128 && t128 >= 256) return 128;
+        return (M > 64 && t128 >= GIM_SMALL_TILES) ? 641 : 64;
+    }
+    return (rows128 && t128 >= GIM_SMALL_TILES) ? 1264 : 64;
+}
+
+// The whole launch decision; bmode / gen: operand path of conv_igemm_kernel (BMODE, GENF).  Tile / split: the caller's explicit choice
+// (ConvP.tune_tile / tune_ks; tune_tile < 0 = heuristics only), else the table row of this shape, else the heuristic.  Tile code + 20000 =
+// the patch-resident kernel (plain 3x3 layers); rows and caller choices without it keep the tap-major loop they were tuned on; a launch with
+// neither takes the patch-resident kernel where the geometry allows it (tools/patch_autotune.py compares the two kernels per layer).
+static IgemmPlan plan_igemm(ConvP& p, int bmode, int gen) {
+    IgemmPlan q{};
+    const Geo& g = p.g;
+    const int M = p.M, Cb = p.Cb, HW = g.H * g.W, ncls = g.pc ? 4 : 1;
+    const long long t128 = (long long)((M + 127) / 128) * ((Cb + 127) / 128) * ncls;
+    // the patch-resident and the fp16 kernels: k-contiguous operands on 16-byte loads, >= 32 output channels ...
+    const bool vec_ops = p.pix == p.Ca && Cb >= 32 && !((uintptr_t)p.x & 15) && !((uintptr_t)p.w & 15);
+    // ... the patch-resident ones: a plain 3x3 convolution on a map of >= 64 pixels (a one-pixel-wide map of >= 128 rows:
+    // (BM / W + 2) * (W + 2) patch pixels would exceed the P_PER quads a thread stages)
+    const bool plain3x3 = !g.pc && !g.ups && g.s_in == 1 && g.s_in_x == 1 && g.os == 1 && g.Th == 3 && g.Tw == 3 && HW >= 64 && g.W >= 2;
+    const bool rows128 = HW >= 128 && g.W <= 64;
+    int want_ks = p.tune_ks, cfg;
+    if (bmode == 0 && gen == 0 && p.f16 && p.Ca % 32 == 0 && vec_ops) {
+        // fp16 operands: K steps of 32, tile by shape; no table rows (the table was measured on the fp32 kernels), no caller tile
+        q.family = plain3x3 ? IGEMM_PATCH_F16 : IGEMM_F16;
+        q.KB = 32;
+        cfg = heuristic_tile(q.family, M, Cb, t128, rows128);
+    } else {
+        const bool forced = p.tune_tile != 0 || p.tune_ks > 0;
+        const TuneEntry* te = forced ? nullptr : tune_lookup(p.tune_kind, M, p.Ca, Cb, p.Ktot, g.pc);
+        if (te) want_ks = te->ks;
+        q.table_hit = te != nullptr;
+        int want = p.tune_tile > 0 ? p.tune_tile : (te ? te->tile : 0);   // 0: heuristic
+        const bool patch_row = want >= 20000;
+        if (patch_row) want -= 20000;
+        const bool patch_ok = gen == 0 && plain3x3 && vec_ops && p.Ca % 16 == 0 && !(bmode == 1 && Cb % 4 != 0);
+        q.KB = 16;
+        if ((patch_row || (!te && p.tune_tile == 0 && p.tune_ks == 0)) && patch_ok) {
+            q.family = IGEMM_PATCH;
+            cfg = want == 6432 ? 64 : want;
+            if (cfg != 128 && cfg != 641 && cfg != 1264 && cfg != 64) cfg = heuristic_tile(q.family, M, Cb, t128, rows128);
+            // <= 64 output channels: 64-column tiles; 128-row tiles: whole image rows only
+            if (Cb <= 64 && (cfg == 128 || cfg == 641)) cfg = cfg == 128 ? 1264 : 64;
+            if ((cfg == 128 || cfg == 1264) && !rows128) cfg = cfg == 128 ? 641 : 64;
+            if (Cb <= 64 && cfg == 641) cfg = 64;
+        } else {
+            q.family = IGEMM_TAP;
+            if (Cb > 64) {
+                cfg = want ? want : heuristic_tile(q.family, M, Cb, t128, rows128);
+                if (cfg != 641 && cfg != 1264 && cfg != 64 && cfg != 6432) cfg = 128;
+            } else if (Cb > 32) {
+                cfg = (want == 64 || want == 6432 || want == 1264) ? want : heuristic_tile(q.family, M, Cb, t128, rows128);
+            } else {
+                cfg = Cb > 16 ? 12832 : 12816;   // (128x16: the 16x16x4 MFMA tile for <= 16 output channels)
+            }
+            // tile code 6432 = the 64x64 tile with K step 32 (fast path with Ca % 32 == 0 only): the small tile does 8 MFMAs per wave
+            // and K step, so the per-step costs (barrier, loop, address update, LDS round trip) weigh twice as much as on the 64x128
+            // tile; a 32-deep step halves them at 36 KB of LDS (still 4 workgroups per CU)
+            if (cfg == 6432 && gen == 0 && p.Ca % 32 == 0) q.KB = 32;
+            if (cfg == 6432) cfg = 64;
+        }
+    }
+    for (const TileCfg& t : g_tiles)
+        if (t.code == cfg) { q.BM = t.BM; q.BN = t.BN; }
 #ifndef GIM_NO_PM   // (a second build of the library for same-box A/B runs)
     // small maps: position-major rows, padding taps skipped (Geo.pm) - a tile of BM rows then holds BM / N pixel positions
-    if constexpr (GEN == 0) {
-        const int taps = p.g.Th * p.g.Tw;
-        p.g.pm = (taps > 1 && taps <= 32 && p.g.H * p.g.W <= PM_MAX_PIXELS && p.g.N >= PM_MIN_IMAGES && p.pix == p.Ca && p.Ca % KB == 0) ? 1 : 0;
+    if (q.family == IGEMM_TAP && gen == 0) {
+        const int taps = g.Th * g.Tw;
+        p.g.pm = (taps > 1 && taps <= 32 && HW <= PM_MAX_PIXELS && g.N >= PM_MIN_IMAGES && p.pix == p.Ca && p.Ca % q.KB == 0) ? 1 : 0;
         if (p.g.pm) pm_make_perms(p.g);
     }
 #endif
-    p.ksplit = p.no_split ? 1 : plan_ksplit((long long)gx * gy * ncls, nk, BM * BN, p.tune_ks);
-    p.kper = (nk + p.ksplit - 1) / p.ksplit;
-    p.ksplit = (nk + p.kper - 1) / p.kper;
-    if (t_plan_out) {
-        // out[7] bits 8..: the share of the launch's K steps that is SKIPPED, in 1/1000 (position-major rows skip padding taps; else 0)
-        const int32_t v[8] = {table_hit ? 1 : 0, BM, BN, p.ksplit, gx, gy, p.ksplit * ncls, (1000 - pm_valid_permille(p.g, p.M, BM)) << 8};
-        for (int i = 0; i < 8; ++i) t_plan_out[i] = v[i];
-        return;
-    }
-    if (p.ksplit > 1 && p.post_slope != 1.f) {   // the K slices are combined by addition: no nonlinearity behind them
-        gim_set_error("conv fwd: post_slope with a launch that splits K (ask gim_conv_launch_plan first)");
-        t_launch_refused = true;
-        return;
-    }
-    if (p.ksplit > 1 && !p.y_zeroed) (void)hipMemsetAsync(p.y, 0, y_elems * sizeof(float), st);
-    if constexpr (BMODE == 0 && (GEN & 2) == 0) {   // the inference epilogue exists for the forward operand path only
-        if (p.epi) {
-            hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, TM, TN, BMODE, GEN, KB, 1>), dim3(gx, gy, ncls), dim3(256), 0, st, p);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, TM, TN, BMODE, GEN, KB>), dim3(gx, gy, p.ksplit * ncls), dim3(256), 0, st, p);
-}
-
-template <int BM, int BN, int TM, int TN, int BMODE, int GEN>
-static void launch_cfg(const ConvP& p, size_t y_elems, hipStream_t st, bool table_hit) {
-    launch_cfg_kb<BM, BN, TM, TN, BMODE, GEN>(p, y_elems, st, table_hit);
-}
-
-// 64x64 tile (tile code 64), optionally with K step 32 (tile code 6432: fp32 MFMA fast path with Ca % 32 == 0 only): the small
-// tile does 8 MFMAs per wave and K step, so the per-step costs (barrier, loop, address update, LDS round trip) weigh twice as
-// much as on the 64x128 tile; a 32-deep step halves them at 36 KB of LDS (still 4 workgroups per CU).
-template <int BMODE, int GEN>
-static void launch_64x64(const ConvP& p, size_t y_elems, hipStream_t st, bool table_hit, bool kb32) {
-    if constexpr (GEN == 0) {
-        if (kb32 && p.Ca % 32 == 0) {
-            launch_cfg_kb<64, 64, 1, 1, BMODE, GEN, 32>(p, y_elems, st, table_hit);
-            return;
-        }
-    }
-    launch_cfg<64, 64, 1, 1, BMODE, GEN>(p, y_elems, st, table_hit);
-}
-
-// Patch-resident launch (conv_igemm_patch_kernel) of a plain 3x3 convolution on the fast path, when the geometry allows it; the
-// tile and split-K choice are the caller's / the table row's (tile code + 20000) / the heuristic's.  Returns false when the launch
-// is not eligible (the tap-major kernel runs).  tools/patch_autotune.py compares the two kernels per layer.
-template <int BM, int BN, int TM, int TN, int BMODE>
-static void launch_patch_cfg(ConvP p, size_t y_elems, hipStream_t st, bool table_hit) {
-    const int gx = (p.M + BM - 1) / BM, gy = (p.Cb + BN - 1) / BN;
-    const int chunks = p.Ca / 16, T = 9;
-    int ks = p.no_split ? 1 : plan_ksplit((long long)gx * gy, chunks * T, BM * BN, p.tune_ks);
-    if (ks > chunks) ks = chunks;
-    const int cps = (chunks + ks - 1) / ks;
-    p.ksplit = (chunks + cps - 1) / cps;
-    p.kper = cps * T;
-    if (t_plan_out) {
-        const int32_t v[8] = {table_hit ? 1 : 0, BM, BN, p.ksplit, gx, gy, p.ksplit, 1};
-        for (int i = 0; i < 8; ++i) t_plan_out[i] = v[i];
-        return;
-    }
-    if (p.ksplit > 1 && p.post_slope != 1.f) {
-        gim_set_error("conv fwd: post_slope with a launch that splits K (ask gim_conv_launch_plan first)");
-        t_launch_refused = true;
-        return;
-    }
-    if (p.ksplit > 1 && !p.y_zeroed) (void)hipMemsetAsync(p.y, 0, y_elems * sizeof(float), st);
-    const int Wt = p.g.W < BM ? p.g.W : BM;
-    const int PP = (BM / Wt + 2) * (Wt + 2);
-    const int P_SZ = (PP * 20 + 3) & ~3;
-    const int B_SZ = (BMODE == 0) ? BN * 20 : 16 * BN;
-    const size_t lds = (size_t)(2 * P_SZ + 2 * B_SZ) * sizeof(float);
-    if constexpr (BMODE == 0) {
-        if (p.epi) {
-            hipLaunchKernelGGL((conv_igemm_patch_kernel<BM, BN, TM, TN, BMODE, 1>), dim3(gx, gy, 1), dim3(256), lds, st, p);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((conv_igemm_patch_kernel<BM, BN, TM, TN, BMODE>), dim3(gx, gy, p.ksplit), dim3(256), lds, st, p);
-}
-
-template <int BMODE>
-static bool launch_patch(const ConvP& p, size_t y_elems, hipStream_t st, int want, bool table_hit) {
-    const Geo& g = p.g;
-    if (g.pc || g.ups || g.s_in != 1 || g.s_in_x != 1 || g.os != 1 || g.Th != 3 || g.Tw != 3) return false;
-    if (p.Ca % 16 != 0 || p.pix != p.Ca || p.Cb < 32 || ((uintptr_t)p.x & 15) || ((uintptr_t)p.w & 15)) return false;
-    if (BMODE == 1 && p.Cb % 4 != 0) return false;
-    const int HW = g.H * g.W;
-    if (HW < 64) return false;
-    if (g.W < 2) return false;   // a one-pixel-wide map of >= 128 rows: (BM / W + 2) * (W + 2) patch pixels would exceed the P_PER quads a thread stages
-    // tile: the caller's / table's choice, else as launch_igemm's heuristic; 128-row tiles need H * W >= 128 and W <= 64
-    int cfg = want;
-    if (cfg == 6432) cfg = 64;
-    if (cfg != 128 && cfg != 641 && cfg != 1264 && cfg != 64) {
-        if (p.Cb > 64) {
-            const long long t128 = (long long)((p.M + 127) / 128) * ((p.Cb + 127) / 128);
-            cfg = p.M <= 64 ? 641 : (t128 < GIM_SMALL_TILES ? 64 : 641);
+    q.gx = (M + q.BM - 1) / q.BM;
+    q.gy = (Cb + q.BN - 1) / q.BN;
+    const bool patch = q.family == IGEMM_PATCH || q.family == IGEMM_PATCH_F16;
+    if (patch) {   // split in whole channel chunks (the patch stays resident over the 9 taps of a chunk)
+        const int chunks = p.Ca / q.KB, T = 9;
+        int ks = p.no_split ? 1 : plan_ksplit((long long)q.gx * q.gy, chunks * T, q.BM * q.BN, want_ks);
+        if (ks > chunks) ks = chunks;
+        const int cps = (chunks + ks - 1) / ks;
+        q.ksplit = (chunks + cps - 1) / cps;
+        q.kper = cps * T;
+        const int Wt = g.W < q.BM ? g.W : q.BM;
+        const int PP = (q.BM / Wt + 2) * (Wt + 2);
+        if (q.family == IGEMM_PATCH) {
+            const int P_SZ = (PP * 20 + 3) & ~3, B_SZ = (bmode == 0) ? q.BN * 20 : 16 * q.BN;
+            q.lds_bytes = (2 * P_SZ + 2 * B_SZ) * (int)sizeof(float);
         } else {
-            cfg = p.M <= 64 ? 64 : 1264;
+            const int P_SZ = (PP * 40 + 7) & ~7;
+            q.lds_bytes = (2 * P_SZ + 2 * q.BN * 40) * (int)sizeof(_Float16);
         }
+    } else {       // split in K steps
+        const int nk = (p.Ktot + q.KB - 1) / q.KB;
+        q.ksplit = p.no_split ? 1 : plan_ksplit((long long)q.gx * q.gy * ncls, nk, q.BM * q.BN, want_ks);
+        q.kper = (nk + q.ksplit - 1) / q.ksplit;
+        q.ksplit = (nk + q.kper - 1) / q.kper;
     }
-    if (p.Cb <= 64 && (cfg == 128 || cfg == 641)) cfg = cfg == 128 ? 1264 : 64;
-    if ((cfg == 128 || cfg == 1264) && (HW < 128 || g.W > 64)) cfg = cfg == 128 ? 641 : 64;
-    if (p.Cb <= 64 && cfg == 641) cfg = 64;
-    if (cfg == 128) launch_patch_cfg<128, 128, 2, 2, BMODE>(p, y_elems, st, table_hit);
-    else if (cfg == 641) launch_patch_cfg<64, 128, 1, 2, BMODE>(p, y_elems, st, table_hit);
-    else if (cfg == 1264) launch_patch_cfg<128, 64, 2, 1, BMODE>(p, y_elems, st, table_hit);
-    else launch_patch_cfg<64, 64, 1, 1, BMODE>(p, y_elems, st, table_hit);
-    return true;
+    q.gz = q.ksplit * ncls;
+    p.ksplit = q.ksplit;
+    p.kper = q.kper;
+    return q;
 }
 
-// fp16-operand launch (conv_igemm_f16_kernel): K steps of 32, tile by shape - the kernel is bound by operand traffic, so the largest
-// tile that still fills the chip; split-K as for the fp32 kernels.  No table rows (the table was measured on the fp32 kernels).
-template <int BM, int BN, int TM, int TN>
-static void launch_f16_cfg(ConvP p, size_t y_elems, hipStream_t st) {
-    const int gx = (p.M + BM - 1) / BM, gy = (p.Cb + BN - 1) / BN;
-    const int ncls = p.g.pc ? 4 : 1;
-    const int nk = p.Ktot / 32;
-    p.ksplit = p.no_split ? 1 : plan_ksplit((long long)gx * gy * ncls, nk, BM * BN, p.tune_ks);
-    p.kper = (nk + p.ksplit - 1) / p.ksplit;
-    p.ksplit = (nk + p.kper - 1) / p.kper;
-    if (t_plan_out) {
-        const int32_t v[8] = {0, BM, BN, p.ksplit, gx, gy, p.ksplit * ncls, 2};
-        for (int i = 0; i < 8; ++i) t_plan_out[i] = v[i];
-        return;
+// one tile configuration of run_igemm: the kernel of the plan's family, and among its instantiations the plan's K step and the call's
+// epilogue.  (EPI = 1 launches never split K - ConvP.epi comes with no_split - so the plan's grid is theirs too.)
+template <int BM, int BN, int TM, int TN, int BMODE, int GEN>
+static void launch_tile(const ConvP& p, const IgemmPlan& q, hipStream_t st) {
+    constexpr bool WIDE = BN >= 64;                          // the patch-resident and fp16 kernels exist for the four tiles of >= 64 columns
+    constexpr bool HAS_EPI = BMODE == 0 && (GEN & 2) == 0;   // the inference epilogue exists for the forward operand path only
+    void (*kernel)(const ConvP) = conv_igemm_kernel<BM, BN, TM, TN, BMODE, GEN, 16>;
+    if constexpr (HAS_EPI) { if (p.epi) kernel = conv_igemm_kernel<BM, BN, TM, TN, BMODE, GEN, 16, 1>; }
+    if constexpr (BM == 64 && BN == 64 && GEN == 0) {
+        if (q.KB == 32) kernel = conv_igemm_kernel<BM, BN, TM, TN, BMODE, GEN, 32>;
+        if constexpr (HAS_EPI) { if (q.KB == 32 && p.epi) kernel = conv_igemm_kernel<BM, BN, TM, TN, BMODE, GEN, 32, 1>; }
     }
-    if (p.ksplit > 1 && p.post_slope != 1.f) {
-        gim_set_error("conv fwd: post_slope with a launch that splits K (ask gim_conv_launch_plan first)");
-        t_launch_refused = true;
-        return;
+    if constexpr (WIDE && GEN == 0) {
+        if (q.family == IGEMM_PATCH) kernel = conv_igemm_patch_kernel<BM, BN, TM, TN, BMODE>;
+        if constexpr (BMODE == 0) { if (q.family == IGEMM_PATCH && p.epi) kernel = conv_igemm_patch_kernel<BM, BN, TM, TN, BMODE, 1>; }
     }
-    if (p.ksplit > 1 && !p.y_zeroed) (void)hipMemsetAsync(p.y, 0, y_elems * sizeof(float), st);
-    hipLaunchKernelGGL((conv_igemm_f16_kernel<BM, BN, TM, TN>), dim3(gx, gy, p.ksplit * ncls), dim3(256), 0, st, p);
+    if constexpr (WIDE && BMODE == 0 && GEN == 0) {
+        if (q.family == IGEMM_F16) kernel = conv_igemm_f16_kernel<BM, BN, TM, TN>;
+        if (q.family == IGEMM_PATCH_F16) kernel = conv_igemm_patch_f16_kernel<BM, BN, TM, TN>;
+    }
+    hipLaunchKernelGGL(kernel, dim3(q.gx, q.gy, q.gz), dim3(256), q.lds_bytes, st, p);
 }
 
-// patch-resident fp16 launch of a plain 3x3 convolution (conv_igemm_patch_f16_kernel); split-K in whole 32-channel chunks
-template <int BM, int BN, int TM, int TN>
-static void launch_patch_f16_cfg(ConvP p, size_t y_elems, hipStream_t st) {
-    const int gx = (p.M + BM - 1) / BM, gy = (p.Cb + BN - 1) / BN;
-    const int chunks = p.Ca / 32, T = 9;
-    int ks = p.no_split ? 1 : plan_ksplit((long long)gx * gy, chunks * T, BM * BN, p.tune_ks);
-    if (ks > chunks) ks = chunks;
-    const int cps = (chunks + ks - 1) / ks;
-    p.ksplit = (chunks + cps - 1) / cps;
-    p.kper = cps * T;
-    if (t_plan_out) {
-        const int32_t v[8] = {0, BM, BN, p.ksplit, gx, gy, p.ksplit, 2};
-        for (int i = 0; i < 8; ++i) t_plan_out[i] = v[i];
-        return;
-    }
-    if (p.ksplit > 1 && p.post_slope != 1.f) {
-        gim_set_error("conv fwd: post_slope with a launch that splits K (ask gim_conv_launch_plan first)");
-        t_launch_refused = true;
-        return;
-    }
-    if (p.ksplit > 1 && !p.y_zeroed) (void)hipMemsetAsync(p.y, 0, y_elems * sizeof(float), st);
-    const int Wt = p.g.W < BM ? p.g.W : BM;
-    const int PP = (BM / Wt + 2) * (Wt + 2);
-    const int P_SZ = (PP * 40 + 7) & ~7;
-    const size_t lds = (size_t)(2 * P_SZ + 2 * BN * 40) * sizeof(_Float16);
-    hipLaunchKernelGGL((conv_igemm_patch_f16_kernel<BM, BN, TM, TN>), dim3(gx, gy, p.ksplit), dim3(256), lds, st, p);
-}
-
-static bool launch_patch_f16(const ConvP& p, size_t y_elems, hipStream_t st) {
-    const Geo& g = p.g;
-    if (g.pc || g.ups || g.s_in != 1 || g.s_in_x != 1 || g.os != 1 || g.Th != 3 || g.Tw != 3) return false;
-    const int HW = g.H * g.W;
-    if (HW < 64 || g.W < 2) return false;
-    const long long t128 = (long long)((p.M + 127) / 128) * ((p.Cb + 127) / 128);
-    const bool big = HW >= 128 && g.W <= 64 && t128 >= 256;      // 128-row tiles: whole image rows, enough of them to fill the chip
-    if (p.Cb > 64) {
-        if (big) launch_patch_f16_cfg<128, 128, 2, 2>(p, y_elems, st);
-        else if (p.M > 64 && t128 >= GIM_SMALL_TILES) launch_patch_f16_cfg<64, 128, 1, 2>(p, y_elems, st);
-        else launch_patch_f16_cfg<64, 64, 1, 1>(p, y_elems, st);
-    } else {
-        if (big || (HW >= 128 && g.W <= 64 && t128 >= GIM_SMALL_TILES)) launch_patch_f16_cfg<128, 64, 2, 1>(p, y_elems, st);
-        else launch_patch_f16_cfg<64, 64, 1, 1>(p, y_elems, st);
-    }
-    return true;
-}
-
-static bool launch_f16(const ConvP& p, size_t y_elems, hipStream_t st) {
-    if (p.Ca % 32 != 0 || p.pix != p.Ca || p.Cb < 32 || ((uintptr_t)p.x & 15) || ((uintptr_t)p.w & 15)) return false;
-    if (launch_patch_f16(p, y_elems, st)) return true;
-    const long long t128 = (long long)((p.M + 127) / 128) * ((p.Cb + 127) / 128) * (p.g.pc ? 4 : 1);
-    if (p.Cb > 64) {
-        if (p.M <= 64 || t128 < GIM_SMALL_TILES) launch_f16_cfg<64, 64, 1, 1>(p, y_elems, st);
-        else if (t128 < 256) launch_f16_cfg<64, 128, 1, 2>(p, y_elems, st);
-        else launch_f16_cfg<128, 128, 2, 2>(p, y_elems, st);
-    } else {
-        if (p.M <= 64 || t128 < GIM_SMALL_TILES) launch_f16_cfg<64, 64, 1, 1>(p, y_elems, st);
-        else launch_f16_cfg<128, 64, 2, 1>(p, y_elems, st);
-    }
-    return true;
-}
-
-// tile by shape (largest accumulator block the channel count fills); parallelism for small M comes from split-K.
-// tune_tile / tune_ks: the caller's explicit choice (gim_conv_shape.tune_tile / tune_ksplit; tune_tile < 0 = heuristics only),
-// else the table row of this shape, else the heuristic.
+// Launches what plan_igemm(p, BMODE, GEN) planned.  An argument error that only the plan reveals is returned before anything is enqueued.
 template <int BMODE, int GEN>
-static void launch_igemm(const ConvP& p, size_t y_elems, hipStream_t st) {
-    const int M = p.M, Cb = p.Cb;
-    if constexpr (BMODE == 0 && GEN == 0) {
-        if (p.f16 && launch_f16(p, y_elems, st)) return;
+static int run_igemm(const ConvP& p, const IgemmPlan& q, size_t y_elems, hipStream_t st) {
+    if (q.ksplit > 1 && p.post_slope != 1.f) {   // the K slices are combined by addition: no nonlinearity behind them
+        gim_set_error("conv fwd: post_slope with a launch that splits K (ask gim_conv_launch_plan first)");
+        return GIM_E_BADARG;
     }
-    ConvP pt = p;
-    const bool forced = p.tune_tile != 0 || p.tune_ks > 0;
-    const TuneEntry* te = forced ? nullptr : tune_lookup(p.tune_kind, M, p.Ca, Cb, p.Ktot, p.g.pc);
-    if (te) pt.tune_ks = te->ks;
-    const bool hit = te != nullptr;
-    int want = p.tune_tile > 0 ? p.tune_tile : (te ? te->tile : 0);   // 0: heuristic
-    // tile code + 20000: the patch-resident kernel (plain 3x3 layers); rows and caller choices without it keep the tap-major loop
-    // they were tuned on; a launch with neither row nor caller choice takes the patch-resident kernel where the geometry allows it
-    const bool patch_row = want >= 20000;
-    if (patch_row) want -= 20000;
-    if constexpr (GEN == 0) {
-        if ((patch_row || (!te && p.tune_tile == 0 && p.tune_ks == 0)) && launch_patch<BMODE>(pt, y_elems, st, want, hit)) return;
-    }
-    if (Cb > 64) {
-        const long long t128 = (long long)((M + 127) / 128) * ((Cb + 127) / 128) * (p.g.pc ? 4 : 1);
-        int cfg = want ? want : (M <= 64 ? 641 : (t128 < GIM_SMALL_TILES ? 64 : 641));
-        if (cfg == 641) launch_cfg<64, 128, 1, 2, BMODE, GEN>(pt, y_elems, st, hit);
-        else if (cfg == 1264) launch_cfg<128, 64, 2, 1, BMODE, GEN>(pt, y_elems, st, hit);
-        else if (cfg == 64 || cfg == 6432) launch_64x64<BMODE, GEN>(pt, y_elems, st, hit, cfg == 6432);
-        else launch_cfg<128, 128, 2, 2, BMODE, GEN>(pt, y_elems, st, hit);
-    } else if (Cb > 32) {
-        int cfg = (want == 64 || want == 6432 || want == 1264) ? want : (M <= 64 ? 64 : 1264);
-        if (cfg == 64 || cfg == 6432) launch_64x64<BMODE, GEN>(pt, y_elems, st, hit, cfg == 6432);
-        else launch_cfg<128, 64, 2, 1, BMODE, GEN>(pt, y_elems, st, hit);
-    } else if (Cb > 16) {
-        launch_cfg<128, 32, 1, 1, BMODE, GEN>(pt, y_elems, st, hit);
-    } else {
-        launch_cfg<128, 16, 1, 1, BMODE, GEN>(pt, y_elems, st, hit);   // 16x16x4 MFMA tile for <= 16 output channels
-    }
+    if (q.ksplit > 1 && !p.y_zeroed) (void)hipMemsetAsync(p.y, 0, y_elems * sizeof(float), st);
+    if (q.BM == 128 && q.BN == 128) launch_tile<128, 128, 2, 2, BMODE, GEN>(p, q, st);
+    else if (q.BM == 64 && q.BN == 128) launch_tile<64, 128, 1, 2, BMODE, GEN>(p, q, st);
+    else if (q.BM == 128 && q.BN == 64) launch_tile<128, 64, 2, 1, BMODE, GEN>(p, q, st);
+    else if (q.BM == 64 && q.BN == 64) launch_tile<64, 64, 1, 1, BMODE, GEN>(p, q, st);
+    else if (q.BN == 32) launch_tile<128, 32, 1, 1, BMODE, GEN>(p, q, st);
+    else launch_tile<128, 16, 1, 1, BMODE, GEN>(p, q, st);
+    return GIM_OK;
+}
+
+// One forward-style call, validated and filled (the first half of an entry point): what plan_igemm and run_igemm need.
+struct ConvCall { ConvP p; size_t y_elems; int bmode, gen; };   // y_elems: floats of the output (a split-K launch clears them first)
+
+// the second half of every forward-style entry point
+static int plan_and_run(ConvCall& c, void* stream, const char* what) {
+    const IgemmPlan q = plan_igemm(c.p, c.bmode, c.gen);
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if (c.bmode == 0) rc = c.gen ? run_igemm<0, 1>(c.p, q, c.y_elems, st) : run_igemm<0, 0>(c.p, q, c.y_elems, st);
+    else if (c.gen == 0) rc = run_igemm<1, 0>(c.p, q, c.y_elems, st);
+    else if (c.gen == 1) rc = run_igemm<1, 1>(c.p, q, c.y_elems, st);
+    else if (c.gen == 2) rc = run_igemm<1, 2>(c.p, q, c.y_elems, st);
+    else rc = run_igemm<1, 3>(c.p, q, c.y_elems, st);
+    return rc ? rc : gim_check_launch(what);
+}
+
+// What every forward-style entry point fills the same way: geometry, GEMM sizes, zero page, the buffer range of the gathered tensor
+// (Ca channels per tap, pix floats between its pixels) and the launch-table kind; with `tune`, the caller's launch overrides.
+static int convp_begin(ConvP& p, const Geo& g, int Ca, int Cb, int pix, int tune_kind, const gim_conv_shape* tune, const char* too_big) {
+    p.zero = zero_page();
+    p.pos_inf = __builtin_inff();
+    p.g = g;
+    p.Ca = Ca; p.Cb = Cb; p.pix = pix;
+    p.M = g.N * g.H * g.W; p.Ktot = g.Th * g.Tw * Ca;
+    const unsigned long long xb = (unsigned long long)g.N * g.Hin * g.Win * pix * 4ull;
+    GIM_CHECK_ARG(xb <= 0x7FFFFFF0ull, too_big);
+    p.x_bytes = (unsigned)xb;
+    p.tune_kind = tune_kind;
+    if (tune) { p.tune_tile = tune->tune_tile; p.tune_ks = tune->tune_ksplit; p.y_zeroed = tune->out_zeroed; }
+    return GIM_OK;
+}
+
+// Operands beyond the 32-bit buffer-offset range: the batch is halved (images are independent; per_image = floats of the larger
+// operand per image).  True: the caller runs `a`, then `b` on pointers advanced by a.N images.
+template <class Shape>
+static bool split_batch(const Shape& s, size_t per_image, Shape& a, Shape& b) {
+    if (s.N <= 1 || per_image * s.N * sizeof(float) <= BUF_MAX_BYTES) return false;
+    a = s; b = s;
+    a.N = s.N / 2; b.N = s.N - a.N;
+    return true;
+}
+
+// 3 -> 3 / 1 -> 1 image layers: direct convolution (conv_tiny.hip) unless the caller chose a launch (tune_* / deterministic mode)
+static bool tiny_route(const gim_conv_shape* s) { return s->tune_tile == 0 && s->tune_ksplit == 0 && gim_tiny_shape(s); }
+
+// elements per image of the input-side tensor (xi: x, dx, mask_x) and of the output-side one (yi: y, dy).  dx_side: the dgrads, whose
+// dx is at half resolution in the sub-pixel form only (a plain upsample's dx is produced at the full one)
+static void image_elems(const gim_conv_shape* s, bool dx_side, size_t& xi, size_t& yi) {
+    const int half = dx_side ? (s->ups && s->wfold ? 1 : 0) : s->ups;
+    xi = (size_t)(s->H >> half) * (s->W >> half) * s->Cin;
+    yi = (size_t)(s->H >> s->pool) * (s->W >> s->pool) * s->Cout;
+}
+
+static int fwd_call(ConvCall& c, const float* x, const float* w, const float* bias, const float* sigma, const float* residual, float* y,
+                    const gim_conv_shape* s) {
+    c = ConvCall{};
+    ConvP& p = c.p;
+    const bool up_fold = s->ups && s->wfold;
+    int rc = convp_begin(p, s->pool ? geo_s2(s, false) : (up_fold ? geo_pc(s, 0) : geo_plain(s, false)), s->Cin, s->Cout, s->Cin, 0, s,
+                         "conv: one image of the gathered tensor exceeds 2 GiB (32-bit buffer offsets)");
+    if (rc) return rc;
+    p.x = x; p.w = w; p.bias = bias; p.sigma = sigma; p.res = residual; p.mask_x = nullptr; p.y = y;
+    p.Cin_w = s->Cin;
+    p.pre_slope = s->pre_slope; p.mask_slope = 1.f; p.out_scale = s->pool ? 0.25f : 1.f; p.res_ups = s->res_ups;
+    GIM_CHECK_ARG(s->post_slope >= 0.f && s->post_slope <= 1.f, "conv fwd: post_slope must be in [0, 1] (0 or 1 = none)");
+    p.post_slope = (s->post_slope > 0.f) ? s->post_slope : 1.f;
+    p.f16 = s->prec == 1;
+    c.y_elems = (size_t)s->N * (s->H >> s->pool) * (s->W >> s->pool) * s->Cout;
+    GIM_CHECK_ARG(c.y_elems * sizeof(float) <= 0x7FFFFFF0ull, "conv: one image of the output exceeds 2 GiB (32-bit buffer offsets)");
+    c.bmode = 0;
+    c.gen = ((s->Cin % BK) != 0 || ((uintptr_t)x & 15) || ((uintptr_t)w & 15)) ? 1 : 0;
+    return GIM_OK;
 }
 
 extern "C" int gim_conv2d_fwd(const float* x, const float* w, const float* bias, const float* sigma, const float* residual,
@@ -2031,49 +2024,22 @@ extern "C" int gim_conv2d_fwd(const float* x, const float* w, const float* bias,
     int rc = check_shape(s);
     if (rc) return rc;
     GIM_CHECK_ARG(x && w && y, "conv fwd: null pointer");
-    // 3 -> 3 / 1 -> 1 image layers: direct convolution (conv_tiny.hip) unless the caller chose a launch (tune_* / deterministic mode)
-    if (s->tune_tile == 0 && s->tune_ksplit == 0 && gim_tiny_fwd(x, w, bias, sigma, residual, y, s, (hipStream_t)stream, t_plan_out))
-        return t_plan_out ? GIM_OK : gim_check_launch("gim_conv2d_fwd");
-    {   // operands beyond the 32-bit buffer-offset range: halve the batch (images are independent)
-        const size_t xi = (size_t)(s->H >> s->ups) * (s->W >> s->ups) * s->Cin;        // elements per image
-        const size_t yi = (size_t)(s->H >> s->pool) * (s->W >> s->pool) * s->Cout;
+    if (tiny_route(s)) {
+        gim_tiny_fwd(x, w, bias, sigma, residual, y, s, (hipStream_t)stream);
+        return gim_check_launch("gim_conv2d_fwd");
+    }
+    size_t xi, yi;
+    image_elems(s, false, xi, yi);
+    gim_conv_shape a, b;
+    if (split_batch(*s, xi > yi ? xi : yi, a, b)) {
         const size_t ri = s->res_ups ? yi / 4 : yi;
-        if (s->N > 1 && (xi > yi ? xi : yi) * s->N * sizeof(float) > BUF_MAX_BYTES) {
-            gim_conv_shape a = *s, b = *s;
-            a.N = s->N / 2; b.N = s->N - a.N;
-            rc = gim_conv2d_fwd(x, w, bias, sigma, residual, y, &a, stream);
-            if (rc) return rc;
-            return gim_conv2d_fwd(x + a.N * xi, w, bias, sigma, residual ? residual + a.N * ri : nullptr, y + a.N * yi, &b, stream);
-        }
+        rc = gim_conv2d_fwd(x, w, bias, sigma, residual, y, &a, stream);
+        if (rc) return rc;
+        return gim_conv2d_fwd(x + a.N * xi, w, bias, sigma, residual ? residual + a.N * ri : nullptr, y + a.N * yi, &b, stream);
     }
-    ConvP p{};
-    p.zero = zero_page();
-    p.pos_inf = __builtin_inff();
-    const bool up_fold = s->ups && s->wfold;
-    p.g = s->pool ? geo_s2(s, false) : (up_fold ? geo_pc(s, 0) : geo_plain(s, false));
-    p.x = x; p.w = w; p.bias = bias; p.sigma = sigma; p.res = residual; p.mask_x = nullptr; p.y = y;
-    p.Ca = s->Cin; p.Cb = s->Cout; p.Cin_w = s->Cin; p.pix = s->Cin;
-    p.M = p.g.N * p.g.H * p.g.W; p.Ktot = p.g.Th * p.g.Tw * s->Cin;
-    {
-        const unsigned long long xb = (unsigned long long)p.g.N * p.g.Hin * p.g.Win * p.Ca * 4ull;
-        GIM_CHECK_ARG(xb <= 0x7FFFFFF0ull, "conv: one image of the gathered tensor exceeds 2 GiB (32-bit buffer offsets)");
-        p.x_bytes = (unsigned)xb;
-    }
-    p.pre_slope = s->pre_slope; p.mask_slope = 1.f; p.out_scale = s->pool ? 0.25f : 1.f; p.res_ups = s->res_ups;
-    GIM_CHECK_ARG(s->post_slope >= 0.f && s->post_slope <= 1.f, "conv fwd: post_slope must be in [0, 1] (0 or 1 = none)");
-    p.post_slope = (s->post_slope > 0.f) ? s->post_slope : 1.f;
-    p.tune_kind = 0;
-    p.tune_tile = s->tune_tile; p.tune_ks = s->tune_ksplit; p.y_zeroed = s->out_zeroed;
-    p.f16 = s->prec == 1;
-    const size_t y_elems = (size_t)s->N * (s->H >> s->pool) * (s->W >> s->pool) * s->Cout;
-    GIM_CHECK_ARG(y_elems * sizeof(float) <= 0x7FFFFFF0ull, "conv: one image of the output exceeds 2 GiB (32-bit buffer offsets)");
-    const bool gen = (s->Cin % BK) != 0 || ((uintptr_t)x & 15) || ((uintptr_t)w & 15);
-    t_launch_refused = false;
-    if (gen) launch_igemm<0, 1>(p, y_elems, (hipStream_t)stream);
-    else launch_igemm<0, 0>(p, y_elems, (hipStream_t)stream);
-    if (t_launch_refused) return GIM_E_BADARG;
-    if (t_plan_out) return GIM_OK;
-    return gim_check_launch("gim_conv2d_fwd");
+    ConvCall c;
+    rc = fwd_call(c, x, w, bias, sigma, residual, y, s);
+    return rc ? rc : plan_and_run(c, stream, "gim_conv2d_fwd");
 }
 
 // Forward-only strided convolution with a per-channel epilogue (inference of the baseline authenticators, baselines.py): the plain
@@ -2104,28 +2070,55 @@ extern "C" int gim_conv2d_infer(const float* x, const float* w, const float* bia
     const int Ho = s->H / s->stride, Wo = s->W / s->stride;
     const size_t xi = (size_t)s->H * s->W * s->Cin, yi = (size_t)Ho * Wo * s->Cout;   // elements per image
     GIM_CHECK_ARG((xi > yi ? xi : yi) * sizeof(float) <= BUF_MAX_BYTES, "conv infer: one image exceeds 2 GiB (32-bit buffer offsets)");
-    if (s->N > 1 && (xi > yi ? xi : yi) * s->N * sizeof(float) > BUF_MAX_BYTES) {   // halve the batch (images are independent)
-        gim_infer_conv a = *s, b = *s;
-        a.N = s->N / 2; b.N = s->N - a.N;
+    gim_infer_conv a, b;
+    if (split_batch(*s, xi > yi ? xi : yi, a, b)) {
         const int rc = gim_conv2d_infer(x, w, bias, slope, y, &a, stream);
         if (rc) return rc;
         return gim_conv2d_infer(x + a.N * xi, w, bias, slope, y + a.N * yi, &b, stream);
     }
-    ConvP p{};
-    p.zero = zero_page();
-    p.pos_inf = __builtin_inff();
-    p.g = geo_strided(s);
+    ConvCall c{};
+    ConvP& p = c.p;
+    const int rc = convp_begin(p, geo_strided(s), s->Cin, s->Cout, s->Cin, 0, nullptr, "conv infer: one image exceeds 2 GiB (32-bit buffer offsets)");
+    if (rc) return rc;
     p.x = x; p.w = w; p.bias = bias; p.slope = slope; p.y = y;
-    p.Ca = s->Cin; p.Cb = s->Cout; p.Cin_w = s->Cin; p.pix = s->Cin;
-    p.M = p.g.N * p.g.H * p.g.W; p.Ktot = p.g.Th * p.g.Tw * s->Cin;
-    p.x_bytes = (unsigned)(xi * s->N * 4ull);
+    p.Cin_w = s->Cin;
     p.pre_slope = 1.f; p.mask_slope = 1.f; p.out_scale = 1.f; p.post_slope = 1.f;
-    p.tune_kind = 0;
     p.epi = 1; p.no_split = 1;
-    const bool gen = (s->Cin % BK) != 0 || ((uintptr_t)x & 15) || ((uintptr_t)w & 15);
-    if (gen) launch_igemm<0, 1>(p, yi * s->N, (hipStream_t)stream);
-    else launch_igemm<0, 0>(p, yi * s->N, (hipStream_t)stream);
-    return gim_check_launch("gim_conv2d_infer");
+    c.y_elems = yi * s->N;
+    c.gen = ((s->Cin % BK) != 0 || ((uintptr_t)x & 15) || ((uintptr_t)w & 15)) ? 1 : 0;
+    return plan_and_run(c, stream, "gim_conv2d_infer");
+}
+
+// dx from dy.  pool: dx [N,H,W,Cin] from dy [N,H/2,W/2,Cout] by input-parity classes; sub-pixel (ups+wfold): dx [N,H/2,W/2,Cin]
+// directly from dy [N,H,W,Cout] by a stride-2 gather; plain: dx at the conv's resolution
+static int dgrad_call(ConvCall& c, const float* dy, const float* w, const float* sigma, const float* mask_x, float* dx,
+                      const gim_conv_shape* s, bool transposed, const float* res_half, float res_scale) {
+    c = ConvCall{};
+    ConvP& p = c.p;
+    const bool up_fold = s->ups && s->wfold;
+    GIM_CHECK_ARG(!(mask_x && s->ups && !up_fold), "conv dgrad: mask_x with ups == 1 needs folded weights");
+    int rc = convp_begin(p, s->pool ? geo_pc(s, 1) : (up_fold ? geo_s2(s, true) : geo_plain(s, true)), s->Cout, s->Cin, s->Cout, 1, s,
+                         "conv: one image of the gathered tensor exceeds 2 GiB (32-bit buffer offsets)");
+    if (rc) return rc;
+    p.x = dy; p.w = w; p.bias = nullptr; p.sigma = sigma; p.res = res_half; p.res_scale = res_scale; p.mask_x = mask_x; p.y = dx;
+    p.Cin_w = s->Cin;
+    p.pre_slope = 1.f; p.mask_slope = s->pre_slope; p.out_scale = s->pool ? 0.25f : 1.f; p.res_ups = 0;
+    p.post_slope = 1.f;
+    c.y_elems = (size_t)s->N * (s->H >> (up_fold ? 1 : 0)) * (s->W >> (up_fold ? 1 : 0)) * s->Cin;
+    GIM_CHECK_ARG(c.y_elems * sizeof(float) <= 0x7FFFFFF0ull, "conv: one image of the output exceeds 2 GiB (32-bit buffer offsets)");
+    const bool gen = (s->Cout % BK) != 0 || ((uintptr_t)dy & 15);
+    const bool bscalar = (s->Cin % 4) != 0 || ((uintptr_t)w & 15);
+    p.f16 = transposed && s->prec == 1;   // fp16 operands: the k-contiguous (transposed-weights) form only - ops.py routes fp16 dgrads there
+    if (transposed) {
+        // WT[ci][a][b][co]: the weight rows are k-contiguous (k = (tap, co)), i.e. the forward kernel's operand layout
+        GIM_CHECK_ARG(!gen && !((uintptr_t)w & 15), "conv dgrad (transposed weights): Cout % 16 == 0 and 16-byte aligned operands required");
+        p.Cin_w = s->Cout;
+        p.tune_kind = 4;
+        c.bmode = 0; c.gen = 0;
+    } else {
+        c.bmode = 1; c.gen = (gen ? 1 : 0) | (bscalar ? 2 : 0);
+    }
+    return GIM_OK;
 }
 
 static int dgrad_impl(const float* dy, const float* w, const float* sigma, const float* mask_x, float* dx,
@@ -2133,59 +2126,22 @@ static int dgrad_impl(const float* dy, const float* w, const float* sigma, const
     int rc = check_shape(s);
     if (rc) return rc;
     GIM_CHECK_ARG(dy && w && dx, "conv dgrad: null pointer");
-    if (!transposed && !res_half && s->tune_tile == 0 && s->tune_ksplit == 0 && gim_tiny_dgrad(dy, w, sigma, mask_x, dx, s, (hipStream_t)stream, t_plan_out))
-        return t_plan_out ? GIM_OK : gim_check_launch("gim_conv2d_dgrad");
-    const bool up_fold = s->ups && s->wfold;
-    GIM_CHECK_ARG(!(mask_x && s->ups && !up_fold), "conv dgrad: mask_x with ups == 1 needs folded weights");
-    {
-        const size_t yi = (size_t)(s->H >> s->pool) * (s->W >> s->pool) * s->Cout;             // dy elements per image
-        const size_t xi = (size_t)(s->H >> (up_fold ? 1 : 0)) * (s->W >> (up_fold ? 1 : 0)) * s->Cin;   // dx (and mask) per image
-        if (s->N > 1 && (xi > yi ? xi : yi) * s->N * sizeof(float) > BUF_MAX_BYTES) {
-            gim_conv_shape a = *s, b = *s;
-            a.N = s->N / 2; b.N = s->N - a.N;
-            rc = dgrad_impl(dy, w, sigma, mask_x, dx, &a, stream, transposed, res_half, res_scale);
-            if (rc) return rc;
-            return dgrad_impl(dy + a.N * yi, w, sigma, mask_x ? mask_x + a.N * xi : nullptr, dx + a.N * xi, &b, stream, transposed,
-                              res_half ? res_half + a.N * (xi / 4) : nullptr, res_scale);
-        }
+    if (!transposed && !res_half && tiny_route(s)) {
+        gim_tiny_dgrad(dy, w, sigma, mask_x, dx, s, (hipStream_t)stream);
+        return gim_check_launch("gim_conv2d_dgrad");
     }
-    ConvP p{};
-    p.zero = zero_page();
-    p.pos_inf = __builtin_inff();
-    // pool: dx [N,H,W,Cin] from dy [N,H/2,W/2,Cout] by input-parity classes; sub-pixel (ups+wfold): dx
-    // [N,H/2,W/2,Cin] directly from dy [N,H,W,Cout] by a stride-2 gather; plain: dx at the conv's resolution
-    p.g = s->pool ? geo_pc(s, 1) : (up_fold ? geo_s2(s, true) : geo_plain(s, true));
-    p.x = dy; p.w = w; p.bias = nullptr; p.sigma = sigma; p.res = res_half; p.res_scale = res_scale; p.mask_x = mask_x; p.y = dx;
-    p.Ca = s->Cout; p.Cb = s->Cin; p.Cin_w = s->Cin; p.pix = s->Cout;
-    p.M = p.g.N * p.g.H * p.g.W; p.Ktot = p.g.Th * p.g.Tw * s->Cout;
-    {
-        const unsigned long long xb = (unsigned long long)p.g.N * p.g.Hin * p.g.Win * p.Ca * 4ull;
-        GIM_CHECK_ARG(xb <= 0x7FFFFFF0ull, "conv: one image of the gathered tensor exceeds 2 GiB (32-bit buffer offsets)");
-        p.x_bytes = (unsigned)xb;
+    size_t xi, yi;
+    image_elems(s, true, xi, yi);
+    gim_conv_shape a, b;
+    if (split_batch(*s, xi > yi ? xi : yi, a, b)) {
+        rc = dgrad_impl(dy, w, sigma, mask_x, dx, &a, stream, transposed, res_half, res_scale);
+        if (rc) return rc;
+        return dgrad_impl(dy + a.N * yi, w, sigma, mask_x ? mask_x + a.N * xi : nullptr, dx + a.N * xi, &b, stream, transposed,
+                          res_half ? res_half + a.N * (xi / 4) : nullptr, res_scale);
     }
-    p.pre_slope = 1.f; p.mask_slope = s->pre_slope; p.out_scale = s->pool ? 0.25f : 1.f; p.res_ups = 0;
-    p.post_slope = 1.f;
-    const size_t y_elems = (size_t)s->N * (s->H >> (up_fold ? 1 : 0)) * (s->W >> (up_fold ? 1 : 0)) * s->Cin;
-    GIM_CHECK_ARG(y_elems * sizeof(float) <= 0x7FFFFFF0ull, "conv: one image of the output exceeds 2 GiB (32-bit buffer offsets)");
-    const bool gen = (s->Cout % BK) != 0 || ((uintptr_t)dy & 15);
-    const bool bscalar = (s->Cin % 4) != 0 || ((uintptr_t)w & 15);
-    hipStream_t st = (hipStream_t)stream;
-    p.tune_kind = 1;
-    p.tune_tile = s->tune_tile; p.tune_ks = s->tune_ksplit; p.y_zeroed = s->out_zeroed;
-    p.f16 = transposed && s->prec == 1;   // fp16 operands: the k-contiguous (transposed-weights) form only - ops.py routes fp16 dgrads there
-    if (transposed) {
-        // WT[ci][a][b][co]: the weight rows are k-contiguous (k = (tap, co)), i.e. the forward kernel's operand layout
-        GIM_CHECK_ARG(!gen && !((uintptr_t)w & 15), "conv dgrad (transposed weights): Cout % 16 == 0 and 16-byte aligned operands required");
-        p.Cin_w = s->Cout;
-        p.tune_kind = 4;
-        launch_igemm<0, 0>(p, y_elems, st);
-        if (t_plan_out) return GIM_OK;
-    return gim_check_launch("gim_conv2d_dgrad_t");
-    }
-    if (gen) { if (bscalar) launch_igemm<1, 3>(p, y_elems, st); else launch_igemm<1, 1>(p, y_elems, st); }
-    else     { if (bscalar) launch_igemm<1, 2>(p, y_elems, st); else launch_igemm<1, 0>(p, y_elems, st); }
-    if (t_plan_out) return GIM_OK;
-    return gim_check_launch("gim_conv2d_dgrad");
+    ConvCall c;
+    rc = dgrad_call(c, dy, w, sigma, mask_x, dx, s, transposed, res_half, res_scale);
+    return rc ? rc : plan_and_run(c, stream, transposed ? "gim_conv2d_dgrad_t" : "gim_conv2d_dgrad");
 }
 
 extern "C" int gim_conv2d_dgrad(const float* dy, const float* w, const float* sigma, const float* mask_x, float* dx,
@@ -2209,6 +2165,19 @@ extern "C" int gim_conv2d_dgrad_t(const float* dy, const float* wt, const float*
     return dgrad_impl(dy, wt, sigma, mask_x, dx, s, stream, true);
 }
 
+// stride (1, J) gather over K x (K + J - 1) taps: logical grid (H, W / J)
+static Geo geo_xfold(const gim_conv_shape* s, int J) {
+    Geo g{};
+    const int pad = (s->KH - 1) / 2;
+    geo_grid(g, s->N, s->H, s->W / J);
+    g.Hin = s->H; g.Win = s->W; g.ups = 0;
+    g.s_in = 1; g.s_in_x = J; g.off_y = g.off_x = -pad;
+    g.Th = g.KF = s->KH; g.Tw = g.KFw = s->KH + J - 1;
+    g.wa_base = g.wb_base = 0; g.wa_step = g.wb_step = 1;
+    g.os = 1;
+    return g;
+}
+
 // dgrad of a plain convolution with <= 8 input channels on x-folded weights (gim_conv2d_xfold_weights): the forward kernel's
 // operand path over dy with stride (1, J), K x (K + J - 1) taps and J * Cin output columns.
 extern "C" int gim_conv2d_dgrad_xfold(const float* dy, const float* wx, const float* sigma, const float* mask_x, float* dx,
@@ -2219,39 +2188,23 @@ extern "C" int gim_conv2d_dgrad_xfold(const float* dy, const float* wx, const fl
     GIM_CHECK_ARG(!s->ups && !s->pool && !s->wfold, "conv dgrad (x-folded): plain convolutions only");
     GIM_CHECK_ARG(J >= 2 && (J & (J - 1)) == 0 && s->W % J == 0 && J * s->Cin <= 32, "conv dgrad (x-folded): J must be a power of two dividing W with J * Cin <= 32");
     GIM_CHECK_ARG(s->Cout % BK == 0 && !((uintptr_t)dy & 15) && !((uintptr_t)wx & 15), "conv dgrad (x-folded): Cout % 16 == 0 and 16-byte aligned operands required");
-    {
-        const size_t yi = (size_t)s->H * s->W * s->Cout, xi = (size_t)s->H * s->W * s->Cin;
-        if (s->N > 1 && (xi > yi ? xi : yi) * s->N * sizeof(float) > BUF_MAX_BYTES) {
-            gim_conv_shape a = *s, b = *s;
-            a.N = s->N / 2; b.N = s->N - a.N;
-            rc = gim_conv2d_dgrad_xfold(dy, wx, sigma, mask_x, dx, &a, J, stream);
-            if (rc) return rc;
-            return gim_conv2d_dgrad_xfold(dy + a.N * yi, wx, sigma, mask_x ? mask_x + a.N * xi : nullptr, dx + a.N * xi, &b, J, stream);
-        }
+    const size_t yi = (size_t)s->H * s->W * s->Cout, xi = (size_t)s->H * s->W * s->Cin;
+    gim_conv_shape a, b;
+    if (split_batch(*s, xi > yi ? xi : yi, a, b)) {
+        rc = gim_conv2d_dgrad_xfold(dy, wx, sigma, mask_x, dx, &a, J, stream);
+        if (rc) return rc;
+        return gim_conv2d_dgrad_xfold(dy + a.N * yi, wx, sigma, mask_x ? mask_x + a.N * xi : nullptr, dx + a.N * xi, &b, J, stream);
     }
-    ConvP p{};
-    p.zero = zero_page();
-    p.pos_inf = __builtin_inff();
-    const int pad = (s->KH - 1) / 2;
-    Geo g{};
-    geo_grid(g, s->N, s->H, s->W / J);
-    g.Hin = s->H; g.Win = s->W; g.ups = 0;
-    g.s_in = 1; g.s_in_x = J; g.off_y = g.off_x = -pad;
-    g.Th = g.KF = s->KH; g.Tw = g.KFw = s->KH + J - 1;
-    g.wa_base = g.wb_base = 0; g.wa_step = g.wb_step = 1;
-    g.os = 1;
-    p.g = g;
+    ConvCall c{};
+    ConvP& p = c.p;
+    // (tune_kind 5: no table rows - heuristics, or the caller's tune_* fields)
+    rc = convp_begin(p, geo_xfold(s, J), s->Cout, J * s->Cin, s->Cout, 5, s, "conv: one image of the gathered tensor exceeds 2 GiB (32-bit buffer offsets)");
+    if (rc) return rc;
     p.x = dy; p.w = wx; p.bias = nullptr; p.sigma = sigma; p.res = nullptr; p.mask_x = mask_x; p.y = dx;
-    p.Ca = s->Cout; p.Cb = J * s->Cin; p.Cin_w = s->Cout; p.pix = s->Cout;
-    p.M = g.N * g.H * g.W; p.Ktot = g.Th * g.Tw * s->Cout;
-    p.x_bytes = (unsigned)((unsigned long long)s->N * s->H * s->W * s->Cout * 4ull);
+    p.Cin_w = s->Cout;
     p.pre_slope = 1.f; p.mask_slope = s->pre_slope; p.out_scale = 1.f; p.res_ups = 0; p.post_slope = 1.f;
-    const size_t y_elems = (size_t)s->N * s->H * s->W * s->Cin;
-    p.tune_kind = 5;   // no table rows: heuristics (or the caller's tune_* fields)
-    p.tune_tile = s->tune_tile; p.tune_ks = s->tune_ksplit; p.y_zeroed = s->out_zeroed;
-    launch_igemm<0, 0>(p, y_elems, (hipStream_t)stream);
-    if (t_plan_out) return GIM_OK;
-    return gim_check_launch("gim_conv2d_dgrad_xfold");
+    c.y_elems = (size_t)s->N * s->H * s->W * s->Cin;
+    return plan_and_run(c, stream, "gim_conv2d_dgrad_xfold");
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -2355,108 +2308,27 @@ static Geo geo_rows(const gim_conv_shape* s) {
 }
 
 // y = conv(xp, w) / sigma + bias + residual on the padded, activated copy xp = gim_pad_image(x) and wp = gim_conv2d_pack_rows_weights(w)
+// (a batch beyond the buffer range is refused, not halved: the caller owns the padded copy)
 extern "C" int gim_conv2d_fwd_rows(const float* xp, const float* wp, const float* bias, const float* sigma, const float* residual,
                                    float* y, const gim_conv_shape* s, void* stream) {
     int rc = rows_shape_ok(s);
     if (rc) return rc;
     GIM_CHECK_ARG(xp && wp && y && !((uintptr_t)xp & 15) && !((uintptr_t)wp & 15), "conv fwd (rows form): null or unaligned pointer");
-    ConvP p{};
-    p.zero = zero_page();
-    p.pos_inf = __builtin_inff();
-    p.g = geo_rows(s);
+    ConvCall c{};
+    ConvP& p = c.p;
     const int CaP = (s->KH * s->Cin + 15) & ~15;
+    // (tune_kind 6: no table rows - heuristics, or the caller's tune_* fields)
+    rc = convp_begin(p, geo_rows(s), CaP, s->Cout, s->Cin, 6, s, "conv fwd (rows form): the padded image batch exceeds 2 GiB (32-bit buffer offsets): split the batch");
+    if (rc) return rc;
     p.x = xp; p.w = wp; p.bias = bias; p.sigma = sigma; p.res = residual; p.mask_x = nullptr; p.y = y;
-    p.Ca = CaP; p.Cb = s->Cout; p.Cin_w = CaP; p.pix = s->Cin;
-    p.M = p.g.N * p.g.H * p.g.W; p.Ktot = s->KH * CaP;
-    const unsigned long long xb = (unsigned long long)p.g.N * p.g.Hin * p.g.Win * s->Cin * 4ull;
-    GIM_CHECK_ARG(xb <= 0x7FFFFFF0ull, "conv fwd (rows form): the padded image batch exceeds 2 GiB (32-bit buffer offsets): split the batch");
-    p.x_bytes = (unsigned)xb;
+    p.Cin_w = CaP;
     p.pre_slope = 1.f; p.mask_slope = 1.f; p.out_scale = 1.f; p.res_ups = 0;
     GIM_CHECK_ARG(s->post_slope >= 0.f && s->post_slope <= 1.f, "conv fwd: post_slope must be in [0, 1] (0 or 1 = none)");
     p.post_slope = (s->post_slope > 0.f) ? s->post_slope : 1.f;
-    p.tune_kind = 6;   // no table rows: heuristics (or the caller's tune_* fields)
-    p.tune_tile = s->tune_tile; p.tune_ks = s->tune_ksplit; p.y_zeroed = s->out_zeroed;
-    p.f16 = 0;
-    const size_t y_elems = (size_t)s->N * s->H * s->W * s->Cout;
-    GIM_CHECK_ARG(y_elems * sizeof(float) <= 0x7FFFFFF0ull, "conv: the output exceeds 2 GiB (32-bit buffer offsets): split the batch");
-    t_launch_refused = false;
-    launch_igemm<0, 0>(p, y_elems, (hipStream_t)stream);
-    if (t_launch_refused) return GIM_E_BADARG;
-    if (t_plan_out) return GIM_OK;
-    return gim_check_launch("gim_conv2d_fwd_rows");
+    c.y_elems = (size_t)s->N * s->H * s->W * s->Cout;
+    GIM_CHECK_ARG(c.y_elems * sizeof(float) <= 0x7FFFFFF0ull, "conv: the output exceeds 2 GiB (32-bit buffer offsets): split the batch");
+    return plan_and_run(c, stream, "gim_conv2d_fwd_rows");
 }
-
-// wgrad roles.  plain: A = dy [N,H,W,Cout], B = gathered x.  pool: A = dy [N,H/2,W/2,Cout], B = x gathered with
-// stride 2 over the (K+1)^2 folded taps -> slabs in F layout [Cout][KF][KF][Cin].  sub-pixel (ups + wfold), roles
-// swapped: A = leaky_relu(x) [N,H/2,W/2,Cin], B = dy [N,H,W,Cout] gathered with stride 2 -> slabs
-// G[Cin][KF][KF][Cout] with G[ci][ta][tb][co] = dF[co][K-ta][K-tb][ci] (gim_wgrad_finish un-transposes).
-struct WgPlan { int bm, bn, ns, mper, rows, cols, M, table_hit, bk, patch, patch_target, f16; };
-
-static WgPlan wgrad_plan(const gim_conv_shape* s) {
-    WgPlan q{};
-    const bool up_fold = s->ups && s->wfold;
-    const int KF = s->wfold ? s->KH + 1 : s->KH;
-    q.rows = up_fold ? s->Cin : s->Cout;
-    q.cols = KF * KF * (up_fold ? s->Cout : s->Cin);
-    const long long M = (long long)s->N * (s->H >> (s->wfold ? 1 : 0)) * (s->W >> (s->wfold ? 1 : 0));
-    q.M = (int)M;
-    // launch choice: the caller's (gim_conv_shape.tune_tile / tune_wgrad), else the table row of this shape, else the heuristic
-    int target = s->tune_wgrad > 0 ? s->tune_wgrad : 0;
-    int tile = s->tune_tile > 0 ? s->tune_tile : 0;
-    if (!target && !tile && s->tune_tile == 0) {
-        const int pcw = (s->pool ? 1 : 0) + (up_fold ? 2 : 0);
-        const TuneEntry* te = tune_lookup(2, (int)M, q.rows, q.cols, s->KH, pcw);
-        if (te) { target = te->ks; tile = te->tile; q.table_hit = 1; }
-    }
-    if (tile >= 20000) { q.patch = 1; q.patch_target = target; tile -= 20000; }   // row-resident kernel (plain 3x3 layers)
-    // fp16 operands (conv_wgrad_f16_kernel): one tile shape, 32 pixels per K step; the table rows were measured on the fp32 kernels
-    const bool f16 = s->prec == 1 && q.rows % 4 == 0 && (up_fold ? s->Cout : s->Cin) % 4 == 0 && q.rows >= 32 && q.cols >= 64;
-    if (f16) { q.patch = 0; tile = 128; if (!(s->tune_wgrad > 0)) target = 0; q.f16 = 1; q.table_hit = 0; }
-    q.bm = q.rows > 64 ? 128 : (q.rows > 32 ? 64 : 32);
-    q.bn = (q.bm == 32) ? 128 : (q.cols > 64 ? 128 : 64);
-    if (tile == 128) { q.bm = 128; q.bn = 128; }
-    else if (tile == 641) { q.bm = 64; q.bn = 128; }
-    else if (tile == 1264) { q.bm = 128; q.bn = 64; }
-    else if (tile == 64 || tile == 6432) { q.bm = 64; q.bn = 64; }
-    else if (tile == 32128) { q.bm = 32; q.bn = 128; }
-    // 32-pixel K steps: fp32 path, both operands on 16-byte loads (the launcher falls back to 16 otherwise)
-    q.bk = ((f16 || tile == 6432) && q.rows % 4 == 0 && (up_fold ? s->Cout : s->Cin) % 4 == 0) ? 32 : BK;
-    const long long tiles = (long long)((q.cols + q.bn - 1) / q.bn) * ((q.rows + q.bm - 1) / q.bm);
-    // Heuristic: about four workgroups per CU in total and at least 32 K-steps (512 pixels) per workgroup, so that the float
-    // atomics of the combine stay small next to the MFMA work - unless that leaves most CUs idle (1x1 convs and linears on small
-    // maps: few tiles, few pixels): a launch with one workgroup per CU runs one wave per SIMD and pays the full load latency every
-    // K step (~1.8 us), so short slices on many CUs win although they add more partial tiles (measured: tools/conv_autotune.py).
-    // An explicit / table target lifts the 512-pixel floor to 64 (4 K-steps).
-    long long minpix = 512;
-    // (fp16 kernel: the same slicing - half as many, longer slices were measured 13 % slower over the config-5 step, 43.5 vs 49.8
-    //  episodes/s: the kernel is bound by operand traffic and wants the waves in flight, not fewer epilogues)
-    if (!target) {
-        target = 1024;
-        if (tiles * ((M + 511) / 512) < 256) minpix = 128;
-    } else {
-        minpix = 64;
-    }
-    long long S = (target + tiles - 1) / tiles;
-    const long long maxS = (M + minpix - 1) / minpix;
-    if (S > maxS) S = maxS;
-    if (S > 1024) S = 1024;
-    if (S < 1) S = 1;
-    long long mp = (M + S - 1) / S;
-    mp = (mp + q.bk - 1) / q.bk * q.bk;
-    q.mper = (int)mp;
-    q.ns = (int)((M + mp - 1) / mp);
-    return q;
-}
-
-// The pixel slices of one weight gradient are combined either with float atomics in the kernel epilogue (n_slabs = 1: the
-// caller sees ONE slab, no separate reduce pass - at 16 episodes per GPU that pass cost 7 % of the step; the sum order then
-// varies from run to run in the last bits) or, deterministically, as gim_conv2d_wgrad_slabs(shape) separate slabs that
-// gim_wgrad_finish adds up in a fixed order.  The caller chooses per call through n_slabs.
-extern "C" int gim_conv2d_wgrad_slabs(const gim_conv_shape* s) {
-    if (check_shape(s)) return GIM_E_BADARG;
-    return wgrad_plan(s).ns;
-}
-
 template <int VA, int VB, bool FASTB>
 static void launch_wgrad(const WgP& p, int bm, int bn, int bk, dim3 g, hipStream_t st) {
     if constexpr (VA == 4 && VB == 4) {
@@ -2558,36 +2430,159 @@ __global__ __launch_bounds__(64 * NARROW_PARTS) void wgrad_1x1_narrow_kernel(con
     }
 }
 
+// wgrad roles.  plain: A = dy [N,H,W,Cout], B = gathered x.  pool: A = dy [N,H/2,W/2,Cout], B = x gathered with
+// stride 2 over the (K+1)^2 folded taps -> slabs in F layout [Cout][KF][KF][Cin].  sub-pixel (ups + wfold), roles
+// swapped: A = leaky_relu(x) [N,H/2,W/2,Cin], B = dy [N,H,W,Cout] gathered with stride 2 -> slabs
+// G[Cin][KF][KF][Cout] with G[ci][ta][tb][co] = dF[co][K-ta][K-tb][ci] (gim_wgrad_finish un-transposes).
+//
+// The pixel slices of one weight gradient are combined either with float atomics in the kernel epilogue (n_slabs = 1: the
+// caller sees ONE slab, no separate reduce pass - at 16 episodes per GPU that pass cost 7 % of the step; the sum order then
+// varies from run to run in the last bits) or, deterministically, as gim_conv2d_wgrad_slabs(shape) separate slabs that
+// gim_wgrad_finish adds up in a fixed order.  The caller chooses per call through n_slabs.
+enum WgFamily { WG_MFMA = 0, WG_MFMA_F16, WG_TINY, WG_ROW, WG_NARROW };   // conv_wgrad(_f16)_kernel, conv_tiny.hip, conv_wgrad_row_kernel, wgrad_1x1_narrow_kernel
+enum WgCombine { WG_SLABS = 0, WG_ONE_SLAB, WG_ACC };   // gim_conv2d_wgrad_slabs(shape) slabs; n_slabs = 1; the caller's pre-zeroed accumulator
+struct WgPlan {
+    int family;
+    int rows, cols, M;     // the gradient matrix [rows][cols]; pixels summed over
+    int ns;                // pixel slices of the MFMA slicing, whatever the family (gim_conv2d_wgrad_slabs)
+    int atomic;            // slices combine by float atomics into one zeroed slab
+    int bm, bn, bk, xcd;   // MFMA families: tile, pixels per K step (both operands on 16-byte loads: see wgrad_impl), XCD-balanced slices
+    int slices, mper;      // pixel slices of the family that runs, pixels per slice
+    int gx, gy, gz;
+    int table_hit;
+};
+
+// The whole decision for one weight gradient.  rows_form: gim_conv2d_wgrad_rows_acc; aligned: dy and x on 16-byte boundaries (the
+// row-resident kernel needs it; gim_conv_launch_plan reports the aligned case).
+static WgPlan wgrad_plan(const gim_conv_shape* s0, bool rows_form, int combine, bool aligned) {
+    WgPlan q{};
+    gim_conv_shape v = *s0;
+    if (rows_form) {   // row-contiguous form: table rows do not apply (other column count), fp32 only
+        v.tune_tile = s0->tune_tile ? s0->tune_tile : -1;
+        v.prec = 0;
+    }
+    const gim_conv_shape* s = &v;
+    const bool up_fold = s->ups && s->wfold;
+    const int KF = s->wfold ? s->KH + 1 : s->KH;
+    q.rows = up_fold ? s->Cin : s->Cout;
+    q.cols = KF * KF * (up_fold ? s->Cout : s->Cin);
+    const long long M = (long long)s->N * (s->H >> (s->wfold ? 1 : 0)) * (s->W >> (s->wfold ? 1 : 0));
+    q.M = (int)M;
+    // launch choice: the caller's (gim_conv_shape.tune_tile / tune_wgrad), else the table row of this shape, else the heuristic
+    int target = s->tune_wgrad > 0 ? s->tune_wgrad : 0;
+    int tile = s->tune_tile > 0 ? s->tune_tile : 0;
+    if (!target && !tile && s->tune_tile == 0) {
+        const int pcw = (s->pool ? 1 : 0) + (up_fold ? 2 : 0);
+        const TuneEntry* te = tune_lookup(2, (int)M, q.rows, q.cols, s->KH, pcw);
+        if (te) { target = te->ks; tile = te->tile; q.table_hit = 1; }
+    }
+    bool row_resident = false;     // tile code + 20000: the row-resident kernel (plain 3x3 layers); target = workgroups wanted
+    int row_target = 0;
+    if (tile >= 20000) { row_resident = true; row_target = target; tile -= 20000; }
+    // fp16 operands (conv_wgrad_f16_kernel): one tile shape, 32 pixels per K step; the table rows were measured on the fp32 kernels
+    const bool f16 = s->prec == 1 && q.rows % 4 == 0 && (up_fold ? s->Cout : s->Cin) % 4 == 0 && q.rows >= 32 && q.cols >= 64;
+    if (f16) { row_resident = false; tile = 128; if (!(s->tune_wgrad > 0)) target = 0; q.table_hit = 0; }
+    q.bm = q.rows > 64 ? 128 : (q.rows > 32 ? 64 : 32);
+    q.bn = (q.bm == 32) ? 128 : (q.cols > 64 ? 128 : 64);
+    if (tile == 128) { q.bm = 128; q.bn = 128; }
+    else if (tile == 641) { q.bm = 64; q.bn = 128; }
+    else if (tile == 1264) { q.bm = 128; q.bn = 64; }
+    else if (tile == 64 || tile == 6432) { q.bm = 64; q.bn = 64; }
+    else if (tile == 32128) { q.bm = 32; q.bn = 128; }
+    // 32-pixel K steps: fp32 path, both operands on 16-byte loads (the launcher falls back to 16 otherwise)
+    q.bk = ((f16 || tile == 6432) && q.rows % 4 == 0 && (up_fold ? s->Cout : s->Cin) % 4 == 0) ? 32 : BK;
+    const long long tiles = (long long)((q.cols + q.bn - 1) / q.bn) * ((q.rows + q.bm - 1) / q.bm);
+    // Heuristic: about four workgroups per CU in total and at least 32 K-steps (512 pixels) per workgroup, so that the float
+    // atomics of the combine stay small next to the MFMA work - unless that leaves most CUs idle (1x1 convs and linears on small
+    // maps: few tiles, few pixels): a launch with one workgroup per CU runs one wave per SIMD and pays the full load latency every
+    // K step (~1.8 us), so short slices on many CUs win although they add more partial tiles (measured: tools/conv_autotune.py).
+    // An explicit / table target lifts the 512-pixel floor to 64 (4 K-steps).
+    long long minpix = 512;
+    // (fp16 kernel: the same slicing - half as many, longer slices were measured 13 % slower over the config-5 step, 43.5 vs 49.8
+    //  episodes/s: the kernel is bound by operand traffic and wants the waves in flight, not fewer epilogues)
+    if (!target) {
+        target = 1024;
+        if (tiles * ((M + 511) / 512) < 256) minpix = 128;
+    } else {
+        minpix = 64;
+    }
+    long long S = (target + tiles - 1) / tiles;
+    const long long maxS = (M + minpix - 1) / minpix;
+    if (S > maxS) S = maxS;
+    if (S > 1024) S = 1024;
+    if (S < 1) S = 1;
+    long long mp = (M + S - 1) / S;
+    mp = (mp + q.bk - 1) / q.bk * q.bk;
+    q.ns = (int)((M + mp - 1) / mp);
+    if (rows_form) {   // K tap rows of CaP columns each (the slicing above is the plain form's)
+        q.cols = s->KH * ((s->KH * s->Cin + 15) & ~15);
+        q.bn = (q.bm == 32 || q.cols > 64) ? 128 : 64;
+    }
+    q.atomic = combine == WG_ACC || (combine == WG_ONE_SLAB && q.ns > 1);
+    const bool plain = !rows_form && !s->wfold && !s->ups && !s->pool;
+    const bool untuned = s->tune_tile == 0 && s->tune_wgrad == 0;   // an explicit tile / slice choice of the caller means the MFMA kernel
+    if (!rows_form && combine != WG_SLABS && untuned && gim_tiny_shape(s)) {
+        // 3 -> 3 / 1 -> 1 image layers, slices combined by atomics: the direct kernel (conv_tiny.hip)
+        const dim3 g = gim_tiny_grid(s);
+        q.family = WG_TINY;
+        q.table_hit = q.bm = q.bn = 0;
+        q.gx = g.x; q.gy = g.y; q.gz = 1;
+        q.slices = q.gx * q.gy;
+    } else if (plain && row_resident && q.atomic && s->KH == 3 && s->Cin % 32 == 0 && s->Cout % 128 == 0 && s->H * s->W >= 16 && s->W >= 4 && aligned) {
+        // plain 3x3, row-resident kernel: on request only
+        // (W >= 4: the narrowest instantiation walks rows of 4 pixels - a non-square 8 x 2 map passes H * W >= 16 and must not run it)
+        q.family = WG_ROW;
+        q.bm = 128; q.bn = 96;
+        q.gx = 3 * (s->Cin / 32); q.gy = s->Cout / 128;
+        const int wgs = q.gx * q.gy;
+        long long Sr = ((row_target > 0 ? row_target : 1024) + wgs - 1) / wgs;
+        const long long maxSr = (M + 127) / 128;          // at least 8 steps per slice
+        if (Sr > maxSr) Sr = maxSr;
+        if (Sr < 1) Sr = 1;
+        mp = (M + Sr - 1) / Sr;
+        mp = (mp + 15) / 16 * 16;
+        q.slices = q.gz = (int)((M + mp - 1) / mp);
+    } else if (plain && s->KH == 1 && q.atomic && (s->Cin <= 8 || s->Cout <= 8) && (s->Cin >= 16 || s->Cout >= 16) && M % NARROW_U == 0 && untuned) {
+        // 1x1 convolution with <= 8 channels on one side, atomic combine: the outer-product kernel (no table row: nothing to choose)
+        q.family = WG_NARROW;
+        q.table_hit = q.bm = q.bn = 0;
+        mp = NARROW_MPER;
+        q.slices = q.gx = (int)((M + NARROW_MPER - 1) / NARROW_MPER);
+        q.gy = ((s->Cin <= 8 ? s->Cout : s->Cin) + 63) / 64;
+        q.gz = 1;
+    } else {
+        q.family = f16 ? WG_MFMA_F16 : WG_MFMA;
+        q.slices = q.ns;
+        q.xcd = (q.ns >= 64 || (q.ns >= 8 && q.ns % 8 == 0)) ? 1 : 0;   // every XCD gets (nearly) the same number of slices
+        q.gx = (q.cols + q.bn - 1) / q.bn; q.gy = (q.rows + q.bm - 1) / q.bm;
+        q.gz = q.xcd ? (q.ns + 7) / 8 * 8 : q.ns;                       // z padded: wgrad_block
+    }
+    q.mper = (int)mp;
+    return q;
+}
+
+extern "C" int gim_conv2d_wgrad_slabs(const gim_conv_shape* s) {
+    if (check_shape(s)) return GIM_E_BADARG;
+    return wgrad_plan(s, false, WG_SLABS, true).ns;
+}
+
+// Validate, plan and fill the kernel parameters of one weight gradient (the first half of wgrad_impl, and of the plan query).
 // prezeroed: the caller guarantees slabs / bias_slabs hold zeros (or a partial sum to add to): pixel slices are combined
-// with float atomics and nothing is cleared here (gim_conv2d_wgrad_acc).
-static int wgrad_impl(const float* dy, const float* x, float* slabs, float* bias_slabs, int n_slabs, const gim_conv_shape* s,
-                      void* stream, bool prezeroed, bool rows = false) {
+// with float atomics and nothing is cleared (gim_conv2d_wgrad_acc).
+static int wgrad_call(WgP& p, WgPlan& q, const float* dy, const float* x, float* slabs, float* bias_slabs, int n_slabs, const gim_conv_shape* s,
+                      bool prezeroed, bool rows) {
     int rc = check_shape(s);
     if (rc) return rc;
     GIM_CHECK_ARG(dy && x && slabs, "conv wgrad: null pointer");
-    WgPlan q = wgrad_plan(s);
-    const int CaP = (s->KH * s->Cin + 15) & ~15;
-    if (rows) {   // row-contiguous form: K tap rows of CaP columns each; table rows do not apply (other column count)
-        gim_conv_shape v = *s;
-        v.tune_tile = s->tune_tile ? s->tune_tile : -1;
-        v.prec = 0;
-        q = wgrad_plan(&v);
-        WgPlan q2 = q;
-        q2.cols = s->KH * CaP;
-        q2.bn = q2.cols > 64 ? 128 : 64;
-        if (q2.bm == 32) q2.bn = 128;
-        q = q2;
-    }
-    const bool atomic = prezeroed ? true : (n_slabs == 1 && q.ns > 1);
+    q = wgrad_plan(s, rows, prezeroed ? WG_ACC : (n_slabs == 1 ? WG_ONE_SLAB : WG_SLABS), !((uintptr_t)dy & 15) && !((uintptr_t)x & 15));
     if (!prezeroed) GIM_CHECK_ARG(n_slabs == 1 || n_slabs == q.ns, "conv wgrad: n_slabs must be 1 (atomic combine) or gim_conv2d_wgrad_slabs(shape)");
     const bool up_fold = s->ups && s->wfold;
     GIM_CHECK_ARG(!(up_fold && bias_slabs), "conv wgrad: the sub-pixel form does not produce the bias gradient (use gim_colsum)");
-    WgP p{};
+    p = WgP{};
     p.zero = zero_page();
     p.pos_inf = __builtin_inff();
     if (rows) p.g = geo_rows(s);
-    else if (s->pool) p.g = geo_s2(s, false);
-    else if (up_fold) p.g = geo_s2(s, false);
+    else if (s->pool || up_fold) p.g = geo_s2(s, false);
     else p.g = geo_plain(s, false);
     if (up_fold) {
         p.dy = x; p.x = dy; p.Cin = s->Cout; p.Cout = s->Cin; p.pre_slope = 1.f; p.a_slope = s->pre_slope; p.pix = s->Cout;
@@ -2595,93 +2590,61 @@ static int wgrad_impl(const float* dy, const float* x, float* slabs, float* bias
         p.dy = dy; p.x = x; p.Cin = s->Cin; p.Cout = s->Cout; p.pre_slope = s->pre_slope; p.a_slope = 1.f; p.pix = s->Cin;
     }
     p.slabs = slabs; p.bias_slabs = bias_slabs;
-    p.M = q.M; p.Kcols = q.cols; p.mper = q.mper; p.atomic = atomic ? 1 : 0;
-    if (rows) { p.Cin = CaP; p.pix = s->Cin; p.pre_slope = 1.f; }   // columns per tap row; the padded copy is already activated
-    {
-        const unsigned long long xb = (unsigned long long)p.g.N * p.g.Hin * p.g.Win * p.pix * 4ull;
-        GIM_CHECK_ARG(xb <= 0x7FFFFFF0ull, "conv wgrad: gathered tensor larger than 2 GiB (32-bit buffer offsets): split the batch");
-        p.x_bytes = (unsigned)xb;
-    }
-    if (atomic && !prezeroed && !t_plan_out) {
-        (void)hipMemsetAsync(slabs, 0, (size_t)q.rows * q.cols * sizeof(float), (hipStream_t)stream);
-        if (bias_slabs) (void)hipMemsetAsync(bias_slabs, 0, (size_t)q.rows * sizeof(float), (hipStream_t)stream);
-    }
-    // 3 -> 3 / 1 -> 1 image layers, slices combined by atomics: the direct kernel (conv_tiny.hip)
-    if (!rows && (prezeroed || n_slabs == 1) && s->tune_tile == 0 && s->tune_wgrad == 0 && gim_tiny_shape(s)) {
-        if (!prezeroed && !atomic && !t_plan_out) {   // (atomic: the memsets above have run)
-            (void)hipMemsetAsync(slabs, 0, (size_t)q.rows * q.cols * sizeof(float), (hipStream_t)stream);
-            if (bias_slabs) (void)hipMemsetAsync(bias_slabs, 0, (size_t)q.rows * sizeof(float), (hipStream_t)stream);
-        }
-        (void)gim_tiny_wgrad_acc(dy, x, slabs, bias_slabs, s, (hipStream_t)stream, t_plan_out);
-        return t_plan_out ? GIM_OK : gim_check_launch("gim_conv2d_wgrad");
-    }
-    // plain 3x3, row-resident kernel: on request (tile code >= 20000 from the caller or the table row; ks / target = workgroups wanted)
-    // (W >= 4: the narrowest instantiation walks rows of 4 pixels - a non-square 8 x 2 map passes H * W >= 16 and must not run it)
-    if (!rows && q.patch && atomic && s->KH == 3 && !s->wfold && !s->ups && !s->pool && s->Cin % 32 == 0 && s->Cout % 128 == 0 && s->H * s->W >= 16 &&
-        s->W >= 4 && !((uintptr_t)dy & 15) && !((uintptr_t)x & 15)) {
-        const int tiles = 3 * (s->Cin / 32) * (s->Cout / 128);
-        long long S = ((q.patch_target > 0 ? q.patch_target : 1024) + tiles - 1) / tiles;
-        const long long maxS = (q.M + 127) / 128;          // at least 8 steps per slice
-        if (S > maxS) S = maxS;
-        if (S < 1) S = 1;
-        long long mp = (q.M + S - 1) / S;
-        mp = (mp + 15) / 16 * 16;
-        const int nsp = (int)((q.M + mp - 1) / mp);
-        if (t_plan_out) {
-            const int32_t v[8] = {q.table_hit, 128, 96, nsp, 3 * (s->Cin / 32), s->Cout / 128, nsp, 1};
-            for (int i = 0; i < 8; ++i) t_plan_out[i] = v[i];
-            return GIM_OK;
-        }
-        p.mper = (int)mp; p.ns = nsp;
-        const dim3 gp(3 * (s->Cin / 32), s->Cout / 128, nsp);
-        const int Wt = s->W < 16 ? s->W : 16;
-        if (Wt == 16) hipLaunchKernelGGL(conv_wgrad_row_kernel<16>, gp, dim3(256), 0, (hipStream_t)stream, p);
-        else if (Wt == 8) hipLaunchKernelGGL(conv_wgrad_row_kernel<8>, gp, dim3(256), 0, (hipStream_t)stream, p);
-        else hipLaunchKernelGGL(conv_wgrad_row_kernel<4>, gp, dim3(256), 0, (hipStream_t)stream, p);
-        return gim_check_launch("gim_conv2d_wgrad");
-    }
-    // 1x1 convolution with <= 8 channels on one side, atomic combine: the outer-product kernel (no table row: nothing to choose)
-    if (!rows && s->KH == 1 && !s->wfold && !s->ups && !s->pool && atomic && (s->Cin <= 8 || s->Cout <= 8) && (s->Cin >= 16 || s->Cout >= 16) && q.M % NARROW_U == 0 &&
-        s->tune_tile == 0 && s->tune_wgrad == 0) {   // an explicit tile / slice choice of the caller means the MFMA kernel
-        const bool wide_is_dy = s->Cin <= 8;
-        const int Cw = wide_is_dy ? s->Cout : s->Cin, Cn = wide_is_dy ? s->Cin : s->Cout;
-        const int nsl = (q.M + NARROW_MPER - 1) / NARROW_MPER;
-        if (t_plan_out) {
-            const int32_t v[8] = {0, 0, 0, nsl, nsl, (Cw + 63) / 64, 1, 0};
-            for (int i = 0; i < 8; ++i) t_plan_out[i] = v[i];
-            return GIM_OK;
-        }
-        const dim3 g(nsl, (Cw + 63) / 64), b(64 * NARROW_PARTS);
-        const float *wd = wide_is_dy ? dy : x, *nr = wide_is_dy ? x : dy;
-        if (Cn == 3) hipLaunchKernelGGL((wgrad_1x1_narrow_kernel<3, true>), g, b, 0, (hipStream_t)stream, wd, nr, slabs, bias_slabs, q.M, Cw, Cn, s->pre_slope, wide_is_dy ? 1 : 0);
-        else if (Cn == 6) hipLaunchKernelGGL((wgrad_1x1_narrow_kernel<6, true>), g, b, 0, (hipStream_t)stream, wd, nr, slabs, bias_slabs, q.M, Cw, Cn, s->pre_slope, wide_is_dy ? 1 : 0);
-        else hipLaunchKernelGGL((wgrad_1x1_narrow_kernel<8, false>), g, b, 0, (hipStream_t)stream, wd, nr, slabs, bias_slabs, q.M, Cw, Cn, s->pre_slope, wide_is_dy ? 1 : 0);
-        return gim_check_launch("gim_conv2d_wgrad");
-    }
-    p.ns = q.ns;
-    p.xcd = (q.ns >= 64 || (q.ns >= 8 && q.ns % 8 == 0)) ? 1 : 0;   // every XCD gets (nearly) the same number of slices
-    dim3 g((q.cols + q.bn - 1) / q.bn, (q.rows + q.bm - 1) / q.bm, p.xcd ? (q.ns + 7) / 8 * 8 : q.ns);   // z padded: wgrad_block
-    if (t_plan_out) {
-        const int32_t v[8] = {q.table_hit, q.bm, q.bn, q.ns, (int32_t)g.x, (int32_t)g.y, (int32_t)g.z, q.f16 ? 2 : 0};
-        for (int i = 0; i < 8; ++i) t_plan_out[i] = v[i];
-        return GIM_OK;
-    }
-    // per operand as the kernel sees it (the sub-pixel form swaps the roles): A = p.dy with p.Cout channels, B = p.x with p.Cin
-    const bool va = (p.Cout % 4 == 0) && !((uintptr_t)p.dy & 15);
-    const bool vb = (p.Cin % 4 == 0) && !((uintptr_t)p.x & 15);
-    const int bk = (q.bk == 32 && va && vb) ? 32 : BK;
-    const bool fastb = vb && p.g.ups == 0 && ((p.g.H * p.g.W) & (bk - 1)) == 0;   // a K step stays inside one image
+    p.M = q.M; p.Kcols = q.cols; p.mper = q.mper; p.ns = q.slices; p.xcd = q.xcd; p.atomic = q.atomic;
+    if (rows) { p.Cin = (s->KH * s->Cin + 15) & ~15; p.pix = s->Cin; p.pre_slope = 1.f; }   // columns per tap row; the padded copy is already activated
+    const unsigned long long xb = (unsigned long long)p.g.N * p.g.Hin * p.g.Win * p.pix * 4ull;
+    GIM_CHECK_ARG(xb <= 0x7FFFFFF0ull, "conv wgrad: gathered tensor larger than 2 GiB (32-bit buffer offsets): split the batch");
+    p.x_bytes = (unsigned)xb;
+    return GIM_OK;
+}
+
+static int wgrad_impl(const float* dy, const float* x, float* slabs, float* bias_slabs, int n_slabs, const gim_conv_shape* s,
+                      void* stream, bool prezeroed, bool rows = false) {
+    WgP p;
+    WgPlan q;
+    const int rc = wgrad_call(p, q, dy, x, slabs, bias_slabs, n_slabs, s, prezeroed, rows);
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (q.f16 && va && vb && bk == 32) {
-        if (fastb) hipLaunchKernelGGL(conv_wgrad_f16_kernel<true>, g, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(conv_wgrad_f16_kernel<false>, g, dim3(256), 0, st, p);
-        return gim_check_launch("gim_conv2d_wgrad");
+    if (!prezeroed && (q.atomic || q.family == WG_TINY)) {   // (the direct kernel always adds into its slot)
+        (void)hipMemsetAsync(slabs, 0, (size_t)q.rows * q.cols * sizeof(float), st);
+        if (bias_slabs) (void)hipMemsetAsync(bias_slabs, 0, (size_t)q.rows * sizeof(float), st);
     }
-    if (va && fastb) launch_wgrad<4, 4, true>(p, q.bm, q.bn, bk, g, st);
-    else if (va && vb) launch_wgrad<4, 4, false>(p, q.bm, q.bn, bk, g, st);
-    else if (va) launch_wgrad<4, 1, false>(p, q.bm, q.bn, bk, g, st);
-    else if (vb) launch_wgrad<1, 4, false>(p, q.bm, q.bn, bk, g, st);
-    else launch_wgrad<1, 1, false>(p, q.bm, q.bn, bk, g, st);
+    const dim3 g(q.gx, q.gy, q.gz);
+    switch (q.family) {
+    case WG_TINY:
+        gim_tiny_wgrad_acc(dy, x, slabs, bias_slabs, s, st);
+        break;
+    case WG_ROW:   // rows of min(W, 16) pixels
+        if (s->W >= 16) hipLaunchKernelGGL(conv_wgrad_row_kernel<16>, g, dim3(256), 0, st, p);
+        else if (s->W == 8) hipLaunchKernelGGL(conv_wgrad_row_kernel<8>, g, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL(conv_wgrad_row_kernel<4>, g, dim3(256), 0, st, p);
+        break;
+    case WG_NARROW: {
+        const int wide_is_dy = s->Cin <= 8 ? 1 : 0;
+        const int Cw = wide_is_dy ? s->Cout : s->Cin, Cn = wide_is_dy ? s->Cin : s->Cout;
+        const dim3 b(64 * NARROW_PARTS);
+        const float *wd = wide_is_dy ? dy : x, *nr = wide_is_dy ? x : dy;
+        if (Cn == 3) hipLaunchKernelGGL((wgrad_1x1_narrow_kernel<3, true>), g, b, 0, st, wd, nr, slabs, bias_slabs, q.M, Cw, Cn, s->pre_slope, wide_is_dy);
+        else if (Cn == 6) hipLaunchKernelGGL((wgrad_1x1_narrow_kernel<6, true>), g, b, 0, st, wd, nr, slabs, bias_slabs, q.M, Cw, Cn, s->pre_slope, wide_is_dy);
+        else hipLaunchKernelGGL((wgrad_1x1_narrow_kernel<8, false>), g, b, 0, st, wd, nr, slabs, bias_slabs, q.M, Cw, Cn, s->pre_slope, wide_is_dy);
+        break;
+    }
+    default: {
+        // What depends on the real pointers stays here (the plan assumes aligned operands): vector width per operand as the kernel
+        // sees it (the sub-pixel form swaps the roles: A = p.dy with p.Cout channels, B = p.x with p.Cin), K step, fast B path.
+        const bool va = (p.Cout % 4 == 0) && !((uintptr_t)p.dy & 15);
+        const bool vb = (p.Cin % 4 == 0) && !((uintptr_t)p.x & 15);
+        const int bk = (q.bk == 32 && va && vb) ? 32 : BK;
+        const bool fastb = vb && p.g.ups == 0 && ((p.g.H * p.g.W) & (bk - 1)) == 0;   // a K step stays inside one image
+        if (q.family == WG_MFMA_F16 && va && vb && bk == 32 && fastb) hipLaunchKernelGGL(conv_wgrad_f16_kernel<true>, g, dim3(256), 0, st, p);
+        else if (q.family == WG_MFMA_F16 && va && vb && bk == 32) hipLaunchKernelGGL(conv_wgrad_f16_kernel<false>, g, dim3(256), 0, st, p);
+        else if (va && fastb) launch_wgrad<4, 4, true>(p, q.bm, q.bn, bk, g, st);
+        else if (va && vb) launch_wgrad<4, 4, false>(p, q.bm, q.bn, bk, g, st);
+        else if (va) launch_wgrad<4, 1, false>(p, q.bm, q.bn, bk, g, st);
+        else if (vb) launch_wgrad<1, 4, false>(p, q.bm, q.bn, bk, g, st);
+        else launch_wgrad<1, 1, false>(p, q.bm, q.bn, bk, g, st);
+    }
+    }
     return gim_check_launch("gim_conv2d_wgrad");
 }
 
@@ -2691,16 +2654,15 @@ extern "C" int gim_conv2d_wgrad(const float* dy, const float* x, float* slabs, f
 }
 
 extern "C" int gim_conv2d_wgrad_acc(const float* dy, const float* x, float* acc, float* bias_acc, const gim_conv_shape* s, void* stream) {
-    if (check_shape(s) == 0) {   // operands beyond the 32-bit buffer-offset range: halve the batch, both halves ADD into acc
-        const size_t yi = (size_t)(s->H >> s->pool) * (s->W >> s->pool) * s->Cout;
-        const size_t xi = (size_t)(s->H >> s->ups) * (s->W >> s->ups) * s->Cin;
-        if (s->N > 1 && (xi > yi ? xi : yi) * s->N * sizeof(float) > BUF_MAX_BYTES) {
-            gim_conv_shape a = *s, b = *s;
-            a.N = s->N / 2; b.N = s->N - a.N;
-            const int rc = gim_conv2d_wgrad_acc(dy, x, acc, bias_acc, &a, stream);
-            if (rc) return rc;
-            return gim_conv2d_wgrad_acc(dy + a.N * yi, x + a.N * xi, acc, bias_acc, &b, stream);
-        }
+    int rc = check_shape(s);
+    if (rc) return rc;
+    size_t xi, yi;
+    image_elems(s, false, xi, yi);
+    gim_conv_shape a, b;
+    if (split_batch(*s, xi > yi ? xi : yi, a, b)) {   // both halves ADD into acc
+        rc = gim_conv2d_wgrad_acc(dy, x, acc, bias_acc, &a, stream);
+        if (rc) return rc;
+        return gim_conv2d_wgrad_acc(dy + a.N * yi, x + a.N * xi, acc, bias_acc, &b, stream);
     }
     return wgrad_impl(dy, x, acc, bias_acc, 1, s, stream, true);
 }
@@ -2715,21 +2677,56 @@ extern "C" int gim_conv2d_wgrad_rows_acc(const float* dy, const float* xp, float
     return wgrad_impl(dy, xp, acc, bias_acc, 1, s, stream, true, true);
 }
 
-// The launch a conv entry point would make for `shape`, without launching anything (tests, tools/conv_autotune.py).
+// The launch a conv entry point would make for `shape`, without launching anything (tests, tools/conv_autotune.py): the entry
+// point's own validation and fill (on aligned stand-in pointers that nothing dereferences), then its planner.
 //   kind 0 = gim_conv2d_fwd, 1 = gim_conv2d_dgrad, 2 = gim_conv2d_dgrad_t, 3 = gim_conv2d_wgrad_acc
 //   out[8] = {1 if a row of the compiled-in launch table matched this shape, tile rows BM, tile columns BN,
 //             split-K factor (wgrad: pixel slices), grid x, grid y, grid z, loop form (0 tap-major, 1 patch-resident, 2 fp16 operands,
 //             3 direct image-layer kernel) | skipped share of the K steps in 1/1000 << 8 (position-major rows, Geo.pm)}
+// A batch beyond the buffer range reports the plan of its last half.
+static void plan_row(int32_t* out, int table_hit, int bm, int bn, int slices, int gx, int gy, int gz, int form) {
+    const int32_t v[8] = {table_hit, bm, bn, slices, gx, gy, gz, form};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+}
+
+static int launch_plan(const gim_conv_shape* s, int kind, int32_t* out) {
+    float* const fake = reinterpret_cast<float*>(uintptr_t(4096));
+    int rc = check_shape(s);
+    if (rc) return rc;
+    if (kind < 2 && tiny_route(s)) {
+        const dim3 g = gim_tiny_grid(s);
+        plan_row(out, 0, GIM_TINY_TILE * GIM_TINY_TILE, kind == 0 ? s->Cout : s->Cin, 1, g.x, g.y, 1, 3);
+        return GIM_OK;
+    }
+    size_t xi, yi;
+    image_elems(s, kind == 1 || kind == 2, xi, yi);
+    gim_conv_shape a, b;
+    if (split_batch(*s, xi > yi ? xi : yi, a, b)) {
+        rc = launch_plan(&a, kind, out);
+        return rc ? rc : launch_plan(&b, kind, out);
+    }
+    if (kind == 3) {
+        const int form[] = {0, 2, 3, 1, 0};   // by WgFamily
+        WgP p;
+        WgPlan q;
+        rc = wgrad_call(p, q, fake, fake, fake, nullptr, 1, s, true, false);
+        if (!rc) plan_row(out, q.table_hit, q.bm, q.bn, q.slices, q.gx, q.gy, q.gz, form[q.family]);
+        return rc;
+    }
+    const int form[] = {0, 1, 2, 2};          // by IgemmFamily
+    ConvCall c;
+    rc = kind == 0 ? fwd_call(c, fake, fake, nullptr, nullptr, nullptr, fake, s)
+                   : dgrad_call(c, fake, fake, nullptr, nullptr, fake, s, kind == 2, nullptr, 0.f);
+    if (rc) return rc;
+    const IgemmPlan q = plan_igemm(c.p, c.bmode, c.gen);
+    // bits 8.. of out[7]: the share of the launch's K steps that is SKIPPED, in 1/1000 (position-major rows skip padding taps; else 0)
+    const int skipped = 1000 - pm_valid_permille(c.p.g, c.p.M, q.BM);
+    plan_row(out, q.table_hit, q.BM, q.BN, q.ksplit, q.gx, q.gy, q.gz, form[q.family] | (skipped << 8));
+    return GIM_OK;
+}
+
 extern "C" int gim_conv_launch_plan(const gim_conv_shape* s, int kind, int32_t* out) {
     GIM_CHECK_ARG(s && out && kind >= 0 && kind <= 3, "conv_launch_plan: bad args");
-    float* const fake = reinterpret_cast<float*>(uintptr_t(4096));   // aligned, never dereferenced: nothing is launched
     for (int i = 0; i < 8; ++i) out[i] = -1;
-    t_plan_out = out;
-    int rc;
-    if (kind == 0) rc = gim_conv2d_fwd(fake, fake, nullptr, nullptr, nullptr, fake, s, nullptr);
-    else if (kind == 1) rc = gim_conv2d_dgrad(fake, fake, nullptr, nullptr, fake, s, nullptr);
-    else if (kind == 2) rc = gim_conv2d_dgrad_t(fake, fake, nullptr, nullptr, fake, s, nullptr);
-    else rc = gim_conv2d_wgrad_acc(fake, fake, fake, nullptr, s, nullptr);
-    t_plan_out = nullptr;
-    return rc;
+    return launch_plan(s, kind, out);
 }

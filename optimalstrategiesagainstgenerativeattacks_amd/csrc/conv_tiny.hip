@@ -24,7 +24,7 @@ struct TinyP {
     int res_ups;
 };
 
-constexpr int TT = 16;   // output tile edge
+constexpr int TT = GIM_TINY_TILE;   // output tile edge
 
 // FLIP = false: forward (gathered channels = CI of w, produced = CO); true: dgrad (gathered = CO, produced = CI, taps flipped)
 template <int K, int CI, int CO, bool FLIP>
@@ -145,54 +145,35 @@ bool gim_tiny_shape(const gim_conv_shape* s) {
     return !s->ups && !s->pool && !s->wfold && s->Cin == s->Cout && (s->Cin == 3 || s->Cin == 1) && (s->KH == 3 || s->KH == 9);
 }
 
+dim3 gim_tiny_grid(const gim_conv_shape* s) { return dim3(((s->H + TT - 1) / TT) * ((s->W + TT - 1) / TT), s->N); }
+
 template <bool FLIP>
 static void tiny_launch(const TinyP& p, const gim_conv_shape* s, hipStream_t st) {
-    const dim3 g(((s->H + TT - 1) / TT) * ((s->W + TT - 1) / TT), s->N);
+    const dim3 g = gim_tiny_grid(s);
     if (s->KH == 3 && s->Cin == 3) hipLaunchKernelGGL((conv_tiny_kernel<3, 3, 3, FLIP>), g, dim3(256), 0, st, p);
     else if (s->KH == 9 && s->Cin == 3) hipLaunchKernelGGL((conv_tiny_kernel<9, 3, 3, FLIP>), g, dim3(256), 0, st, p);
     else if (s->KH == 3) hipLaunchKernelGGL((conv_tiny_kernel<3, 1, 1, FLIP>), g, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((conv_tiny_kernel<9, 1, 1, FLIP>), g, dim3(256), 0, st, p);
 }
 
-bool gim_tiny_fwd(const float* x, const float* w, const float* bias, const float* sigma, const float* res, float* y,
-                  const gim_conv_shape* s, hipStream_t st, int32_t* plan_out) {
-    if (!gim_tiny_shape(s) || s->N > 65535) return false;
-    if (plan_out) {
-        const int32_t v[8] = {0, TT * TT, s->Cout, 1, ((s->H + TT - 1) / TT) * ((s->W + TT - 1) / TT), s->N, 1, 3};
-        for (int i = 0; i < 8; ++i) plan_out[i] = v[i];
-        return true;
-    }
+void gim_tiny_fwd(const float* x, const float* w, const float* bias, const float* sigma, const float* res, float* y,
+                  const gim_conv_shape* s, hipStream_t st) {
     TinyP p{};
     p.in = x; p.w = w; p.bias = bias; p.sigma = sigma; p.res = res; p.out = y;
     p.N = s->N; p.H = s->H; p.W = s->W; p.pre_slope = s->pre_slope; p.post_slope = s->post_slope > 0.f ? s->post_slope : 1.f; p.res_ups = s->res_ups;
     tiny_launch<false>(p, s, st);
-    return true;
 }
 
-bool gim_tiny_dgrad(const float* dy, const float* w, const float* sigma, const float* mask_x, float* dx, const gim_conv_shape* s,
-                    hipStream_t st, int32_t* plan_out) {
-    if (!gim_tiny_shape(s) || s->N > 65535) return false;
-    if (plan_out) {
-        const int32_t v[8] = {0, TT * TT, s->Cin, 1, ((s->H + TT - 1) / TT) * ((s->W + TT - 1) / TT), s->N, 1, 3};
-        for (int i = 0; i < 8; ++i) plan_out[i] = v[i];
-        return true;
-    }
+void gim_tiny_dgrad(const float* dy, const float* w, const float* sigma, const float* mask_x, float* dx, const gim_conv_shape* s,
+                    hipStream_t st) {
     TinyP p{};
     p.in = dy; p.w = w; p.sigma = sigma; p.res = mask_x; p.out = dx;
     p.N = s->N; p.H = s->H; p.W = s->W; p.pre_slope = s->pre_slope; p.post_slope = 1.f;
     tiny_launch<true>(p, s, st);
-    return true;
 }
 
-bool gim_tiny_wgrad_acc(const float* dy, const float* x, float* acc, float* bias_acc, const gim_conv_shape* s, hipStream_t st,
-                        int32_t* plan_out) {
-    if (!gim_tiny_shape(s) || s->N > 65535) return false;
-    const dim3 g(((s->H + TT - 1) / TT) * ((s->W + TT - 1) / TT), s->N);
-    if (plan_out) {
-        const int32_t v[8] = {0, 0, 0, (int32_t)(g.x * g.y), (int32_t)g.x, (int32_t)g.y, 1, 3};
-        for (int i = 0; i < 8; ++i) plan_out[i] = v[i];
-        return true;
-    }
+void gim_tiny_wgrad_acc(const float* dy, const float* x, float* acc, float* bias_acc, const gim_conv_shape* s, hipStream_t st) {
+    const dim3 g = gim_tiny_grid(s);
     TinyP p{};
     p.in = x; p.res = dy; p.out = acc; p.out2 = bias_acc;
     p.N = s->N; p.H = s->H; p.W = s->W; p.pre_slope = s->pre_slope;
@@ -200,5 +181,4 @@ bool gim_tiny_wgrad_acc(const float* dy, const float* x, float* acc, float* bias
     else if (s->KH == 9 && s->Cin == 3) hipLaunchKernelGGL((conv_tiny_wgrad_kernel<9, 3, 3>), g, dim3(256), 0, st, p);
     else if (s->KH == 3) hipLaunchKernelGGL((conv_tiny_wgrad_kernel<3, 1, 1>), g, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((conv_tiny_wgrad_kernel<9, 1, 1>), g, dim3(256), 0, st, p);
-    return true;
 }

@@ -895,3 +895,33 @@ def test_integration_md_ctypes_stub_runs():
     y_stub = ns["conv2d_nhwc"](x, w.permute(0, 2, 3, 1).contiguous(), b, sigma, leaky_slope=0.2)
     y_pkg = ops.conv2d(x, w, b, None, sigma, None, None, 0, 0.2)
     assert torch.equal(y_stub, y_pkg)
+
+
+def test_fwd_refuses_post_slope_on_a_split_k_launch_before_anything_is_enqueued():
+    """Library boundary (direct ctypes call): gim_conv2d_fwd with post_slope on a launch that splits K returns GIM_E_BADARG, sets the
+    message and leaves the output buffer untouched - no memset, no kernel: the K slices are combined by addition, so no nonlinearity
+    can follow them.  80 images of 4 x 4 pixels, 512 -> 512, 3 x 3: the shape test_deterministic_switch_... pins as splitting K."""
+    import ctypes
+
+    from optimalstrategiesagainstgenerativeattacks_amd import _lib
+    lib = _lib.load()
+    N, S, C, K = 80, 4, 512, 3
+    sh = _lib.GimConvShape(N, S, S, C, C, K, 0, 0.2)
+    sh.post_slope = 0.2
+    plan = (ctypes.c_int32 * 8)()
+    _lib.check(lib.gim_conv_launch_plan(ctypes.byref(sh), 0, ctypes.cast(plan, ctypes.c_void_p)), "plan")
+    assert plan[3] > 1, list(plan)
+    g = torch.Generator(device=dev()).manual_seed(5)
+    x = torch.randn(N, S, S, C, device=dev(), generator=g)
+    w = torch.randn(C, K, K, C, device=dev(), generator=g) / (C * K * K) ** 0.5
+    y = torch.full((N, S, S, C), 7.25, device=dev())
+    st = torch.cuda.current_stream().cuda_stream
+    rc = lib.gim_conv2d_fwd(x.data_ptr(), w.data_ptr(), None, None, None, y.data_ptr(), ctypes.byref(sh), st)
+    torch.cuda.synchronize()
+    assert rc == -1      # GIM_E_BADARG
+    assert b"post_slope with a launch that splits K" in lib.gim_last_error()
+    assert bool((y == 7.25).all()), "the refused call wrote to its output"
+    sh.post_slope = 0.0      # the same launch without the activation runs and fills y
+    _lib.check(lib.gim_conv2d_fwd(x.data_ptr(), w.data_ptr(), None, None, None, y.data_ptr(), ctypes.byref(sh), st), "fwd")
+    ref = F.conv2d(F.leaky_relu(x.double(), 0.2).permute(0, 3, 1, 2), w.double().permute(0, 3, 1, 2), padding=1).permute(0, 2, 3, 1)
+    assert relerr(y, ref) < TOL
