@@ -28,6 +28,29 @@ class GimInferConv(ctypes.Structure):
 P = c_void_p
 SP = POINTER(GimConvShape)
 
+
+# Rows of the job tables that the grouped launches read from device memory (ops.layout_tables).  Every `typedef struct` of
+# include/gim_hip.h has its mirror here under the same name in camel case (gim_sn_job -> GimSnJob); tests/test_host.py compares them.
+class GimFoldJob(ctypes.Structure):
+    _fields_ = [("w", P), ("f", P), ("Cout", c_int32), ("Cin", c_int32), ("KH", c_int32), ("reserved", c_int32)]
+
+
+class GimSnJob(ctypes.Structure):
+    _fields_ = [("w", P), ("u", P), ("v", P), ("off_sigma", c_int64), ("off_u", c_int64), ("off_v", c_int64), ("off_scratch", c_int64),
+                ("Cout", c_int32), ("Cin", c_int32), ("KH", c_int32), ("reserved", c_int32)]
+
+
+class GimWgradJob(ctypes.Structure):
+    _fields_ = [("src", P), ("bias_src", P), ("w", P), ("sigma", P), ("u", P), ("v", P), ("tmp", P), ("partial", P),
+                ("grad_w", P), ("grad_b", P), ("Cout", c_int32), ("Cin", c_int32), ("K", c_int32), ("fold", c_int32),
+                ("n_chunks", c_int32), ("exclusive", c_int32)]
+
+
+class GimGemmJob(ctypes.Structure):
+    _fields_ = [("A", P), ("B", P), ("C", P), ("bias", P), ("M", c_int32), ("N", c_int32), ("K", c_int32), ("ldc", c_int32),
+                ("sAi", c_int64), ("sAk", c_int64), ("sBk", c_int64), ("sBj", c_int64), ("flags", c_int32), ("reserved", c_int32)]
+
+
 # name -> argtypes (all return int unless noted); this table is also what tests check against the header
 SIGNATURES = {
     "gim_conv2d_fwd": [P, P, P, P, P, P, SP, P],

@@ -18,7 +18,6 @@ Unless noted, tensors between blocks are NHWC ``[N, H, W, C]`` float32 on the GP
 import collections
 import math
 
-import numpy as np
 import torch
 import torch.nn as nn
 
@@ -110,28 +109,18 @@ class SNConv2d(nn.Module):
         self.register_buffer("weight_v", v)
 
         self._sn_queue = collections.deque()  # (sigma, u, v) triples precomputed by an SNPlan round
-        self._fold_cache = None     # ops._DerivedWeights: the folded weights F of weight_orig at version _fold_version()
         self._wants_fold = False    # set by the first folded() call: SNPlan.run then folds this conv together with the others
-
-    def _fold_version(self):
-        """What F was made from: weight_orig's storage, autograd version counter (torch-side writes) and optim.weights_epoch (the
-        fused Adam kernel)."""
-        from . import optim
-        w = self.weight_orig
-        return (w.data_ptr(), w._version, optim.weights_epoch(w))
+        self._fold_slot = (kernel_size + 1, "fold")     # where ops._WT_CACHE keeps the folded weights F of weight_orig
 
     def fold_is_stale(self):
-        return self._fold_cache is None or self._fold_cache.version != self._fold_version()
+        return ops._WT_CACHE.is_stale(self.weight_orig, self._fold_slot)
 
     def folded(self):
         """The (k+1)^2-tap folded weights for the pool / sub-pixel forms, recomputed only when weight_orig changed; other streams
         (one per encoder pass) reuse F behind the kernel that wrote it (ops._StreamReady)."""
         self._wants_fold = True
-        if self.fold_is_stale():
-            with torch.no_grad():
-                f = ops._folded(ops.weight_phys(self.weight_orig), self.out_channels, self.in_channels, self.kernel_size)
-            self._fold_cache = ops._DerivedWeights(f, self._fold_version())
-        return self._fold_cache.use_on_current_stream()
+        return ops._WT_CACHE.get(self.weight_orig, self._fold_slot, lambda: ops._folded(
+            ops.weight_phys(self.weight_orig), self.out_channels, self.in_channels, self.kernel_size))
 
     def forward(self, x, res=None, ups=0, pre_slope=1.0, pool=False, res_ups=False, post_slope=1.0, x_act=False, fork_pool_slope=None):
         """post_slope != 1: returns (y, activated) - see ops.conv2d_post_act; x_act: x was stored activated by such a producer.
@@ -158,30 +147,27 @@ class SNPlan:
     weights and on u only, never on activations, so a forward pass that will call each conv `rounds` times runs
     `rounds` batched rounds up front (4 launches each, gim_spectral_sigma_batched) and every SNConv2d call then
     just pops its precomputed (sigma, u, v).  Sequential semantics are those of the per-call hook: round r uses
-    the u left by round r-1.  The job table is static and rebuilt only if a tensor moves.
+    the u left by round r-1.  The job table is static and rebuilt only if a tensor moves (ops._TableCache).
 
     The per-round outputs live in persistent buffers (two alternating sets), so their addresses are the same every
     step - which lets the batched weight-gradient finish (ops.WgradQueue) and hipGraph capture keep static tables.
     A backward pass that still needs a set which later forwards have overwritten (more than two forwards of the same
     model before its backward) is refused by ops.ConvFn rather than computed from stale values."""
 
-    _JOB = np.dtype([("w", "<u8"), ("u", "<u8"), ("v", "<u8"), ("off_sigma", "<i8"), ("off_u", "<i8"), ("off_v", "<i8"),
-                     ("off_scratch", "<i8"), ("Cout", "<i4"), ("Cin", "<i4"), ("KH", "<i4"), ("reserved", "<i4")])
-
     def __init__(self, convs):
         self.convs = [c for c in convs if isinstance(c, SNConv2d)]
-        self._key = None
         self._gen = 0      # number of run() calls so far; run g writes buffer set g & 1
         self._bufs = {}
+        self._tables = ops._TableCache("SNPlan", 1)     # (every conv's w, u, v address) -> job table of the power iterations
+        self._fold_tables = ops._TableCache("SNPlan folds", None, skip_in_capture=True)   # (w address of the stale convs) -> fold table + outputs
 
     def stale(self, gen):
         """True when the outputs of run number `gen` have been overwritten."""
         return self._gen - gen > 2
 
-    def _build(self, key):
-        dev = self.convs[0].weight_orig.device
-        jobs = np.zeros(len(self.convs), dtype=self._JOB)
-        cols, rows, self._views = [], [], []
+    def _build(self):
+        jobs = (_lib.GimSnJob * len(self.convs))()
+        cols, rows, views = [], [], []
         off = 0
 
         def take(n):
@@ -203,13 +189,8 @@ class SNPlan:
                     cols.append((j, xb, r, rows_per))
             for rb in range((Cout + 3) // 4):
                 rows.append((j, rb))
-            self._views.append((o_s, o_u, Cout, o_v, K))
-        self._total = off
-        self._jobs = torch.from_numpy(jobs.view(np.uint8).copy()).to(dev)
-        self._cols = torch.tensor(cols, dtype=torch.int32).to(dev)
-        self._rows = torch.tensor(rows, dtype=torch.int32).to(dev)
-        self._n = (len(self.convs), len(cols), len(rows))
-        self._key = key
+            views.append((o_s, o_u, Cout, o_v, K))
+        return ops._DeviceTable(jobs, cols, rows, extra=(len(jobs), len(cols), len(rows), off, views))
 
     @torch.no_grad()
     def run(self, rounds, training):
@@ -218,58 +199,52 @@ class SNPlan:
         w0 = self.convs[0].weight_orig
         if not (w0.is_cuda and w0.dtype == torch.float32):
             raise RuntimeError("weights must be CUDA float32 (got %s on %s): the GIM engine has no CPU path" % (w0.dtype, w0.device))
-        key = tuple(t.data_ptr() for c in self.convs for t in (c.weight_orig, c.weight_u, c.weight_v))
-        if key != self._key:
-            self._build(key)
-        lib = _lib.load()
-        dev = self.convs[0].weight_orig.device
+        tab = self._tables.get(tuple(t.data_ptr() for c in self.convs for t in (c.weight_orig, c.weight_u, c.weight_v)), self._build)
+        (d_jobs, d_cols, d_rows), (n_jobs, n_cols, n_rows, total, views) = tab.ptrs, tab.extra
+        raw = ops._stream()
+        tab.use_on_current_stream(raw)
         for c in self.convs:
             c._sn_queue.clear()
         gen = self._gen
         self._gen += 1
         for r in range(rounds):
             out = self._bufs.get((gen & 1, r))
-            if out is None or out.numel() != self._total or out.device != dev:
-                out = self._bufs[(gen & 1, r)] = torch.empty(self._total, device=dev, dtype=torch.float32)
-            _lib.check(lib.gim_spectral_sigma_batched(self._jobs.data_ptr(), self._n[0], self._cols.data_ptr(), self._n[1],
-                                                      self._rows.data_ptr(), self._n[2], out.data_ptr(), 1 if training else 0,
-                                                      torch.cuda.current_stream().cuda_stream), "spectral_sigma_batched")
-            for c, (o_s, o_u, Cout, o_v, K) in zip(self.convs, self._views):
+            if out is None or out.numel() != total or out.device != w0.device:
+                out = self._bufs[(gen & 1, r)] = torch.empty(total, device=w0.device, dtype=torch.float32)
+            _lib.check(_lib.load().gim_spectral_sigma_batched(d_jobs, n_jobs, d_cols, n_cols, d_rows, n_rows, out.data_ptr(), 1 if training else 0, raw),
+                       "spectral_sigma_batched")
+            for c, (o_s, o_u, Cout, o_v, K) in zip(self.convs, views):
                 c._sn_queue.append((out[o_s:o_s + 1], out[o_u:o_u + Cout], out[o_v:o_v + K], (self, gen)))
-        self._fold_stale()
+        self._fold_stale(raw)
 
-    def _fold_stale(self):
+    def _fold_stale(self, raw):
         """The folded weights (pool / sub-pixel forms) of every conv of the plan whose weights changed since its last fold, in ONE
         launch (each conv would otherwise fold itself at its first use: ~30 launches of ~10 us per training step, on the
-        forward's critical path).  Results go where SNConv2d.folded() keeps them."""
+        forward's critical path).  Results go where SNConv2d.folded() finds them; a set of stale convs first met inside a hipGraph
+        capture is left to fold itself."""
         todo = [c for c in self.convs if c._wants_fold and c.fold_is_stale()]
         if len(todo) < 2:
             return     # a single stale conv folds itself at its call
-        dev = todo[0].weight_orig.device
-        sig = tuple(c.weight_orig.data_ptr() for c in todo)
-        ent = getattr(self, "_fold_tab", {}).get(sig)
-        if ent is None:
-            if torch.cuda.is_current_stream_capturing():
-                return
-            jobs = np.zeros(len(todo), dtype=np.dtype([("w", "<u8"), ("f", "<u8"), ("Cout", "<i4"), ("Cin", "<i4"), ("KH", "<i4"), ("r", "<i4")]))
-            bufs, tab = [], []
+
+        def build():
+            jobs = (_lib.GimFoldJob * len(todo))()
+            bufs, chunks = [], []
             for j, c in enumerate(todo):
                 KF = c.kernel_size + 1
                 n = c.out_channels * KF * KF * c.in_channels
                 if n >= 1 << 31:
                     raise RuntimeError("folded weights of more than 2^31 elements (gim_conv2d_fold_weights_batched indexes with 32 bits)")
-                f = torch.empty(n, device=dev, dtype=torch.float32)
-                bufs.append(f)
-                jobs[j] = (c.weight_orig.data_ptr(), f.data_ptr(), c.out_channels, c.in_channels, c.kernel_size, 0)
-                tab += [(j, ch) for ch in range((n + 65535) // 65536)]
-            ent = (torch.from_numpy(jobs.view(np.uint8).copy()).to(dev), torch.tensor(tab, dtype=torch.int32).to(dev), len(tab), bufs)
-            if not hasattr(self, "_fold_tab"):
-                self._fold_tab = {}
-            self._fold_tab[sig] = ent
-        dj, dt, nb, bufs = ent
-        _lib.check(_lib.load().gim_conv2d_fold_weights_batched(dj.data_ptr(), dt.data_ptr(), nb, ops._stream()), "fold_weights_batched")
-        for c, f in zip(todo, bufs):
-            c._fold_cache = ops._DerivedWeights(f, c._fold_version())
+                bufs.append(torch.empty(n, device=c.weight_orig.device, dtype=torch.float32))
+                jobs[j] = (c.weight_orig.data_ptr(), bufs[j].data_ptr(), c.out_channels, c.in_channels, c.kernel_size, 0)
+                chunks += [(j, ch) for ch in range((n + 65535) // 65536)]
+            return ops._DeviceTable(jobs, chunks, extra=(len(chunks), bufs))
+        tab = self._fold_tables.get(tuple(c.weight_orig.data_ptr() for c in todo), build)
+        if tab is None:
+            return
+        tab.use_on_current_stream(raw)
+        _lib.check(_lib.load().gim_conv2d_fold_weights_batched(tab.ptrs[0], tab.ptrs[1], tab.extra[0], raw), "fold_weights_batched")
+        for c, f in zip(todo, tab.extra[1]):
+            ops._WT_CACHE.install(c.weight_orig, c._fold_slot, f)
 
 
 def sn_convs(*modules):

@@ -7,14 +7,15 @@ must be CUDA(HIP) float32.  Activations are NHWC.
 import collections
 import ctypes
 import os
+import struct
 import weakref
 
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import _lib
-from ._lib import GimConvShape, check
+from . import _lib, optim
+from ._lib import GimConvShape, GimGemmJob, GimWgradJob, check
 
 LRELU_SLOPE = 0.2
 
@@ -331,8 +332,8 @@ def _folded(wp, Cout, Cin, KH):
 
 
 class _StreamReady:
-    """A buffer that ONE stream writes and others then use (the lanes and the encoders' side streams share WgradQueue pages, _transposed
-    and SNConv2d.folded weights).  Built right after the writing work was issued on the current stream."""
+    """A buffer that ONE stream writes and others then use (the lanes and the encoders' side streams share WgradQueue pages, the job
+    tables of the grouped launches and the weight copies of _WT_CACHE).  Built right after the writing work was issued on the current stream."""
     __slots__ = ("tensor", "event", "streams", "in_capture")
 
     def __init__(self, tensor):
@@ -364,16 +365,60 @@ class _StreamReady:
 
 
 # --------------------------------------------------------------------------------------------
+# job tables of the grouped launches (one launch serves many layers and reads their jobs from device memory)
+# --------------------------------------------------------------------------------------------
+def layout_tables(jobs, *tables):
+    """(bytes, offsets): a ctypes array of job structs (_lib.Gim*Job) and any number of int32 tables (lists of equal-length int
+    tuples: which block works on what) as ONE buffer, every section at a multiple of 16 bytes.  An empty table becomes one
+    placeholder row of two zeros, so that its launch is always handed a valid pointer."""
+    blob, offsets = bytearray(), []
+    for sec in [bytes(jobs)] + [struct.pack("<%di" % (len(t) * len(t[0])), *(v for row in t for v in row)) if t else bytes(8)
+                                for t in tables]:
+        blob += bytes(-len(blob) % 16)
+        offsets.append(len(blob))
+        blob += sec
+    return bytes(blob), offsets
+
+
+class _DeviceTable(_StreamReady):
+    """layout_tables(...) in device memory: one pinned staging buffer (kept alive here: the copy is asynchronous), one copy on
+    the current stream.  ptrs: device address of each section; extra: what the site keeps beside them (row counts, buffers the jobs
+    point to).  Every launch first calls use_on_current_stream(raw): a stream other than the builder's then waits for the copy."""
+    __slots__ = ("host", "ptrs", "extra")
+
+    def __init__(self, jobs, *tables, extra=None):
+        blob, offsets = layout_tables(jobs, *tables)
+        self.host = torch.frombuffer(bytearray(blob), dtype=torch.uint8).pin_memory()
+        super().__init__(self.host.to(torch.device("cuda", torch._C._cuda_getDevice()), non_blocking=True))
+        self.ptrs, self.extra = [self.tensor.data_ptr() + o for o in offsets], extra
+
+
+class _TableCache(collections.OrderedDict):
+    """signature -> what build() made of it (a _DeviceTable), least recently used entry dropped beyond `capacity` (None: never).
+    The signatures are addresses of parameters, their .grad buffers and allocator blocks, which repeat from step to step.  A miss
+    inside a hipGraph capture cannot upload a table: get() raises or, with skip_in_capture, returns None."""
+
+    def __init__(self, what, capacity=None, skip_in_capture=False):
+        super().__init__()
+        self.what, self.capacity, self.skip_in_capture = what, capacity, skip_in_capture
+
+    def get(self, sig, build):
+        if sig in self:
+            self.move_to_end(sig)
+        elif not (torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()):
+            self[sig] = build()
+            if self.capacity is not None and len(self) > self.capacity:
+                self.popitem(last=False)
+        elif self.skip_in_capture:
+            return None
+        else:
+            raise RuntimeError("%s: a job table not seen before; run eager warm-up steps (at least 2) before capturing a hipGraph" % self.what)
+        return self[sig]
+
+
+# --------------------------------------------------------------------------------------------
 # deferred, batched weight-gradient finish
 # --------------------------------------------------------------------------------------------
-class _WgradJob(ctypes.Structure):
-    _fields_ = [("src", ctypes.c_void_p), ("bias_src", ctypes.c_void_p), ("w", ctypes.c_void_p), ("sigma", ctypes.c_void_p),
-                ("u", ctypes.c_void_p), ("v", ctypes.c_void_p), ("tmp", ctypes.c_void_p), ("partial", ctypes.c_void_p),
-                ("grad_w", ctypes.c_void_p), ("grad_b", ctypes.c_void_p),
-                ("Cout", ctypes.c_int32), ("Cin", ctypes.c_int32), ("K", ctypes.c_int32), ("fold", ctypes.c_int32),
-                ("n_chunks", ctypes.c_int32), ("exclusive", ctypes.c_int32)]
-
-
 class _ArenaPage(_StreamReady):
     """One zero-filled page of a WgradQueue arena; its first `used` floats are handed out."""
     __slots__ = ("used",)
@@ -404,7 +449,7 @@ class WgradQueue:
         self.streams = set()
         self.stream_of = {}   # raw stream handle -> torch Stream object
         self.cb_queued = False
-        self.cache = collections.OrderedDict()   # job-table signature -> device tables (G / D backward, buffer parities)
+        self.cache = _TableCache("WgradQueue", 16)   # job tuples -> _DeviceTable (G / D backward, buffer parities)
         self.enabled = os.environ.get("GIM_WGRAD_IMMEDIATE") is None
 
     def take(self, n, device):
@@ -436,41 +481,27 @@ class WgradQueue:
         cur = torch.cuda.current_stream()
         for st in self.streams:   # slots were written on the encoders' side streams too
             stream_wait(cur, st)
-        device = self.pages[0].tensor.device
         sig = tuple(self.jobs)
-        dev_tabs = self.cache.get(sig)
-        if dev_tabs is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("WgradQueue: this backward pass has a job table not seen before; run eager warm-up steps "
-                                   "(at least 2) before capturing a hipGraph")
-            arr = (_WgradJob * len(sig))()
+
+        def build():
+            arr = (GimWgradJob * len(sig))()
             tab, tab_sn = [], []
             targets = collections.Counter(jb[8] for jb in sig)   # grad_w pointers: a conv called several times in the pass has several jobs
             for j, jb in enumerate(sig):
-                a = arr[j]
-                (a.src, a.bias_src, a.w, a.sigma, a.u, a.v, a.tmp, a.partial, a.grad_w, a.grad_b,
-                 a.Cout, a.Cin, a.K, a.fold, a.n_chunks) = jb
-                a.exclusive = 1 if targets[jb[8]] == 1 else 0
+                arr[j] = jb + (1 if targets[jb[8]] == 1 else 0,)    # exclusive
                 blocks = [(j, c) for c in range(jb[14])]
                 tab += blocks
                 if jb[3]:
                     tab_sn += blocks
-            host_jobs = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).pin_memory()
-            host_tab = torch.tensor(tab, dtype=torch.int32).pin_memory()
-            host_sn = torch.tensor(tab_sn if tab_sn else [(0, 0)], dtype=torch.int32).pin_memory()
-            dev_tabs = (host_jobs.to(device, non_blocking=True), host_tab.to(device, non_blocking=True),
-                        host_sn.to(device, non_blocking=True), len(tab), len(tab_sn), (host_jobs, host_tab, host_sn))
-            self.cache[sig] = dev_tabs
-            while len(self.cache) > 16:
-                self.cache.popitem(last=False)
-        else:
-            self.cache.move_to_end(sig)
-        dj, dt, dsn, nb, nbs, _ = dev_tabs
-        check(_lib.load().gim_wgrad_finish_batched(dj.data_ptr(), len(sig), dt.data_ptr(), nb, dsn.data_ptr(), nbs, _stream()),
-              "wgrad_finish_batched")
+            return _DeviceTable(arr, tab, tab_sn, extra=(len(tab), len(tab_sn)))
+        ent = self.cache.get(sig, build)
+        raw = _stream()
+        ent.use_on_current_stream(raw)
+        (dj, dt, dsn), (nb, nbs) = ent.ptrs, ent.extra
+        check(_lib.load().gim_wgrad_finish_batched(dj, len(sig), dt, nb, dsn, nbs, raw), "wgrad_finish_batched")
         if len(self.pages) > 1:  # first backward of a new shape: merge into one page for the next pass
             total = sum(pg.used for pg in self.pages)
-            self.pages = [_ArenaPage(total + (total >> 3), device)]
+            self.pages = [_ArenaPage(total + (total >> 3), self.pages[0].tensor.device)]
             self.cache.clear()
         else:
             # the re-zeroing runs on the flushing stream; the next pass's first user on every other stream waits for it
@@ -777,44 +808,62 @@ class ConvFn(Function):
         return (dx, dw, db, dres) + (None,) * ConvFn.N_EXTRA
 
 
-_WT_CACHE = {}   # (weight data_ptr, taps per dim, layout) -> _DerivedWeights
-
-
 class _DerivedWeights(_StreamReady):
-    """A re-laid-out copy of a parameter's weights (_transposed, SNConv2d.folded); version: of the weights it was made from."""
+    """One entry of _WT_CACHE; version: of the weights it was made from, param: weak reference to the parameter."""
     __slots__ = ("version", "param")
 
-    def __init__(self, tensor, version, param=None):
-        super().__init__(tensor)
-        self.version, self.param = version, param     # param: weak reference to the owner, where a cache needs one
+
+class _DerivedWeightCache(dict):
+    """Copies of a parameter's weights in another layout (_transposed's four, SNConv2d's "fold"), one per (parameter storage,
+    slot = (taps per dim, layout)), each valid while the weights are what it was made from: the same parameter object, autograd
+    version counter (torch-side writes) and optim.weights_epoch (the fused Adam kernel).  Entries leave with their parameter."""
+
+    def _fresh(self, w, slot):
+        ent = dict.get(self, (w.data_ptr(),) + slot)
+        return ent if ent is not None and ent.version == (w._version, optim.weights_epoch(w)) and ent.param() is w else None
+
+    def is_stale(self, w, slot):
+        return self._fresh(w, slot) is None
+
+    def install(self, w, slot, tensor):
+        """`tensor` was just written on the current stream from w's weights as they are now (by `make` of get, or elsewhere)."""
+        key = (w.data_ptr(),) + slot
+        ent = self[key] = _DerivedWeights(tensor)
+        ent.version, ent.param = (w._version, optim.weights_epoch(w)), weakref.ref(w, lambda _r: self.pop(key, None))
+        return ent
+
+    def get(self, w, slot, make, raw=None):
+        """The copy in `slot`, made by make() if there is none of the current weights, ready for use on the current stream (raw)."""
+        ent = self._fresh(w, slot)
+        if ent is None:
+            with torch.no_grad():
+                ent = self.install(w, slot, make())
+        return ent.use_on_current_stream(raw)
+
+
+_WT_CACHE = _DerivedWeightCache()
 
 
 def _transposed(lib, w, wk, Cout, Cin, KF, xfold=0, rows=False, subpix=False):
     """WT[Cin][KF][KF][Cout] of the (plain or folded) weights `wk` of parameter `w` - or, xfold = J, the x-folded
     WX[J * Cin][KF][KF + J - 1][Cout] of gim_conv2d_xfold_weights; or, rows, the row-padded WP[Cout][KF][KF * Cin -> 16] of
     gim_conv2d_pack_rows_weights; or, subpix (wk = the folded taps, KF = the conv's K), the stacked parity classes
-    WM[4 Cout][(KF+1)/2][(KF+1)/2][Cin] of gim_conv2d_pack_subpixel_weights - recomputed only when the weights changed (autograd version
-    counter for torch-side writes, optim.weights_epoch for the fused Adam kernel)."""
-    from . import optim
-    version = (w._version, optim.weights_epoch(w))
-    slot = (w.data_ptr(), KF, "rows" if rows else ("subpix" if subpix else xfold))
-    ent = _WT_CACHE.get(slot)
+    WM[4 Cout][(KF+1)/2][(KF+1)/2][Cin] of gim_conv2d_pack_subpixel_weights - from _WT_CACHE: made again only when the weights changed."""
     raw = _stream()
-    if ent is None or ent.version != version or ent.param() is not w:
-        if rows:
-            wt = torch.empty(Cout * KF * ((KF * Cin + 15) & ~15), device=wk.device, dtype=torch.float32)
-            check(lib.gim_conv2d_pack_rows_weights(_p(wk), _p(wt), Cout, Cin, KF, raw), "pack_rows_weights")
-        elif subpix:
-            wt = torch.empty(4 * Cout * ((KF + 1) // 2) ** 2 * Cin, device=wk.device, dtype=torch.float32)
-            check(lib.gim_conv2d_pack_subpixel_weights(_p(wk), _p(wt), Cout, Cin, KF, raw), "pack_subpixel_weights")
-        elif xfold:
-            wt = torch.empty(xfold * Cin * KF * (KF + xfold - 1) * Cout, device=wk.device, dtype=torch.float32)
-            check(lib.gim_conv2d_xfold_weights(_p(wk), _p(wt), Cout, Cin, KF, xfold, raw), "xfold_weights")
-        else:
-            wt = torch.empty(Cin * KF * KF * Cout, device=wk.device, dtype=torch.float32)
-            check(lib.gim_conv2d_transpose_weights(_p(wk), _p(wt), Cout, Cin, KF, raw), "transpose_weights")
-        ent = _WT_CACHE[slot] = _DerivedWeights(wt, version, weakref.ref(w, lambda _r, slot=slot: _WT_CACHE.pop(slot, None)))
-    return ent.use_on_current_stream(raw)
+
+    def run(fn, n, what, *tail):
+        wt = torch.empty(n, device=wk.device, dtype=torch.float32)
+        check(fn(_p(wk), _p(wt), Cout, Cin, KF, *tail, raw), what)
+        return wt
+    if rows:
+        layout, make = "rows", lambda: run(lib.gim_conv2d_pack_rows_weights, Cout * KF * ((KF * Cin + 15) & ~15), "pack_rows_weights")
+    elif subpix:
+        layout, make = "subpix", lambda: run(lib.gim_conv2d_pack_subpixel_weights, 4 * Cout * ((KF + 1) // 2) ** 2 * Cin, "pack_subpixel_weights")
+    elif xfold:
+        layout, make = xfold, lambda: run(lib.gim_conv2d_xfold_weights, xfold * Cin * KF * (KF + xfold - 1) * Cout, "xfold_weights", xfold)
+    else:
+        layout, make = 0, lambda: run(lib.gim_conv2d_transpose_weights, Cin * KF * KF * Cout, "transpose_weights")
+    return _WT_CACHE.get(w, (KF, layout), make, raw)
 
 
 def _conv_dgrad(lib, dy, x, wp, wf, sigma, sh, g, st, w=None, res_half=None):
@@ -1066,41 +1115,19 @@ def linear(x, w, bias=None, pre_slope=1.0):
 # --------------------------------------------------------------------------------------------
 # grouped linears (many nn.Linear on one shared input: the style projections of the AdaIN blocks)
 # --------------------------------------------------------------------------------------------
-class _GemmJob(ctypes.Structure):
-    _fields_ = [("A", ctypes.c_void_p), ("B", ctypes.c_void_p), ("C", ctypes.c_void_p), ("bias", ctypes.c_void_p),
-                ("M", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("ldc", ctypes.c_int32),
-                ("sAi", ctypes.c_int64), ("sAk", ctypes.c_int64), ("sBk", ctypes.c_int64), ("sBj", ctypes.c_int64),
-                ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+_GEMM_TABLES = _TableCache("grouped linears", 64)
 
 
-_GEMM_TABLES = collections.OrderedDict()   # job-list signature -> (device jobs, device tiles, n_tiles, pinned host copies)
-
-
-def _gemm_tables(jobs, col_tiles_only=False):
-    """Device job / tile tables of a grouped launch (include/gim_hip.h gim_gemm_job), cached by their content: the operands are
-    parameters, their .grad buffers and allocator blocks whose addresses repeat from step to step."""
-    sig = (tuple(jobs), col_tiles_only)
-    ent = _GEMM_TABLES.get(sig)
-    if ent is None:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("grouped linears: a job table not seen before; run eager warm-up steps before capturing a hipGraph")
-        arr = (_GemmJob * len(jobs))()
-        tiles = []
-        for j, jb in enumerate(jobs):
-            a = arr[j]
-            (a.A, a.B, a.C, a.bias, a.M, a.N, a.K, a.ldc, a.sAi, a.sAk, a.sBk, a.sBj, a.flags) = jb
-            for it in range(1 if col_tiles_only else (jb[4] + 63) // 64):
-                for jt in range((jb[5] + 63) // 64):
-                    tiles.append((j, it, jt))
-        hj = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).pin_memory()
-        ht = torch.tensor(tiles, dtype=torch.int32).pin_memory()
-        dev = torch.device("cuda", torch._C._cuda_getDevice())
-        ent = _GEMM_TABLES[sig] = (hj.to(dev, non_blocking=True), ht.to(dev, non_blocking=True), len(tiles), (hj, ht))
-        while len(_GEMM_TABLES) > 64:
-            _GEMM_TABLES.popitem(last=False)
-    else:
-        _GEMM_TABLES.move_to_end(sig)
-    return ent
+def _gemm_tables(jobs, col_tiles_only=False, raw=None):
+    """(device job table, device tile table, tiles) of a grouped launch on stream `raw` (include/gim_hip.h gim_gemm_job)."""
+    def build():
+        arr = (GimGemmJob * len(jobs))(*jobs)
+        tiles = [(j, it, jt) for j, jb in enumerate(jobs) for it in range(1 if col_tiles_only else (jb[4] + 63) // 64)
+                 for jt in range((jb[5] + 63) // 64)]
+        return _DeviceTable(arr, tiles, extra=len(tiles))
+    ent = _GEMM_TABLES.get((tuple(jobs), col_tiles_only), build)
+    ent.use_on_current_stream(raw)
+    return ent.ptrs[0], ent.ptrs[1], ent.extra
 
 
 class GroupedLinearFn(Function):
@@ -1125,8 +1152,8 @@ class GroupedLinearFn(Function):
             ys.append(buf[off:off + M * n_].view(M, n_))
             off += M * n_
         jobs = [(_p(x), _p(w), _p(y), _p(b) or 0, M, n_, K, n_, K, 1, 1, K, 0) for w, b, y, n_ in zip(ws, bs, ys, sizes)]
-        dj, dt, nt, _ = _gemm_tables(jobs)
-        check(lib.gim_bgemm_grouped(dj.data_ptr(), dt.data_ptr(), nt, _stream()), "bgemm_grouped")
+        st = _stream()
+        check(lib.gim_bgemm_grouped(*_gemm_tables(jobs, raw=st), st), "bgemm_grouped")
         for n_ in sizes:
             _note_bgemm(1, M, n_, K)
         ctx.save_for_backward(x, *wb)
@@ -1163,11 +1190,9 @@ class GroupedLinearFn(Function):
                 _note_bgemm(1, M, n_, K, 2)
             grads += [gw, gb]
         if jobs:
-            dj, dt, nt, _ = _gemm_tables(jobs)
-            check(lib.gim_bgemm_grouped(dj.data_ptr(), dt.data_ptr(), nt, st), "bgemm_grouped")
+            check(lib.gim_bgemm_grouped(*_gemm_tables(jobs, raw=st), st), "bgemm_grouped")
         if cjobs:
-            dj, dt, nt, _ = _gemm_tables(cjobs, col_tiles_only=True)
-            check(lib.gim_colsum_grouped(dj.data_ptr(), dt.data_ptr(), nt, st), "colsum_grouped")
+            check(lib.gim_colsum_grouped(*_gemm_tables(cjobs, True, st), st), "colsum_grouped")
         return (dx, *grads)
 
 

@@ -321,7 +321,8 @@ def test_bench_dump_outputs_names_dtype_and_budget(tmp_path):
 
 def test_conv_shape_struct_matches_the_header():
     """The ctypes mirror of gim_conv_shape has the header's fields in the header's order (matrix path and launch overrides are
-    per-call fields: the library has no precision / tuning globals)."""
+    per-call fields: the library has no precision / tuning globals) - and so has the mirror of every other struct of the header
+    (the job tables of the grouped launches), each field at the offset the header's field sizes give it."""
     from optimalstrategiesagainstgenerativeattacks_amd import _lib
     header = open(os.path.join(ROOT, "include", "gim_hip.h")).read()
     body = re.search(r"typedef struct \{([^}]*)\} gim_conv_shape;", header).group(1)
@@ -333,6 +334,80 @@ def test_conv_shape_struct_matches_the_header():
     assert fields == [f for f, _ in _lib.GimConvShape._fields_], fields
     assert ctypes.sizeof(_lib.GimConvShape) == 4 * len(fields)
     assert "gim_conv_precision" not in header and "gim_conv_tune_override" not in header
+
+    structs = re.findall(r"typedef struct \{([^}]*)\} (gim_\w+);", header)
+    assert len(structs) == header.count("typedef struct") >= 6
+    sizes = {}
+    for body, name in structs:
+        mirror = getattr(_lib, "".join(part.capitalize() for part in name.split("_")))      # gim_sn_job -> GimSnJob: must exist
+        expect, off = [], 0
+        for decl in re.sub(r"/\*.*?\*/", "", body, flags=re.S).split(";"):
+            decl = decl.strip()
+            if not decl:
+                continue
+            if "*" in decl:      # "const float* w"
+                size, names = 8, [decl.rsplit("*", 1)[1]]
+            else:                # "int32_t Cout, Cin, KH, reserved"
+                ctype, names = decl.split(None, 1)
+                size, names = {"int64_t": 8, "int32_t": 4, "float": 4}[ctype], names.split(",")
+            for f in names:
+                expect.append((f.strip(), off))
+                off += size
+        assert [(f, getattr(mirror, f).offset) for f, _ in mirror._fields_] == expect, name
+        assert ctypes.sizeof(mirror) == off, name
+        sizes[name] = off
+    assert sizes == {"gim_conv_shape": 68, "gim_infer_conv": 28, "gim_fold_job": 32, "gim_sn_job": 72, "gim_wgrad_job": 104,
+                     "gim_gemm_job": 88}
+
+
+def test_job_table_layout():
+    """ops.layout_tables: the job structs and the int32 tables of a grouped launch as one buffer of 16-byte-aligned sections; an
+    empty table is a placeholder row of zeros."""
+    import struct
+    from optimalstrategiesagainstgenerativeattacks_amd import _lib, ops
+    jobs = (_lib.GimFoldJob * 3)((0x7f0000001000, 0x7f0000002000, 3, 5, 1, 0), (0x7f0000003000, 0x7f0000004000, 16, 8, 3, 0),
+                                 (0x7f0000005000, 0x7f0000006000, 72, 64, 3, 0))
+    tab = [(0, 0), (1, 0), (2, 1)]
+    blob, offsets = ops.layout_tables(jobs, tab, [])
+    sections = [bytes(jobs), struct.pack("<6i", 0, 0, 1, 0, 2, 1), bytes(8)]
+    assert len(sections[0]) == 3 * 32 and len(offsets) == 3 and offsets[0] == 0
+    for off, sec in zip(offsets, sections):
+        assert off % 16 == 0 and blob[off:off + len(sec)] == sec
+    assert offsets == sorted(offsets) and all(b >= a + len(sec) for a, b, sec in zip(offsets, offsets[1:], sections))
+    assert len(blob) == offsets[-1] + len(sections[-1])
+    # a table whose length is no multiple of 16 bytes pushes the next section to the next boundary
+    blob, offsets = ops.layout_tables(jobs, [(7, 8, 9)], [(1, 2)])
+    assert offsets == [0, 96, 112] and blob[96:108] == struct.pack("<3i", 7, 8, 9) and blob[112:] == struct.pack("<2i", 1, 2)
+
+
+def test_job_table_cache_is_lru():
+    """ops._TableCache: build runs once per miss, a hit renews the entry, the least recently used one leaves beyond the capacity."""
+    from optimalstrategiesagainstgenerativeattacks_amd import ops
+    built = []
+
+    def build_for(sig):
+        def build():
+            built.append(sig)
+            return ("table", sig)
+        return build
+    cache = ops._TableCache("test", 2)
+    assert len(cache) == 0
+    assert cache.get("a", build_for("a")) == ("table", "a") and cache.get("b", build_for("b")) == ("table", "b")
+    assert len(cache) == 2 and built == ["a", "b"]
+    assert cache.get("c", build_for("c")) == ("table", "c")
+    assert len(cache) == 2 and list(cache) == ["b", "c"]                 # the first signature was evicted
+    assert cache.get("b", build_for("b")) == ("table", "b") and built == ["a", "b", "c"]
+    assert list(cache) == ["c", "b"]                                     # the hit moved its entry to the end ...
+    cache.get("d", build_for("d"))
+    assert list(cache) == ["b", "d"] and built == ["a", "b", "c", "d"]   # ... so the other one left
+    cache.get("a", build_for("a"))
+    assert built == ["a", "b", "c", "d", "a"] and len(cache) == 2
+    cache.clear()
+    assert len(cache) == 0
+    unbounded = ops._TableCache("test")
+    for i in range(100):
+        unbounded.get(i, build_for(i))
+    assert len(unbounded) == 100
 
 
 def test_library_sources_read_no_environment_and_keep_no_mutable_globals():

@@ -61,11 +61,7 @@ class GraphedGimStep:
         # With the counters restored, the caches of tensors derived from the weights (folded weights per conv, transposed weights
         # of the image-gradient dgrad) carry the keys of tensors that the capture only RECORDED, never computed: an eager forward before
         # the first replay would read them.  Drop them (the graph keeps its own references and recomputes them on every replay).
-        from optimalstrategiesagainstgenerativeattacks_amd import model_blocks as mb
         from optimalstrategiesagainstgenerativeattacks_amd import ops
-        for m_ in list(self.mod.authenticator.modules()) + list(self.mod.impersonator.modules()):
-            if isinstance(m_, mb.SNConv2d):
-                m_._fold_cache = None
         ops._WT_CACHE.clear()
         # The weight-gradient arenas were re-zeroed by the flush INSIDE the capture: their "zeroed" marks hold an event that was
         # recorded on a capturing stream only.  An eager backward on another stream would wait on that event from outside the
