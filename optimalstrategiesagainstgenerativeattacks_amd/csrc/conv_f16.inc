@@ -193,24 +193,11 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f16_kernel(const ConvP p) {
         if (ks + 1 < nk) kstep(ks + 1, std::integral_constant<int, 1>(), std::false_type());
     }
 
-    // ---- epilogue: the fp32 kernels' (conv_igemm_kernel) ----
+    // ---- epilogue: the fp32 kernels' (epi_fill, epi_dispatch, epi_block) ----
     EpiCtx ec;
-    ec.pmN = 0;
-    ec.scale = p.out_scale * (p.sigma ? 1.0f / p.sigma[0] : 1.0f);
-    ec.mask_slope = p.mask_slope;
-    ec.post_slope = p.post_slope;
-    ec.res_scale = p.res_scale;
     const bool first = kslice == 0;
-    const bool has_res = p.res != nullptr && first, has_mask = p.mask_x != nullptr;
-    ec.atom = p.ksplit > 1;
-    ec.remap = g.os != 1;
-    ec.M = p.M; ec.Cb = p.Cb;
-    ec.logH = g.logH; ec.logW = g.logW; ec.Hm1 = g.H - 1; ec.Wm1 = g.W - 1; ec.os = g.os; ec.py = g.py; ec.px = g.px;
-    ec.Ho = g.H * g.os; ec.Wo = g.W * g.os;
-    const unsigned ybytes = (unsigned)g.N * (unsigned)ec.Ho * (unsigned)ec.Wo * (unsigned)p.Cb * 4u;
-    ec.ry = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, ybytes, 0x00020000);
-    ec.rr = __builtin_amdgcn_make_buffer_rsrc((void*)p.res, 0, has_res ? ((p.res_ups || has_mask) ? ybytes >> 2 : ybytes) : 0u, 0x00020000);
-    ec.rm = __builtin_amdgcn_make_buffer_rsrc((void*)p.mask_x, 0, has_mask ? ybytes : 0u, 0x00020000);
+    bool has_res, has_mask;
+    epi_fill<false, false>(ec, p, g, first, has_res, has_mask);
     auto run = [&](auto MODEC) {
         constexpr int MODE = decltype(MODEC)::value;
 #pragma unroll
@@ -226,16 +213,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f16_kernel(const ConvP p) {
                 epi_block<16, MODE>(ec, a_, m0 + wm0 + 32 * i + 4 * h, co, cok, bv);
             }
     };
-    if (has_res && has_mask) {     // dgrad with the pooled skip gradient folded in (gim_conv2d_dgrad_res): mask, then + res_scale * up2(res)
-        run(std::integral_constant<int, 4>());
-    } else if (has_res) {
-        if (p.res_ups) run(std::integral_constant<int, 2>());
-        else run(std::integral_constant<int, 1>());
-    } else if (has_mask) {
-        run(std::integral_constant<int, 3>());
-    } else {
-        run(std::integral_constant<int, 0>());
-    }
+    epi_dispatch<0, 0>(p, has_res, has_mask, run);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -402,22 +380,9 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_patch_f16_kernel(const Conv
     if (ch < ch1) chunk(ch, std::integral_constant<int, 0>());
 
     EpiCtx ec;
-    ec.pmN = 0;
-    ec.scale = p.out_scale * (p.sigma ? 1.0f / p.sigma[0] : 1.0f);
-    ec.mask_slope = p.mask_slope;
-    ec.post_slope = p.post_slope;
-    ec.res_scale = p.res_scale;
     const bool first = kslice == 0;
-    const bool has_res = p.res != nullptr && first, has_mask = p.mask_x != nullptr;
-    ec.atom = p.ksplit > 1;
-    ec.remap = false;
-    ec.M = p.M; ec.Cb = p.Cb;
-    ec.logH = g.logH; ec.logW = g.logW; ec.Hm1 = g.H - 1; ec.Wm1 = g.W - 1; ec.os = 1; ec.py = 0; ec.px = 0;
-    ec.Ho = g.H; ec.Wo = g.W;
-    const unsigned ybytes = (unsigned)g.N * (unsigned)g.H * (unsigned)g.W * (unsigned)p.Cb * 4u;
-    ec.ry = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, ybytes, 0x00020000);
-    ec.rr = __builtin_amdgcn_make_buffer_rsrc((void*)p.res, 0, has_res ? ((p.res_ups || has_mask) ? ybytes >> 2 : ybytes) : 0u, 0x00020000);
-    ec.rm = __builtin_amdgcn_make_buffer_rsrc((void*)p.mask_x, 0, has_mask ? ybytes : 0u, 0x00020000);
+    bool has_res, has_mask;
+    epi_fill<true, false>(ec, p, g, first, has_res, has_mask);
     auto run = [&](auto MODEC) {
         constexpr int MODE = decltype(MODEC)::value;
 #pragma unroll
@@ -433,16 +398,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_patch_f16_kernel(const Conv
                 epi_block<16, MODE>(ec, a_, m0 + wm0 + 32 * i + 4 * h, co, cok, bv);
             }
     };
-    if (has_res && has_mask) {     // dgrad with the pooled skip gradient folded in (gim_conv2d_dgrad_res): mask, then + res_scale * up2(res)
-        run(std::integral_constant<int, 4>());
-    } else if (has_res) {
-        if (p.res_ups) run(std::integral_constant<int, 2>());
-        else run(std::integral_constant<int, 1>());
-    } else if (has_mask) {
-        run(std::integral_constant<int, 3>());
-    } else {
-        run(std::integral_constant<int, 0>());
-    }
+    epi_dispatch<0, 0>(p, has_res, has_mask, run);
 }
 
 // -------------------------------------------------------------------------------------------------

@@ -281,6 +281,53 @@ __device__ __forceinline__ void epi_block(const EpiCtx& c, const float (&a)[NE],
     }
 }
 
+// Epilogue set-up shared by the forward-style kernels (fp32 and fp16, tap-major and patch-resident): scale, output geometry and the
+// three buffer resources from the launch and the kernel's (class-selected) geometry.  PLAIN: the patch-resident kernels' geometry
+// (logical pixel = stored pixel: os = 1, py = px = 0) as compile-time constants; PM: the kernel can run position-major rows (Geo.pm).
+// first: this workgroup's K slice is slice 0, the one that adds bias and residual.
+template <bool PLAIN, bool PM>
+__device__ __forceinline__ void epi_fill(EpiCtx& ec, const ConvP& p, const Geo& g, bool first, bool& has_res, bool& has_mask) {
+    ec.scale = p.out_scale * (p.sigma ? 1.0f / p.sigma[0] : 1.0f);
+    ec.mask_slope = p.mask_slope;
+    ec.post_slope = p.post_slope;
+    ec.res_scale = p.res_scale;
+    has_res = p.res != nullptr && first;   // block-uniform
+    has_mask = p.mask_x != nullptr;
+    ec.atom = p.ksplit > 1;
+    ec.remap = PLAIN ? false : g.os != 1;
+    ec.M = p.M; ec.Cb = p.Cb;
+    ec.logH = g.logH; ec.logW = g.logW; ec.Hm1 = g.H - 1; ec.Wm1 = g.W - 1;
+    ec.os = PLAIN ? 1 : g.os; ec.py = PLAIN ? 0 : g.py; ec.px = PLAIN ? 0 : g.px;
+    ec.Ho = g.H * ec.os; ec.Wo = g.W * ec.os;
+    ec.pmN = (PM && g.pm) ? g.N : 0;
+    if constexpr (PM) ec.pm_perm = g.pm_perm;
+    // y (and the mask, which has y's shape) in bytes: the host guarantees < 2 GiB per launch
+    const unsigned ybytes = (unsigned)g.N * (unsigned)ec.Ho * (unsigned)ec.Wo * (unsigned)p.Cb * 4u;
+    ec.ry = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, ybytes, 0x00020000);
+    ec.rr = __builtin_amdgcn_make_buffer_rsrc((void*)p.res, 0, has_res ? ((p.res_ups || has_mask) ? ybytes >> 2 : ybytes) : 0u, 0x00020000);
+    ec.rm = __builtin_amdgcn_make_buffer_rsrc((void*)p.mask_x, 0, has_mask ? ybytes : 0u, 0x00020000);
+}
+
+// The one epilogue mode of a launch, handed to the kernel's `run` (its loop over its accumulator blocks, which knows their layout) as a
+// compile-time constant.  EPI 1 (gim_conv2d_infer): mode 5 only - bias + per-channel PReLU, never split.  Each operand mode holds the
+// training modes its callers can ask for, and run_igemm refuses the others before anything is enqueued:
+//   BMODE 0 (forward, rows form, dgrad on transposed or x-folded weights): a residual comes without a mask - 0, 1, 2, 3
+//   BMODE 1 (k-major dgrad): a residual comes with the mask (gim_conv2d_dgrad_res, the only caller with one)  - 0, 3, 4
+template <int EPI, int BMODE, class Run>
+__device__ __forceinline__ void epi_dispatch(const ConvP& p, bool has_res, bool has_mask, Run&& run) {
+    if constexpr (EPI == 1) {
+        run(std::integral_constant<int, 5>());
+    } else if (has_res) {
+        if constexpr (BMODE == 1) run(std::integral_constant<int, 4>());   // mask, then + res_scale * up2(res): the pooled skip gradient folded in
+        else if (p.res_ups) run(std::integral_constant<int, 2>());
+        else run(std::integral_constant<int, 1>());
+    } else if (has_mask) {
+        run(std::integral_constant<int, 3>());
+    } else {
+        run(std::integral_constant<int, 0>());
+    }
+}
+
 // LDS bytes of the fp32 path's two double-buffered tiles (k-rows padded by 4 floats; the k-major B tile of BMODE 1 is unpadded)
 constexpr int igemm_lds_bytes(int BM, int BN, int KB, int BMODE) {
     return 2 * (BM * (KB + 4) + (BMODE == 0 ? BN * (KB + 4) : KB * BN)) * 4;
@@ -706,25 +753,9 @@ __global__ __launch_bounds__(256, igemm_lds_bytes(BM, BN, KB, BMODE) <= 40960 ? 
 
     // ---- epilogue: out_scale/sigma, bias, residual, activation mask; logical pixel -> stored pixel ----
     EpiCtx ec;
-    ec.pmN = 0;
-    ec.scale = p.out_scale * (p.sigma ? 1.0f / p.sigma[0] : 1.0f);
-    ec.mask_slope = p.mask_slope;
-    ec.post_slope = p.post_slope;
-    ec.res_scale = p.res_scale;
     const bool first = kslice == 0;
-    const bool has_res = p.res != nullptr && first, has_mask = p.mask_x != nullptr;   // block-uniform
-    ec.atom = p.ksplit > 1;
-    ec.remap = g.os != 1;
-    ec.M = p.M; ec.Cb = p.Cb;
-    ec.logH = g.logH; ec.logW = g.logW; ec.Hm1 = g.H - 1; ec.Wm1 = g.W - 1; ec.os = g.os; ec.py = g.py; ec.px = g.px;
-    ec.Ho = g.H * g.os; ec.Wo = g.W * g.os;
-    ec.pmN = g.pm ? g.N : 0;
-    ec.pm_perm = g.pm_perm;
-    // y (and the mask, which has y's shape) in bytes: the host guarantees < 2 GiB per launch
-    const unsigned ybytes = (unsigned)g.N * (unsigned)ec.Ho * (unsigned)ec.Wo * (unsigned)p.Cb * 4u;
-    ec.ry = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, ybytes, 0x00020000);
-    ec.rr = __builtin_amdgcn_make_buffer_rsrc((void*)p.res, 0, has_res ? ((p.res_ups || has_mask) ? ybytes >> 2 : ybytes) : 0u, 0x00020000);
-    ec.rm = __builtin_amdgcn_make_buffer_rsrc((void*)p.mask_x, 0, has_mask ? ybytes : 0u, 0x00020000);
+    bool has_res, has_mask;
+    epi_fill<false, true>(ec, p, g, first, has_res, has_mask);
     auto run = [&](auto MODEC) {
         constexpr int MODE = decltype(MODEC)::value;
         if constexpr (N16) {   // accumulator block i, register e: row 16*i + 4*q16 + e, column r16
@@ -753,18 +784,7 @@ __global__ __launch_bounds__(256, igemm_lds_bytes(BM, BN, KB, BMODE) <= 40960 ? 
                 }
         }
     };
-    if constexpr (EPI == 1) {      // gim_conv2d_infer: bias + per-channel PReLU, never split
-        run(std::integral_constant<int, 5>());
-    } else if (has_res && has_mask) {     // dgrad with the pooled skip gradient folded in (gim_conv2d_dgrad_res): mask, then + res_scale * up2(res)
-        run(std::integral_constant<int, 4>());
-    } else if (has_res) {
-        if (p.res_ups) run(std::integral_constant<int, 2>());
-        else run(std::integral_constant<int, 1>());
-    } else if (has_mask) {
-        run(std::integral_constant<int, 3>());
-    } else {
-        run(std::integral_constant<int, 0>());
-    }
+    epi_dispatch<EPI, BMODE>(p, has_res, has_mask, run);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -834,7 +854,7 @@ __global__ __launch_bounds__(256, TM * TN <= 2 ? 3 : 2) void conv_igemm_patch_ke
         for (int i = 0; i < P_PER; ++i) rp[i] = buf_load4(rx, p_voff[i], (unsigned)(c0 * 4));
     };
     int p_wr = 0;   // float offset of the patch buffer the next store_patch fills (alternates 0 / P_SZ)
-    auto store_patch = [&](int) __attribute__((always_inline)) {
+    auto store_patch = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < P_PER; ++i) {
             if (has_act) {
@@ -895,7 +915,7 @@ __global__ __launch_bounds__(256, TM * TN <= 2 ? 3 : 2) void conv_igemm_patch_ke
     const int ch1 = min(nchunk, ch0 + p.kper / 9);
     load_patch(ch0 * KB);
     load_b(0, 0, ch0 * KB);
-    store_patch(0);
+    store_patch();
     store_b(0);
     __syncthreads();
     // one K step: tap TAP of chunk ch (weight buffer BB: compile-time, the patch buffer is folded into a_row); prefetches the next
@@ -935,7 +955,7 @@ __global__ __launch_bounds__(256, TM * TN <= 2 ? 3 : 2) void conv_igemm_patch_ke
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk][i][e], b[kk][j][e], acc[i][j], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
         if (TAP < 8 || more_chunks) store_b(BB ^ 1);
-        if (TAP == 8 && more_chunks) store_patch(-1);
+        if (TAP == 8 && more_chunks) store_patch();
         __syncthreads();
     };
     int pbuf = 0;   // patch buffer of the chunk being computed
@@ -970,22 +990,9 @@ __global__ __launch_bounds__(256, TM * TN <= 2 ? 3 : 2) void conv_igemm_patch_ke
 
     // ---- epilogue (as conv_igemm_kernel) ----
     EpiCtx ec;
-    ec.pmN = 0;
-    ec.scale = p.out_scale * (p.sigma ? 1.0f / p.sigma[0] : 1.0f);
-    ec.mask_slope = p.mask_slope;
-    ec.post_slope = p.post_slope;
-    ec.res_scale = p.res_scale;
     const bool first = kslice == 0;
-    const bool has_res = p.res != nullptr && first, has_mask = p.mask_x != nullptr;
-    ec.atom = p.ksplit > 1;
-    ec.remap = false;
-    ec.M = p.M; ec.Cb = p.Cb;
-    ec.logH = g.logH; ec.logW = g.logW; ec.Hm1 = g.H - 1; ec.Wm1 = g.W - 1; ec.os = 1; ec.py = 0; ec.px = 0;
-    ec.Ho = g.H; ec.Wo = g.W;
-    const unsigned ybytes = (unsigned)g.N * (unsigned)g.H * (unsigned)g.W * (unsigned)p.Cb * 4u;
-    ec.ry = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, ybytes, 0x00020000);
-    ec.rr = __builtin_amdgcn_make_buffer_rsrc((void*)p.res, 0, has_res ? ((p.res_ups || has_mask) ? ybytes >> 2 : ybytes) : 0u, 0x00020000);
-    ec.rm = __builtin_amdgcn_make_buffer_rsrc((void*)p.mask_x, 0, has_mask ? ybytes : 0u, 0x00020000);
+    bool has_res, has_mask;
+    epi_fill<true, false>(ec, p, g, first, has_res, has_mask);
     auto run = [&](auto MODEC) {
         constexpr int MODE = decltype(MODEC)::value;
 #pragma unroll
@@ -1002,18 +1009,7 @@ __global__ __launch_bounds__(256, TM * TN <= 2 ? 3 : 2) void conv_igemm_patch_ke
                 else epi_block<16, MODE>(ec, a, m0 + wm0 + 32 * i + 4 * h, co, cok, bv);
             }
     };
-    if constexpr (EPI == 1) {      // gim_conv2d_infer: bias + per-channel PReLU, never split
-        run(std::integral_constant<int, 5>());
-    } else if (has_res && has_mask) {     // dgrad with the pooled skip gradient folded in (gim_conv2d_dgrad_res): mask, then + res_scale * up2(res)
-        run(std::integral_constant<int, 4>());
-    } else if (has_res) {
-        if (p.res_ups) run(std::integral_constant<int, 2>());
-        else run(std::integral_constant<int, 1>());
-    } else if (has_mask) {
-        run(std::integral_constant<int, 3>());
-    } else {
-        run(std::integral_constant<int, 0>());
-    }
+    epi_dispatch<EPI, BMODE>(p, has_res, has_mask, run);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1933,6 +1929,11 @@ template <int BMODE, int GEN>
 static int run_igemm(const ConvP& p, const IgemmPlan& q, size_t y_elems, hipStream_t st) {
     if (q.ksplit > 1 && p.post_slope != 1.f) {   // the K slices are combined by addition: no nonlinearity behind them
         gim_set_error("conv fwd: post_slope with a launch that splits K (ask gim_conv_launch_plan first)");
+        return GIM_E_BADARG;
+    }
+    if (p.res && (BMODE == 1) != (p.mask_x != nullptr)) {   // epi_dispatch: the kernels of an operand mode hold the epilogues its entry points reach
+        gim_set_error(BMODE == 0 ? "conv: residual and mask_x together on k-contiguous weights (the k-major dgrad has that epilogue)"
+                                 : "conv dgrad (k-major): a residual needs mask_x");
         return GIM_E_BADARG;
     }
     if (q.ksplit > 1 && !p.y_zeroed) (void)hipMemsetAsync(p.y, 0, y_elems * sizeof(float), st);

@@ -13,7 +13,7 @@ import torch.nn.functional as F
 
 from oracle import gim_oracle as go
 from oracle import portable_fill as pf
-from tests.helpers import T, relerr
+from tests.helpers import T, epi_case, epi_reference, relerr
 
 pytestmark = pytest.mark.gpu
 
@@ -147,6 +147,29 @@ def test_fp16_folded_conv_vs_fp64(case, fp16_path):
     print("fp16 folded conv vs fp64: y %.2e dx %.2e dw %.2e db %.2e" % errs)
     assert all(e < TOL_ROUND for e in errs[:3]) and errs[3] < TOL, errs
     assert errs[0] > 1e-6, "the fp16 path did not run"
+
+
+# The fp16 rows of test_gpu_ops.test_conv_epilogue_modes_per_kernel_family: both fp16 kernels report loop form 2; the map decides between
+# them by the plain3x3 condition of plan_igemm (csrc/conv_igemm.hip) - 4 x 4 = 16 pixels: tap-major, 8 x 8 = 64 pixels: patch-resident.
+# Modes 4 (gim_conv2d_dgrad_res: k-major weights) and 5 (inference entry) exist on the fp32 kernels only.  The patch-resident loop splits
+# K in whole 32-channel chunks, so its split row has 64 input channels.
+F16_EPI_FAMILIES = {
+    # name: (N, S, Cin, Cout)
+    "f16_tap": (2, 4, 32, 64),
+    "f16_patch": (2, 8, 32, 64),
+    "f16_patch_cols96": (2, 8, 32, 96),
+    "f16_patch_rows192": (3, 8, 32, 64),
+}
+F16_EPI_SPLIT = {"f16_tap": (2, 4, 32, 64), "f16_patch_cin64": (2, 8, 64, 64)}   # the forced K split: two 32-channel chunks for the patch loop
+F16_EPI_CASES = ([(f, m, c) for f, c in F16_EPI_FAMILIES.items() for m in ("0_bias", "1_res", "2_res_half", "3_mask")]
+                 + [(f, "split_k", c) for f, c in F16_EPI_SPLIT.items()])
+
+
+@pytest.mark.parametrize("family,mode,case", F16_EPI_CASES, ids=["%s-%s" % c[:2] for c in F16_EPI_CASES])
+def test_fp16_conv_epilogue_modes_per_kernel_family(family, mode, case, fp16_path):
+    """Epilogue modes 0-3 and a forced K split on the two fp16 forward-style kernels, against fp64 on fp16-rounded operands (TOL)."""
+    N, S, Cin, Cout = case
+    epi_case(fp16_path, family, mode, family, N, S, Cin, Cout, 2, False, epi_reference(family, N, S, Cin, Cout, r16), TOL)
 
 
 def test_fp16_path_leaves_ineligible_launches_on_fp32(fp16_path):

@@ -7,7 +7,7 @@ import torch.nn.functional as F
 
 from oracle import gim_oracle as go
 from oracle import portable_fill as pf
-from tests.helpers import T, relerr, relerr_floor
+from tests.helpers import T, epi_case, epi_reference, relerr, relerr_floor
 
 pytestmark = pytest.mark.gpu
 
@@ -377,6 +377,30 @@ def test_conv_with_pooled_skip_reader_one_autograd_node(N, Cin, Cout, K, H, x_ac
         assert relerr(wg.grad.double().cpu(), w.grad) < TOL and relerr(bg.grad.double().cpu(), b.grad) < TOL, fused
         outs.append(xin.grad)
     assert relerr(outs[0], outs[1]) < 1e-6
+
+
+# Kernel family x epilogue mode (csrc/conv_igemm.hip: epi_fill / epi_dispatch / epi_block behind four K loops), at the smallest shapes
+# that reach each family: 32 -> 64 channels (one row of 96: ragged tile columns), 3 x 3.
+EPI_FAMILIES = {
+    # name: (N, S, Cin, Cout, loop form of the plan, position-major rows)
+    "tap": (2, 4, 32, 64, 0, False),               # a 4 x 4 map: below the 64 pixels the patch-resident form needs
+    "tap_pm": (32, 4, 32, 64, 0, True),            # >= 32 images of <= 16 pixels: position-major rows
+    "patch": (2, 8, 32, 64, 1, False),
+    "patch_cols96": (2, 8, 32, 96, 1, False),      # ragged tile columns
+    "patch_rows192": (3, 8, 32, 64, 1, False),     # 192 rows: ragged tile rows where the plan picks 128-row tiles
+}
+EPI_MODES = ["0_bias", "1_res", "2_res_half", "3_mask", "4_mask_res_half", "5_prelu", "split_k"]
+@pytest.mark.parametrize("mode", EPI_MODES)
+@pytest.mark.parametrize("family", list(EPI_FAMILIES))
+def test_conv_epilogue_modes_per_kernel_family(family, mode):
+    """Every epilogue mode on every fp32 forward-style kernel family against fp64 F.conv2d (tolerance of test_conv2d_fwd_bwd): 0 bias,
+    1 residual, 2 half-resolution residual (forward output); 3 mask, 4 mask + pooled skip gradient (x.grad; 4 through
+    ops.conv2d_forkpool -> gim_conv2d_dgrad_res, k-major weights only); 5 per-channel PReLU (ops.conv2d_infer); a forward forced to split
+    K in two (atomic epilogue).  The launch plan is asserted first, so that a planner change cannot turn the matrix into copies of one
+    kernel.  (The fp16 rows are in test_gpu_fp16.py.)"""
+    from optimalstrategiesagainstgenerativeattacks_amd import ops
+    N, S, Cin, Cout, form, pm = EPI_FAMILIES[family]
+    epi_case(ops, family, mode, family, N, S, Cin, Cout, form, pm, epi_reference(family, N, S, Cin, Cout), TOL)
 
 
 def test_linear_fwd_bwd():
