@@ -1,4 +1,6 @@
 """Shared test helpers: portable-fill state dicts / episodes as torch tensors."""
+import collections
+import contextlib
 import json
 import os
 
@@ -140,3 +142,284 @@ def epi_case(ops, family, mode, name, N, S, Cin, Cout, form, pm, ref, tol):
     finally:
         ops._TUNE_OVERRIDE.clear()
         ops._SPLITS_K.clear()
+
+
+# ---- one convolution through ops.conv2d against fp64 F.conv2d autograd (test_gpu_ops.py, test_gpu_fp16.py, test_gpu_rect_maps.py) ----
+class _RoundOperand(torch.autograd.Function):
+    """rnd(t) going forward, the identity going back: an operand the kernel rounds when it stages it."""
+
+    @staticmethod
+    def forward(ctx, t, rnd):
+        return rnd(t)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None
+
+
+class _RoundCotangent(torch.autograd.Function):
+    """The identity going forward, rnd(g) going back: the gradient kernels round the incoming gradient the same way."""
+
+    @staticmethod
+    def forward(ctx, t, rnd):
+        ctx.rnd = rnd
+        return t.view_as(t)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.rnd(g), None
+
+
+@contextlib.contextmanager
+def tune_override(ops, g, tune):
+    """ops._TUNE_OVERRIDE rows {launch kind: (tile code, split)} for the calls of geometry g, taken back on the way out."""
+    for kind, ov in (tune or {}).items():
+        ops._TUNE_OVERRIDE[(kind, g.key)] = ov
+    ops._SPLITS_K.clear()
+    try:
+        yield
+    finally:
+        ops._TUNE_OVERRIDE.clear()
+        ops._SPLITS_K.clear()
+
+
+_CONV_REF = {}
+
+
+def _conv_reference(tag, N, HW, Cin, Cout, K, ups, pool, slope, res, sig, rnd):
+    """(x, w, b, res, y, dy) of conv_fwd_bwd in fp64, NCHW, the leaves holding their gradients of sum(y * dy)."""
+    import torch.nn.functional as F
+    from oracle import gim_oracle as go
+    H, W = (HW, HW) if isinstance(HW, int) else HW
+    x = T(pf.normal(tag + "x", (N, Cin, H >> ups, W >> ups))).requires_grad_()
+    w = T(pf.normal(tag + "w", (Cout, Cin, K, K)) / np.sqrt(Cin * K * K)).requires_grad_()
+    b = T(pf.normal(tag + "b", (Cout,))).requires_grad_()
+    xa = F.leaky_relu(x, slope) if slope != 1.0 else x
+    wr = w
+    if rnd is not None:
+        xa, wr = _RoundOperand.apply(xa, rnd), _RoundOperand.apply(w, rnd)
+    if ups:
+        xa = go.upsample2(xa)
+    y = F.conv2d(xa, wr / (sig or 1.0), None, padding=(K - 1) // 2)
+    if pool:
+        y = F.avg_pool2d(y, 2)
+    if rnd is not None:
+        y = _RoundCotangent.apply(y, rnd)
+    y = y + b.view(1, -1, 1, 1)
+    r_ = None
+    if res:
+        r_ = T(pf.normal(tag + "r", (N, Cout, y.shape[2] >> (res == 2), y.shape[3] >> (res == 2)))).requires_grad_()
+        y = y + (go.upsample2(r_) if res == 2 else r_)
+    dy = T(pf.uniform(tag + "dy", tuple(y.shape)))
+    (y * dy).sum().backward()
+    return x, w, b, r_, y.detach(), dy
+
+
+def conv_fwd_bwd(ops, tag, N, HW, Cin, Cout, K, ups=0, pool=False, slope=1.0, res=0, sig=None, tol=3e-5, pre=None, tune=None, rnd=None, keep_ref=False):
+    """y = [avgpool2](conv(up2^ups(lrelu(x)), w / sig)) + bias [+ res] through ops.conv2d - y, dx, dw, db, dres against fp64 autograd of
+    F.conv2d.  HW: the map of the unfused convolution, one int (square) or (H, W).  res: 0 none, 1 at the output's resolution, 2 at half
+    of it (res_ups).  sig: None, or sigma with u = v = 0 (the plain 1 / sigma scaling of the weight gradient; the spectral term is
+    test_sn_conv_sequence's).  pre: weight and bias own .grad buffers holding this value (the optimizer's bucket), so that the weight
+    gradient goes through the queue and is ADDED there.  tune: launch overrides (tune_override).  rnd: the operand rounding of the fp16
+    path - the reference then convolves rnd(lrelu(x)) with rnd(w) and takes the conv's gradients from rnd(dy).  tol: one bound, or one
+    per compared tensor.  keep_ref: the reference of `tag` is kept for the next call (the same case run another way).  Every error is
+    printed before the first is asserted; returns them."""
+    ref = _CONV_REF.get(tag)
+    if ref is None:
+        ref = _conv_reference(tag, N, HW, Cin, Cout, K, ups, pool, slope, res, sig, rnd)
+        if keep_ref:
+            _CONV_REF[tag] = ref
+    x, w, b, r_, y, dy = ref
+
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    dev = torch.device("cuda:0")
+    nhwc = lambda t: t.detach().permute(0, 2, 3, 1).contiguous().float().to(dev)     # NCHW cpu f64 -> NHWC cuda f32
+    nchw = lambda t: t.detach().permute(0, 3, 1, 2).double().cpu()
+    xg = nhwc(x).requires_grad_()
+    wg = w.detach().float().to(dev).contiguous(memory_format=torch.channels_last).requires_grad_()
+    bg = b.detach().float().to(dev).requires_grad_()
+    rg = nhwc(r_).requires_grad_() if res else None
+    sg = torch.tensor([sig], device=dev) if sig else None
+    errs = {}
+    with tune_override(ops, ops.ConvGeom.of(xg, wg, ups, slope, pool, res == 2, bg, rg, False), tune):
+        yg = ops.conv2d(xg, wg, bg, rg, sg, None, None, ups, slope, pool, res == 2)
+        errs["y"] = relerr(nchw(yg), y)
+        # sigma given without u/v: the spectral term of the weight gradient is skipped only when sigma is None, so
+        # feed u = 0 to test the plain 1/sigma scaling of wgrad here
+        if sig:
+            yg = ops.conv2d(xg, wg, bg, rg, sg, torch.zeros(Cout, device=dev), torch.zeros(Cin * K * K, device=dev), ups, slope, pool, res == 2)
+        if pre is not None:
+            wg.grad = torch.full_like(wg, pre)       # channels-last like the parameter: the bucket's memory order
+            bg.grad = torch.full_like(bg, pre)
+        (yg * nhwc(dy)).sum().backward()
+    assert not ops.wgrad_queue.jobs, "the queue was flushed at the end of backward"
+    errs["dx"] = relerr(nchw(xg.grad), x.grad)
+    errs["dw"] = relerr((wg.grad - (pre or 0.0)).double().cpu(), w.grad)
+    errs["db"] = relerr((bg.grad - (pre or 0.0)).double().cpu(), b.grad)
+    if res:
+        errs["dres"] = relerr(nchw(rg.grad), r_.grad)
+    print("conv_fwd_bwd %s: %s" % (tag, " ".join("%s %.2e" % kv for kv in errs.items())))
+    for k_, e in errs.items():
+        assert e < (tol[k_] if isinstance(tol, dict) else tol), (k_, e)
+    return errs
+
+
+# ---- convolutions on maps with H != W (test_host.py asserts the plans on the CPU, test_gpu_rect_maps.py the numbers) ----
+# geom = (N, H, W, Cin, Cout, K, ups, pool, slope, res) as conv_fwd_bwd reads them; tune: tune_override rows or None.
+# plan: what the row is there to reach, per launch the library plans - "fwd" gim_conv2d_fwd, "dgrad" gim_conv2d_dgrad or "dgrad_t"
+# gim_conv2d_dgrad_t (whichever ops._dgrad_route takes), "wgrad" gim_conv2d_wgrad_acc - as (loop form, tile rows, tile columns, skipped
+# share of the K steps in 1/1000: > 0 = position-major rows), and "route" = (ops._fwd_route, ops._dgrad_route, its J).  A launch that has
+# no plan kind (the "rows" and "subpixel" forwards with their weight gradients, the x-folded dgrad) has no entry.
+RectCase = collections.namedtuple("RectCase", "name geom tune plan")
+
+
+def rect_geom(ops, case):
+    N, H, W, Cin, Cout, K, ups, pool, slope, res = case.geom
+    return ops.ConvGeom.make(N, H, W, Cin, Cout, K, ups, slope, bool(pool), res == 2, True, res != 0)
+
+
+def rect_plan(ops, case):
+    """The plan of one row as the library and the route functions give it now, in the form of RectCase.plan."""
+    g = rect_geom(ops, case)
+
+    def row(kind, code):
+        p = epi_plan(g.shape(kind), code)
+        return (p[7] & 0xff, p[1], p[2], p[7] >> 8)
+    with tune_override(ops, g, case.tune):
+        sh = g.shape("fwd")
+        fwd = ops._fwd_route(g, sh.tune_tile)
+        dgrad, J, _ = ops._dgrad_route(g, sh.prec, True)
+        out = {"route": (fwd, dgrad, J)}
+        if fwd == "plain":
+            out["fwd"] = row("fwd", 0)
+        if dgrad != "xfold":
+            out["dgrad_t" if dgrad == "t" else "dgrad"] = row("dgrad", 2 if dgrad == "t" else 1)
+        if fwd == "plain":
+            out["wgrad"] = row("wgrad", 3)
+    return out
+
+
+def _rc(name, geom, plan, tune=None):
+    return RectCase(name, geom, tune, plan)
+
+
+RECT_CASES = [
+    # tap-major loop, image-major rows: a map below the 64 pixels of the patch-resident kernel
+    _rc("tap_4x8", (2, 4, 8, 32, 64, 3, 0, 0, 0.2, 1),
+        dict(route=("plain", "plain", 0), fwd=(0, 64, 64, 0), dgrad=(0, 128, 32, 0), wgrad=(0, 64, 128, 0))),
+    _rc("tap_8x4", (2, 8, 4, 32, 64, 3, 0, 0, 0.2, 2),
+        dict(route=("plain", "plain", 0), fwd=(0, 64, 64, 0), dgrad=(0, 128, 32, 0), wgrad=(0, 64, 128, 0))),
+    # position-major rows (>= 32 images, <= 16 pixels): pm_perm_of orders the pixels of 2 x 8 and 8 x 2 differently
+    _rc("pm_2x8", (32, 2, 8, 32, 64, 3, 0, 0, 0.2, 1),
+        dict(route=("plain", "plain", 0), fwd=(0, 128, 64, 333), dgrad=(0, 128, 32, 333), wgrad=(0, 64, 128, 0))),
+    _rc("pm_8x2", (32, 8, 2, 32, 64, 3, 0, 0, 0.2, 0),
+        dict(route=("plain", "plain", 0), fwd=(0, 128, 64, 194), dgrad=(0, 128, 32, 194), wgrad=(0, 64, 128, 0))),
+    _rc("pm_1x16", (40, 1, 16, 32, 48, 3, 0, 0, 0.2, 0),  # one tap row valid, ragged output channels
+        dict(route=("plain", "plain", 0), fwd=(0, 128, 64, 667), dgrad=(0, 128, 32, 667), wgrad=(0, 64, 128, 0))),
+    _rc("pm_16x1", (40, 16, 1, 32, 48, 3, 0, 0, 1.0, 1),  # one tap column valid
+        dict(route=("plain", "plain", 0), fwd=(0, 128, 64, 667), dgrad=(0, 128, 32, 667), wgrad=(0, 64, 128, 0))),
+    _rc("pm_1x4", (33, 1, 4, 16, 32, 3, 0, 0, 0.2, 0),  # 128 x 32 tile
+        dict(route=("plain", "plain", 0), fwd=(0, 128, 32, 667), dgrad=(0, 128, 16, 667), wgrad=(0, 32, 128, 0))),
+    # patch-resident loop: Wt = min(W, BM) pixels of BM / Wt + 2 patch rows
+    _rc("patch_4x16", (2, 4, 16, 32, 64, 3, 0, 0, 0.2, 1),
+        dict(route=("plain", "plain", 0), fwd=(1, 64, 64, 0), dgrad=(1, 64, 64, 0), wgrad=(0, 64, 128, 0))),
+    _rc("patch_16x4", (2, 16, 4, 32, 64, 3, 0, 0, 0.2, 2),
+        dict(route=("plain", "plain", 0), fwd=(1, 64, 64, 0), dgrad=(1, 64, 64, 0), wgrad=(0, 64, 128, 0))),
+    _rc("patch_32x2", (2, 32, 2, 32, 64, 3, 0, 0, 0.2, 0),  # the narrowest legal width
+        dict(route=("plain", "plain", 0), fwd=(1, 64, 64, 0), dgrad=(1, 64, 64, 0), wgrad=(0, 64, 128, 0))),
+    _rc("patch_2x32", (2, 2, 32, 32, 64, 3, 0, 0, 1.0, 1),
+        dict(route=("plain", "plain", 0), fwd=(1, 64, 64, 0), dgrad=(1, 64, 64, 0), wgrad=(0, 64, 128, 0))),
+    _rc("patch_2x128", (1, 2, 128, 32, 64, 3, 0, 0, 0.2, 0),  # a tile is half an image row
+        dict(route=("plain", "plain", 0), fwd=(1, 64, 64, 0), dgrad=(1, 64, 64, 0), wgrad=(0, 64, 128, 0))),
+    _rc("patch_128x2", (1, 128, 2, 32, 64, 3, 0, 0, 0.2, 1),  # whole-row tiles at W = 2: 128 x 64
+        dict(route=("plain", "plain", 0), fwd=(1, 128, 64, 0), dgrad=(1, 128, 64, 0), wgrad=(0, 64, 128, 0))),
+    _rc("patch_1x64", (2, 1, 64, 32, 64, 3, 0, 0, 0.2, 0),  # H = 1: two of three patch rows out of range
+        dict(route=("plain", "plain", 0), fwd=(1, 64, 64, 0), dgrad=(1, 64, 64, 0), wgrad=(0, 64, 128, 0))),
+    _rc("tap_64x1", (2, 64, 1, 32, 64, 3, 0, 0, 0.2, 0),  # W = 1: the patch kernel is not allowed there
+        dict(route=("plain", "plain", 0), fwd=(0, 128, 64, 0), dgrad=(0, 128, 32, 0), wgrad=(0, 64, 128, 0))),
+    # 128-row patch tiles on request (tile code + 20000), one K slice
+    _rc("forced_20128_64x2", (3, 64, 2, 32, 160, 3, 0, 0, 0.2, 0),
+        dict(route=("plain", "plain", 0), fwd=(1, 128, 128, 0), dgrad=(1, 128, 64, 0), wgrad=(0, 128, 128, 0)), tune={"fwd": (20128, 1)}),
+    _rc("forced_20641_64x2", (3, 64, 2, 32, 160, 3, 0, 0, 0.2, 1),
+        dict(route=("plain", "plain", 0), fwd=(1, 64, 128, 0), dgrad=(1, 128, 64, 0), wgrad=(0, 128, 128, 0)), tune={"fwd": (20641, 1)}),
+    _rc("forced_20128_4x64", (3, 4, 64, 32, 160, 3, 0, 0, 0.2, 0),
+        dict(route=("plain", "plain", 0), fwd=(1, 128, 128, 0), dgrad=(1, 128, 64, 0), wgrad=(0, 128, 128, 0)), tune={"fwd": (20128, 1)}),
+    _rc("forced_21264_64x2", (3, 64, 2, 32, 64, 3, 0, 0, 0.2, 0),
+        dict(route=("plain", "plain", 0), fwd=(1, 128, 64, 0), dgrad=(1, 128, 64, 0), wgrad=(0, 64, 128, 0)), tune={"fwd": (21264, 1)}),
+    # generic K: Cin not a multiple of 16
+    _rc("genk_4x16", (2, 4, 16, 24, 64, 3, 0, 0, 0.2, 0),
+        dict(route=("plain", "plain", 0), fwd=(0, 128, 64, 0), dgrad=(0, 128, 32, 0), wgrad=(0, 64, 128, 0))),
+    _rc("genk_16x4", (2, 16, 4, 24, 40, 3, 0, 0, 0.2, 1),
+        dict(route=("plain", "plain", 0), fwd=(0, 128, 64, 0), dgrad=(0, 128, 32, 0), wgrad=(0, 64, 128, 0))),
+    # pool fold: stride-2 gather on the logical grid H/2 x W/2
+    _rc("pool_8x16", (2, 8, 16, 32, 64, 3, 0, 1, 0.2, 1),
+        dict(route=("plain", "plain", 0), fwd=(0, 64, 64, 0), dgrad=(0, 128, 32, 0), wgrad=(0, 64, 128, 0))),
+    _rc("pool_16x8", (2, 16, 8, 32, 64, 3, 0, 1, 0.2, 0),
+        dict(route=("plain", "plain", 0), fwd=(0, 64, 64, 0), dgrad=(0, 128, 32, 0), wgrad=(0, 64, 128, 0))),
+    _rc("pool_2x16", (2, 2, 16, 64, 64, 3, 0, 1, 0.2, 1),  # output 1 x 8
+        dict(route=("plain", "plain", 0), fwd=(0, 64, 64, 0), dgrad=(0, 64, 64, 0), wgrad=(0, 64, 128, 0))),
+    _rc("pool_16x2_1x1", (2, 16, 2, 64, 64, 1, 0, 1, 1.0, 0),  # output 8 x 1
+        dict(route=("plain", "plain", 0), fwd=(0, 64, 64, 0), dgrad=(0, 64, 64, 0), wgrad=(0, 64, 128, 0))),
+    _rc("pool_pm_4x8", (40, 4, 8, 32, 32, 3, 0, 1, 0.2, 1),
+        dict(route=("plain", "plain", 0), fwd=(0, 128, 32, 167), dgrad=(0, 128, 32, 125), wgrad=(0, 32, 128, 0))),
+    _rc("pool_pm_8x4", (40, 8, 4, 32, 32, 3, 0, 1, 0.2, 0),
+        dict(route=("plain", "plain", 0), fwd=(0, 128, 32, 104), dgrad=(0, 128, 32, 125), wgrad=(0, 32, 128, 0))),
+    # sub-pixel form: four parity classes on the low-resolution grid H/2 x W/2
+    _rc("subpix_8x16", (3, 8, 16, 32, 64, 3, 1, 0, 0.2, 1),
+        dict(route=("plain", "plain", 0), fwd=(0, 128, 64, 0), dgrad=(0, 128, 32, 0), wgrad=(0, 32, 128, 0))),
+    _rc("subpix_16x8", (3, 16, 8, 32, 64, 3, 1, 0, 0.2, 2),
+        dict(route=("plain", "plain", 0), fwd=(0, 128, 64, 0), dgrad=(0, 128, 32, 0), wgrad=(0, 32, 128, 0))),
+    _rc("subpix_pm_4x8", (33, 4, 8, 32, 64, 3, 1, 0, 0.2, 0),
+        dict(route=("plain", "plain", 0), fwd=(0, 128, 64, 125), dgrad=(0, 128, 32, 167), wgrad=(0, 32, 128, 0))),
+    _rc("subpix_pm_8x4", (33, 8, 4, 32, 64, 3, 1, 0, 0.2, 1),
+        dict(route=("plain", "plain", 0), fwd=(0, 128, 64, 125), dgrad=(0, 128, 32, 104), wgrad=(0, 32, 128, 0))),
+    _rc("subpix_9x9_2x16", (2, 2, 16, 16, 16, 9, 1, 0, 1.0, 1),  # low resolution 1 x 8
+        dict(route=("plain", "plain", 0), fwd=(0, 128, 16, 0), dgrad=(0, 128, 16, 0), wgrad=(0, 32, 128, 0))),
+    _rc("ups_1x1_8x2", (4, 8, 2, 32, 16, 1, 1, 0, 1.0, 0),  # 1x1 behind the upsample
+        dict(route=("plain", "ups", 0), fwd=(0, 128, 16, 0), dgrad=(0, 128, 32, 0), wgrad=(0, 32, 128, 0))),
+    # image layers: "rows" forward on the padded copy, x-folded dgrad where J divides W
+    _rc("img_16x4", (3, 16, 4, 3, 64, 3, 0, 0, 0.2, 0),  # J = 4 = W
+        dict(route=("rows", "xfold", 4))),
+    _rc("img_4x32_9x9", (2, 4, 32, 6, 64, 9, 0, 0, 0.2, 0),
+        dict(route=("rows", "xfold", 4))),
+    _rc("img_8x16_c8", (2, 8, 16, 8, 32, 3, 0, 0, 0.2, 0),  # J = 2
+        dict(route=("rows", "xfold", 2))),
+    _rc("img_32x2", (3, 32, 2, 3, 64, 3, 0, 0, 0.2, 0),  # J does not divide W: transposed-weight dgrad
+        dict(route=("rows", "t", 0), dgrad_t=(0, 128, 16, 0))),
+    _rc("img_8x1", (2, 8, 1, 3, 64, 3, 0, 0, 1.0, 0),
+        dict(route=("rows", "t", 0), dgrad_t=(0, 128, 16, 0))),
+    _rc("img_out_16x8_9x9", (2, 16, 8, 64, 3, 9, 1, 0, 0.2, 0),  # stacked parity classes + depth-to-space
+        dict(route=("subpixel", "plain", 0), dgrad=(0, 64, 64, 0))),
+]
+RECT_IDS = [c.name for c in RECT_CASES]
+
+# Direct gim_conv2d_wgrad_acc calls on the row-resident weight gradient (tile code 20000; N, H, W, Cin, Cout, loop form of the plan):
+# form 1 = the row-resident kernel in 128 x 96 tiles, rows of min(W, 16) pixels; form 0 = refused (W < 4: its narrowest instantiation walks
+# rows of 4 pixels), the MFMA kernel runs instead.
+RECT_WGRAD_ROW_CASES = [
+    (5, 4, 16, 32, 128, 1),      # three slices of 112 pixels: they end inside an image
+    (5, 16, 4, 32, 128, 1),
+    (9, 2, 8, 32, 128, 1),       # two image rows per step
+    (3, 1, 16, 32, 128, 1),
+    (3, 64, 4, 32, 128, 1),
+    (3, 4, 64, 64, 128, 1),
+    (2, 2, 64, 32, 128, 1),
+    (2, 1, 128, 32, 128, 1),
+    (9, 8, 2, 32, 128, 0),       # H * W >= 16 with W = 2
+    (3, 16, 1, 32, 128, 0),
+]
+
+
+def rect_wgrad_row_shape(case):
+    from optimalstrategiesagainstgenerativeattacks_amd import _lib
+    N, H, W, Cin, Cout, _ = case
+    return _lib.GimConvShape(N, H, W, Cin, Cout, 3, 0, 0.2, 0, 0, 0, 20000, 0, 0)
+
+
+def assert_rect_wgrad_row_plan(case):
+    N, H, W, Cin, Cout, form = case
+    plan = epi_plan(rect_wgrad_row_shape(case), 3)
+    if form == 1:
+        assert plan[7] == 1 and plan[1:3] == [128, 96] and plan[4] == 3 * (Cin // 32) and plan[5] == Cout // 128, (case, plan)
+    else:
+        assert plan[7] == 0 and plan[1:3] != [128, 96], (case, plan)

@@ -7,7 +7,7 @@ import torch.nn.functional as F
 
 from oracle import gim_oracle as go
 from oracle import portable_fill as pf
-from tests.helpers import T, epi_case, epi_reference, relerr, relerr_floor
+from tests.helpers import T, conv_fwd_bwd, epi_case, epi_reference, relerr, relerr_floor
 
 pytestmark = pytest.mark.gpu
 
@@ -83,41 +83,7 @@ POOL_CASES = [
 def test_conv2d_fwd_bwd(case):
     from optimalstrategiesagainstgenerativeattacks_amd import ops
     N, Cin, Cout, K, H, ups, slope, use_res, use_sigma = case
-    tag = "conv%s" % (case,)
-    Hs = H >> ups
-    x = T(pf.normal(tag + "x", (N, Cin, Hs, Hs))).requires_grad_()
-    w = T(pf.normal(tag + "w", (Cout, Cin, K, K)) / np.sqrt(Cin * K * K)).requires_grad_()
-    b = T(pf.normal(tag + "b", (Cout,))).requires_grad_()
-    res = T(pf.normal(tag + "r", (N, Cout, H, H))).requires_grad_() if use_res else None
-    sig = 1.7 if use_sigma else 1.0
-    xa = F.leaky_relu(x, slope) if slope != 1.0 else x
-    if ups:
-        xa = go.upsample2(xa)
-    y = F.conv2d(xa, w / sig, b, padding=(K - 1) // 2)
-    if use_res:
-        y = y + res
-    r = T(pf.uniform(tag + "dy", tuple(y.shape)))
-    (y * r).sum().backward()
-
-    xg = nhwc(x).requires_grad_()
-    wg = cl_weight(w)
-    bg = b.detach().float().to(dev()).requires_grad_()
-    rg = nhwc(res).requires_grad_() if use_res else None
-    sg = torch.tensor([sig], device=dev()) if use_sigma else None
-    yg = ops.conv2d(xg, wg, bg, rg, sg, None, None, ups, slope)
-    assert relerr(nchw(yg), y) < TOL
-    # sigma given without u/v: the spectral term of the weight gradient is skipped only when sigma is None, so
-    # feed u = 0 to test the plain 1/sigma scaling of wgrad here (the spectral term is covered by test_sn_conv)
-    if use_sigma:
-        u0 = torch.zeros(Cout, device=dev())
-        v0 = torch.zeros(Cin * K * K, device=dev())
-        yg = ops.conv2d(xg, wg, bg, rg, sg, u0, v0, ups, slope)
-    (yg * nhwc(r)).sum().backward()
-    assert relerr(nchw(xg.grad), x.grad) < TOL, "dx"
-    assert relerr(wg.grad.double().cpu(), w.grad) < TOL, "dw"
-    assert relerr(bg.grad.double().cpu(), b.grad) < TOL, "db"
-    if use_res:
-        assert relerr(nchw(rg.grad), res.grad) < TOL, "dres"
+    conv_fwd_bwd(ops, "conv%s" % (case,), N, H, Cin, Cout, K, ups, False, slope, 1 if use_res else 0, 1.7 if use_sigma else None, TOL)
 
 
 TINY_CASES = [

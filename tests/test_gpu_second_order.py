@@ -240,19 +240,24 @@ CONV_CASES = [
     (40, 8, 32, 32, 3, 0.2, True, True, False, True),       # 8x8 -> pooled 4x4
     (36, 4, 16, 48, 3, 0.2, True, False, True, True),       # 4x4 -> pooled 2x2, x_act
     (32, 2, 64, 64, 1, 1.0, True, False, False, False),     # 2x2 -> pooled 1x1, 1x1 skip (no padding taps to skip)
+    # maps with H != W, given as (H, W)
+    (2, (4, 16), 32, 48, 3, 0.2, False, False, False, False),    # patch-resident loop in the second-order forward
+    (40, (2, 8), 32, 48, 3, 0.2, False, False, False, True),     # position-major rows
+    (2, (16, 8), 32, 64, 3, 0.2, True, False, False, False),     # pool fold: 16x8 -> 8x4
 ]
 
 
 def conv_case(N, H, Cin, Cout, K, slope, pool, use_res, x_act, pm):
     tag = "so_conv%s" % ((N, H, Cin, Cout, K, slope, pool, use_res, x_act),)
-    x = T(pf.normal(tag + "x", (N, H, H, Cin)))
+    H, W = (H, H) if isinstance(H, int) else H       # one side of a square map, or (H, W)
+    x = T(pf.normal(tag + "x", (N, H, W, Cin)))
     w = T(pf.normal(tag + "w", (Cout, Cin, K, K)) / np.sqrt(Cin * K * K))
     b = T(pf.normal(tag + "b", (Cout,)))
     sigma, u, v = _sn_state(w, tag)
-    Ho = H // 2 if pool else H
+    Ho, Wo = (H // 2, W // 2) if pool else (H, W)
     ins = {"x": x, "w": w, "b": b, "sigma": sigma, "u": u, "v": v}
     if use_res:
-        ins["res"] = T(pf.normal(tag + "r", (N, Ho, Ho, Cout)))
+        ins["res"] = T(pf.normal(tag + "r", (N, Ho, Wo, Cout)))
 
     def fwd_r(t):
         return (_ref_conv(t["x"], t["w"], t["b"], t.get("res"), t["u"], t["v"], slope, pool),)
@@ -283,7 +288,7 @@ def test_conv2d_double_backward(case, form, queued):
     if pm:
         # the second-order forward launch (the forward kernel on the masked cotangent: bias None, pre_slope 1) runs position-major
         # rows and skips the padding taps (launch plan out[7] bits 8 and up: the skipped share of the K steps)
-        assert _plan(N, H, H, Cin, Cout, K, pool, 0)[7] >> 8 > 0, ("second-order forward is not position-major", case)
+        assert _plan(N, *ins["x"].shape[1:3], Cin, Cout, K, pool, 0)[7] >> 8 > 0, ("second-order forward is not position-major", case)
 
 
 def _g0(ins, tag):

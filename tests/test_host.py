@@ -755,3 +755,31 @@ def test_conv_geom_derived_values_and_activated_storage():
         assert not ops._SPLITS_K
     finally:
         ops.set_deterministic(prev)
+
+
+def test_rect_cases_reach_the_kernel_families_they_name():
+    """tests/helpers.py RECT_CASES (the GPU parity cases on maps with H != W, tests/test_gpu_rect_maps.py): every row plans the loop
+    form, tile and row order it records, per launch kind, and takes the host routes it records - so a heuristic change cannot quietly
+    turn the rectangles into copies of one kernel family.  Rows that force a tile ask for one K slice and get it."""
+    from optimalstrategiesagainstgenerativeattacks_amd import ops
+    from tests.helpers import RECT_CASES, RECT_WGRAD_ROW_CASES, assert_rect_wgrad_row_plan, epi_plan, rect_geom, rect_plan, tune_override
+    assert len({c.name for c in RECT_CASES}) == len(RECT_CASES) >= 39
+    bad = []
+    for c in RECT_CASES:
+        assert c.geom[1] != c.geom[2], c.name
+        got = rect_plan(ops, c)
+        if got != c.plan:
+            bad.append((c.name, got, c.plan))
+        g = rect_geom(ops, c)
+        with tune_override(ops, g, c.tune):
+            for kind, (_, split) in (c.tune or {}).items():
+                assert epi_plan(g.shape(kind), {"fwd": 0, "dgrad": 1}[kind])[3] == split, c.name
+    assert not bad, bad
+    assert not ops._TUNE_OVERRIDE
+    # every family the table is there for is reached: tap-major image-major and position-major, patch-resident in its four tiles
+    fwd = {c.plan["fwd"] for c in RECT_CASES if "fwd" in c.plan}
+    assert {(1, 64, 64, 0), (1, 128, 64, 0), (1, 64, 128, 0), (1, 128, 128, 0), (0, 64, 64, 0), (0, 128, 16, 0)} <= fwd
+    assert sum(1 for p in fwd if p[3] > 0) >= 5
+    assert {c.plan["route"][:2] for c in RECT_CASES} >= {("plain", "plain"), ("plain", "ups"), ("rows", "xfold"), ("rows", "t"), ("subpixel", "plain")}
+    for case in RECT_WGRAD_ROW_CASES:      # the row-resident weight gradient and its refusals at W < 4
+        assert_rect_wgrad_row_plan(case)
