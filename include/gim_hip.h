@@ -61,6 +61,10 @@ int gim_version(void);
  *                (nearest even, saturating) when they are staged into LDS, v_mfma_f32_32x32x16_f16 with fp32 accumulation - BASELINE
  *                config 5 "fp16 MFMA", opt-in - on eligible launches only (gathered channels % 32 == 0, >= 32 output channels,
  *                forward / gim_conv2d_dgrad_t / wgrad): gim_conv_launch_plan out[7] == 2 says a launch takes it.
+ *                2 = the same kernels and the same launch plan as 1 with the plain IEEE conversion of the pixel-side operands
+ *                (activations, gradients): no clamp at +-65504, so |value| >= 65520 becomes +-inf and reaches the output through
+ *                the fp32 accumulators as it would in fp32 arithmetic.  For backward passes under a dynamic loss scale, whose
+ *                overflow test (gim_adam_step_scaled) looks for exactly that in the gradient bucket.
  *   post_slope : (gim_conv2d_fwd only; 0 or 1 = none) LeakyReLU with this slope on the STORED output, y = lrelu(conv + bias +
  *             residual): the LeakyReLU that the reference applies in front of the NEXT conv (models/model_blocks.py:507), done
  *             once per element here instead of once per tap and output tile in that conv's K loop (which the caller then runs
@@ -398,6 +402,22 @@ int gim_img_att_mix_bwd(const float* dout, const float* q1, const float* k1, con
  * (graph-replay safe).  grad_scale multiplies the gradient first (1/world_size after an all-reduce sum). */
 int gim_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_end, const float* lr,
                   int n_seg, float beta1, float beta2, float eps, float grad_scale, int32_t* step, void* stream);
+
+/* The same update behind a dynamic loss scale (the fp16 matrix path): three launches on `stream`, no host read.
+ *   1. non-finite test of g[0 .. n) (inf or NaN anywhere, padding included; g on a 16-byte boundary) -> overflow word;
+ *   2. the Adam update with gradient factor grad_scale * inv_scale - every workgroup returns before it touches p, m, v
+ *      when the overflow word is set;
+ *   3. one thread: on overflow scale = max(scale / 2, min_scale), clean = 0, skipped += 1, `step` stays; otherwise step += 1,
+ *      clean += 1 and, when clean reaches the growth interval, scale *= 2 and clean = 0.  Clears the overflow word.
+ * `state` is a device array of GIM_SCALER_WORDS 32-bit words (the caller fills it; scale and inv_scale powers of two, so both
+ * stay exact under the factors 2 and 1/2):
+ *   [0] float scale          [1] float inv_scale = 1 / scale     [2] int32 growth interval (clean steps per doubling, >= 1)
+ *   [3] int32 clean steps since the last change of scale         [4] int32 overflow word (0 between calls)
+ *   [5] int32 skipped steps, total                               [6] float min_scale
+ *   [7] int32 1 when the most recent call skipped its step, else 0 */
+#define GIM_SCALER_WORDS 8
+int gim_adam_step_scaled(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_end, const float* lr,
+                         int n_seg, float beta1, float beta2, float eps, float grad_scale, int32_t* step, void* state, void* stream);
 
 /* ---- Inference of the baseline authenticators (baselines/siamese/models.py:14-56,97-114, baselines/arcface/models.py:16-164,214-237
  * as authentication_eval/eval_gim_on_authentication.py:47-72,109-128 runs them: eval mode, no_grad).  Forward only. ----

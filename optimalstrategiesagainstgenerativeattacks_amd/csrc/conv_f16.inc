@@ -23,6 +23,10 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 // finite value instead of an infinity (inf - inf, 0 * inf = NaN two layers later).  SAT = false for weights (spectrally normalised
 // elsewhere, |w| << 65504: no clamp instructions spent on them).  The host keeps gradients inside the range from the other side with
 // a loss scale (ops.loss_scale): fp16 is precise down to 6e-5 only, gradients of a mean loss sit at 1e-3 ... 1e-7.
+// The three kernels below carry the clamp of their PIXEL-side operands as a compile-time flag (kernel parameter SAT, default true =
+// gim_conv_shape.prec 1).  SAT = false (prec 2) is the plain IEEE conversion: |value| >= 65520 becomes +-inf and travels through the
+// fp32 accumulators into the output as it would in fp32 arithmetic - what a dynamic loss scaler detects in the gradient bucket
+// (gim_adam_step_scaled).  Same tiles, same LDS images, same loops: the two instantiations differ in the v_med3_f32 per element only.
 template <bool SAT>
 __device__ __forceinline__ f32x4 sat16(f32x4 v) {
     if constexpr (SAT) {
@@ -38,15 +42,16 @@ __device__ __forceinline__ h8_t cvt8_f16(f32x4 lo, f32x4 hi) {
     const h2_t c = __builtin_convertvector(f32x2{hi[0], hi[1]}, h2_t), d = __builtin_convertvector(f32x2{hi[2], hi[3]}, h2_t);
     return h8_t{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
 }
+template <bool SAT>
 __device__ __forceinline__ h4_t cvt4_f16(f32x4 v) {
-    v = sat16<true>(v);
+    v = sat16<SAT>(v);
     const h2_t a = __builtin_convertvector(f32x2{v[0], v[1]}, h2_t), b = __builtin_convertvector(f32x2{v[2], v[3]}, h2_t);
     return h4_t{a[0], a[1], b[0], b[1]};
 }
 
 // K step: 32 channels of one tap.  LDS rows of 32 halves (64 B) padded to 80 B: byte for byte the image of the fp32 kernel's
 // 16-float rows, so the same conflict-free ds_write_b128 / ds_read_b128 pattern; a 16-byte fragment is 8 k values = one MFMA operand.
-template <int BM, int BN, int TM, int TN>
+template <int BM, int BN, int TM, int TN, bool SAT = true>
 __global__ __launch_bounds__(256, 2) void conv_igemm_f16_kernel(const ConvP p) {
     constexpr int KB = 32, LDH = 40;              // halves per padded LDS row
     constexpr int WAVES_N = BN / (32 * TN), WAVES_M = BM / (32 * TM);
@@ -135,7 +140,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f16_kernel(const ConvP p) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) ra[i][q][e] = __builtin_amdgcn_fmed3f(ra[i][q][e], ra[i][q][e] * p.pre_slope, p.pos_inf);
             }
-            *reinterpret_cast<h8_t*>(&As[buf * A_SZ + (arow + 64 * i) * LDH + aq]) = cvt8_f16<true>(ra[i][0], ra[i][1]);
+            *reinterpret_cast<h8_t*>(&As[buf * A_SZ + (arow + 64 * i) * LDH + aq]) = cvt8_f16<SAT>(ra[i][0], ra[i][1]);
         }
 #pragma unroll
         for (int i = 0; i < B_ROWS; ++i)
@@ -223,7 +228,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f16_kernel(const ConvP p) {
 // once and serves all nine taps from LDS.  Byte for byte the LDS images of the fp32 patch kernel (80-byte rows = 32 halves + pad).
 // Host guarantees as for conv_igemm_patch_kernel, with Ca % 32 == 0 and split-K in whole 32-channel chunks.
 // -------------------------------------------------------------------------------------------------
-template <int BM, int BN, int TM, int TN>
+template <int BM, int BN, int TM, int TN, bool SAT = true>
 __global__ __launch_bounds__(256, 2) void conv_igemm_patch_f16_kernel(const ConvP p) {
     constexpr int KB = 32, LDH = 40;
     constexpr int WAVES_N = BN / (32 * TN), WAVES_M = BM / (32 * TM);
@@ -280,7 +285,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_patch_f16_kernel(const Conv
 #pragma unroll
                     for (int e = 0; e < 4; ++e) rp[i][q][e] = __builtin_amdgcn_fmed3f(rp[i][q][e], rp[i][q][e] * p.pre_slope, p.pos_inf);
             }
-            if (p_lds[i] >= 0) *reinterpret_cast<h8_t*>(&Ps[p_wr + p_lds[i]]) = cvt8_f16<true>(rp[i][0], rp[i][1]);
+            if (p_lds[i] >= 0) *reinterpret_cast<h8_t*>(&Ps[p_wr + p_lds[i]]) = cvt8_f16<SAT>(rp[i][0], rp[i][1]);
         }
         p_wr = p_wr ? 0 : P_SZ;
     };
@@ -414,7 +419,7 @@ __device__ __forceinline__ int wg16_off(int row, int chunk) {   // byte offset i
     return 256 * row + 16 * (chunk ^ (((row & 3) << 2) | ((row >> 2) & 3)));
 }
 
-template <bool FASTB>
+template <bool FASTB, bool SAT = true>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_f16_kernel(const WgP p) {
     constexpr int BM = 128, BN = 128, TM = 2, TN = 2, WBK = 32;
     constexpr int IMG = WBK * 256;                       // bytes of one image
@@ -503,8 +508,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_f16_kernel(const WgP p) {
         }
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
-            *reinterpret_cast<h4_t*>(lds + buf * IMG + st_off[i]) = cvt4_f16(ra[i]);
-            *reinterpret_cast<h4_t*>(lds + (2 + buf) * IMG + st_off[i]) = cvt4_f16(rb[i]);
+            *reinterpret_cast<h4_t*>(lds + buf * IMG + st_off[i]) = cvt4_f16<SAT>(ra[i]);
+            *reinterpret_cast<h4_t*>(lds + (2 + buf) * IMG + st_off[i]) = cvt4_f16<SAT>(rb[i]);
         }
     };
     // transposed-read addresses: lane = 16 g + 4 q + p of the wave; operand block = 32 channels (16 (g & 1) selects the half),

@@ -124,7 +124,7 @@ struct ConvP {
     int kper;     // K-steps per slice
     int pix;      // floats between consecutive PIXELS of the gathered tensor: = Ca, except in the row-contiguous form of the <= 8-channel
                   // image layers (gim_conv2d_fwd_rows: Ca = the padded length of one tap ROW, K * Cin rounded up to 16, pix = Cin)
-    int f16;      // host only: gim_conv_shape.prec == 1 - fp16 operands on v_mfma_f32_32x32x16_f16 where the launch is eligible (conv_f16.inc)
+    int f16;      // host only: gim_conv_shape.prec (1 saturating, 2 IEEE conversion of the pixel side) - fp16 operands on v_mfma_f32_32x32x16_f16 where the launch is eligible (conv_f16.inc)
     const float* slope;   // gim_conv2d_infer (kernels with EPI = 1): per-output-channel PReLU slope [Cb] (NULL = no activation)
     int epi;      // host only: 1 = the launch runs the EPI = 1 instantiation of its kernel (epilogue MODE 5)
     int no_split; // host only: the launch never splits K (a per-channel activation cannot follow partial sums): every launcher clamps
@@ -1630,7 +1630,7 @@ static int check_shape(const gim_conv_shape* s) {
     GIM_CHECK_ARG(!s->pool || (!s->ups && s->H >= 2 && s->W >= 2 && s->wfold), "conv: pool needs ups == 0, H, W >= 2 and folded weights");
     GIM_CHECK_ARG(!s->wfold || s->pool || s->ups, "conv: wfold only with pool or ups");
     GIM_CHECK_ARG((long long)s->N * s->H * s->W < (1ll << 31), "conv: too many output pixels");
-    GIM_CHECK_ARG(s->prec == 0 || s->prec == 1, "conv: prec must be 0 (fp32 MFMA) or 1 (fp16 operands, fp32 accumulate)");
+    GIM_CHECK_ARG(s->prec >= 0 && s->prec <= 2, "conv: prec must be 0 (fp32 MFMA), 1 (fp16 operands, fp32 accumulate; saturating) or 2 (the same, non-saturating)");
     return GIM_OK;
 }
 
@@ -1918,8 +1918,8 @@ static void launch_tile(const ConvP& p, const IgemmPlan& q, hipStream_t st) {
         if constexpr (BMODE == 0) { if (q.family == IGEMM_PATCH && p.epi) kernel = conv_igemm_patch_kernel<BM, BN, TM, TN, BMODE, 1>; }
     }
     if constexpr (WIDE && BMODE == 0 && GEN == 0) {
-        if (q.family == IGEMM_F16) kernel = conv_igemm_f16_kernel<BM, BN, TM, TN>;
-        if (q.family == IGEMM_PATCH_F16) kernel = conv_igemm_patch_f16_kernel<BM, BN, TM, TN>;
+        if (q.family == IGEMM_F16) kernel = p.f16 == 2 ? conv_igemm_f16_kernel<BM, BN, TM, TN, false> : conv_igemm_f16_kernel<BM, BN, TM, TN>;
+        if (q.family == IGEMM_PATCH_F16) kernel = p.f16 == 2 ? conv_igemm_patch_f16_kernel<BM, BN, TM, TN, false> : conv_igemm_patch_f16_kernel<BM, BN, TM, TN>;
     }
     hipLaunchKernelGGL(kernel, dim3(q.gx, q.gy, q.gz), dim3(256), q.lds_bytes, st, p);
 }
@@ -2012,7 +2012,7 @@ static int fwd_call(ConvCall& c, const float* x, const float* w, const float* bi
     p.pre_slope = s->pre_slope; p.mask_slope = 1.f; p.out_scale = s->pool ? 0.25f : 1.f; p.res_ups = s->res_ups;
     GIM_CHECK_ARG(s->post_slope >= 0.f && s->post_slope <= 1.f, "conv fwd: post_slope must be in [0, 1] (0 or 1 = none)");
     p.post_slope = (s->post_slope > 0.f) ? s->post_slope : 1.f;
-    p.f16 = s->prec == 1;
+    p.f16 = s->prec;
     c.y_elems = (size_t)s->N * (s->H >> s->pool) * (s->W >> s->pool) * s->Cout;
     GIM_CHECK_ARG(c.y_elems * sizeof(float) <= 0x7FFFFFF0ull, "conv: one image of the output exceeds 2 GiB (32-bit buffer offsets)");
     c.bmode = 0;
@@ -2109,7 +2109,7 @@ static int dgrad_call(ConvCall& c, const float* dy, const float* w, const float*
     GIM_CHECK_ARG(c.y_elems * sizeof(float) <= 0x7FFFFFF0ull, "conv: one image of the output exceeds 2 GiB (32-bit buffer offsets)");
     const bool gen = (s->Cout % BK) != 0 || ((uintptr_t)dy & 15);
     const bool bscalar = (s->Cin % 4) != 0 || ((uintptr_t)w & 15);
-    p.f16 = transposed && s->prec == 1;   // fp16 operands: the k-contiguous (transposed-weights) form only - ops.py routes fp16 dgrads there
+    p.f16 = transposed ? s->prec : 0;   // fp16 operands: the k-contiguous (transposed-weights) form only - ops.py routes fp16 dgrads there
     if (transposed) {
         // WT[ci][a][b][co]: the weight rows are k-contiguous (k = (tap, co)), i.e. the forward kernel's operand layout
         GIM_CHECK_ARG(!gen && !((uintptr_t)w & 15), "conv dgrad (transposed weights): Cout % 16 == 0 and 16-byte aligned operands required");
@@ -2481,7 +2481,7 @@ static WgPlan wgrad_plan(const gim_conv_shape* s0, bool rows_form, int combine, 
     int row_target = 0;
     if (tile >= 20000) { row_resident = true; row_target = target; tile -= 20000; }
     // fp16 operands (conv_wgrad_f16_kernel): one tile shape, 32 pixels per K step; the table rows were measured on the fp32 kernels
-    const bool f16 = s->prec == 1 && q.rows % 4 == 0 && (up_fold ? s->Cout : s->Cin) % 4 == 0 && q.rows >= 32 && q.cols >= 64;
+    const bool f16 = s->prec >= 1 && q.rows % 4 == 0 && (up_fold ? s->Cout : s->Cin) % 4 == 0 && q.rows >= 32 && q.cols >= 64;
     if (f16) { row_resident = false; tile = 128; if (!(s->tune_wgrad > 0)) target = 0; q.table_hit = 0; }
     q.bm = q.rows > 64 ? 128 : (q.rows > 32 ? 64 : 32);
     q.bn = (q.bm == 32) ? 128 : (q.cols > 64 ? 128 : 64);
@@ -2637,8 +2637,9 @@ static int wgrad_impl(const float* dy, const float* x, float* slabs, float* bias
         const bool vb = (p.Cin % 4 == 0) && !((uintptr_t)p.x & 15);
         const int bk = (q.bk == 32 && va && vb) ? 32 : BK;
         const bool fastb = vb && p.g.ups == 0 && ((p.g.H * p.g.W) & (bk - 1)) == 0;   // a K step stays inside one image
-        if (q.family == WG_MFMA_F16 && va && vb && bk == 32 && fastb) hipLaunchKernelGGL(conv_wgrad_f16_kernel<true>, g, dim3(256), 0, st, p);
-        else if (q.family == WG_MFMA_F16 && va && vb && bk == 32) hipLaunchKernelGGL(conv_wgrad_f16_kernel<false>, g, dim3(256), 0, st, p);
+        const bool f16 = q.family == WG_MFMA_F16 && va && vb && bk == 32, sat = s->prec != 2;   // (prec 2: IEEE conversion, conv_f16.inc)
+        if (f16 && fastb) hipLaunchKernelGGL((sat ? conv_wgrad_f16_kernel<true, true> : conv_wgrad_f16_kernel<true, false>), g, dim3(256), 0, st, p);
+        else if (f16) hipLaunchKernelGGL((sat ? conv_wgrad_f16_kernel<false, true> : conv_wgrad_f16_kernel<false, false>), g, dim3(256), 0, st, p);
         else if (va && fastb) launch_wgrad<4, 4, true>(p, q.bm, q.bn, bk, g, st);
         else if (va && vb) launch_wgrad<4, 4, false>(p, q.bm, q.bn, bk, g, st);
         else if (va) launch_wgrad<4, 1, false>(p, q.bm, q.bn, bk, g, st);

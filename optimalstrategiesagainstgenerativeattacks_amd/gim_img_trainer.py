@@ -106,6 +106,26 @@ class GimTrainerBase(nn.Module):
         return self.get_global_step()
 
 
+class _LossScalers:
+    """Checkpoint entry "loss_scalers": the dynamic loss scale of each optimizer (fp16 matrix path, GIM_FP16_LOSS_SCALE=dynamic).
+    Absent in every other mode, so the file then has the reference's keys only."""
+
+    def __init__(self, **opts):
+        self.opts = opts
+
+    def state_dict(self):
+        scalers = {name: opt.dynamic_scaler() for name, opt in self.opts.items()}
+        if any(sc is None for sc in scalers.values()):
+            return None
+        return {name: sc.state_dict() for name, sc in scalers.items()}
+
+    def load_state_dict(self, sd):
+        for name, opt in self.opts.items():
+            sc = opt.dynamic_scaler()
+            if sc is not None and name in sd:
+                sc.load_state_dict(sd[name])
+
+
 class GIMImgTrainer(GimTrainerBase):
     IM_GROUPS = ("src_encoder", "env_encoder", "env_decoder", "img2img", "img_att", "env_noise_mapper")
 
@@ -123,6 +143,8 @@ class GIMImgTrainer(GimTrainerBase):
         self.au_scheduler, self.im_scheduler = (self.get_lr_scheduler(optimizer=o, milestones=lr_milestones, gamma=lr_gamma)
                                                 for o in (self.authenticator_opt, self.impersonator_opt))
         self._init_checkpoints(outdir)
+        self.checkpoint_io.register_optional(loss_scalers=_LossScalers(authenticator_opt=self.authenticator_opt,
+                                                                       impersonator_opt=self.impersonator_opt))
 
     def authenticator_forward(self, fake_sample, real_sample, si_sample, grad=True):
         ops.join_lanes()

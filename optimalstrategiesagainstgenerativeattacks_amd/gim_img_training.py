@@ -38,15 +38,32 @@ def au_eval_step(trainer, real_sample, fake_sample, si_sample):
             pred_on_real.detach(), pred_on_fake.detach(), fake_sample.detach())
 
 
-def _backward(loss):
+def _backward(loss, opt):
     """loss.backward() - on the fp16 matrix path of (loss * S), S = ops.loss_scale() (the optimizer step un-scales: FusedAdam.step
-    (grad_scale=1 / S)), so that the gradients the fp16 convolution kernels round stay inside fp16's precise range."""
+    (grad_scale=1 / S)), so that the gradients the fp16 convolution kernels round stay inside fp16's precise range.  In dynamic
+    mode S is the device scalar of `opt`'s LossScaler and the backward pass runs armed (ops.armed_backward): an overflow becomes an
+    infinity that the optimizer step finds."""
+    sc = opt.dynamic_scaler()   # None: static scale, or the fp32 matrix path
     s = ops.loss_scale()
-    with ops.caller_thread_backward():     # (the nodes' Python on this thread: 15-25 % less host time per step, see ops)
-        if s != 1.0:
+    with ops.caller_thread_backward(), ops.armed_backward(sc):     # (the nodes' Python on this thread: 15-25 % less host time per step, see ops)
+        if sc is not None:
+            sc.scale_loss(loss).backward()
+        elif s != 1.0:
             (loss * s).backward()
         else:
             loss.backward()
+
+
+def _opt_step(opt):
+    """The optimizer step behind _backward(loss, opt): un-scales by the static scale, or - dynamic mode - by the scaler's own."""
+    if opt.dynamic_scaler() is not None:
+        opt.step()
+    else:
+        sc, opt.loss_scaler = opt.loss_scaler, None   # (a scaler left from dynamic mode keeps its state, unused)
+        try:
+            opt.step(grad_scale=1.0 / ops.loss_scale())
+        finally:
+            opt.loss_scaler = sc
 
 
 def im_train_step(trainer, leaked_sample, si_sample, z=None):
@@ -55,8 +72,8 @@ def im_train_step(trainer, leaked_sample, si_sample, z=None):
     loss, fake_sample, au_out = trainer.forward(mode='impersonator_forward', leaked_sample=leaked_sample,
                                                 si_sample=si_sample, **({} if z is None else {"z": z}))
     loss = loss.mean()
-    _backward(loss)
-    trainer.module.impersonator_opt.step(grad_scale=1.0 / ops.loss_scale())
+    _backward(loss, trainer.module.impersonator_opt)
+    _opt_step(trainer.module.impersonator_opt)
     return loss.detach(), fake_sample.detach(), au_out.detach()
 
 
@@ -67,8 +84,8 @@ def au_train_step(trainer, real_sample, fake_sample, si_sample):
      fake_sample) = trainer.forward(mode='authenticator_forward', fake_sample=fake_sample, real_sample=real_sample,
                                     si_sample=si_sample)
     loss = loss.mean()
-    _backward(loss)
-    trainer.module.authenticator_opt.step(grad_scale=1.0 / ops.loss_scale())
+    _backward(loss, trainer.module.authenticator_opt)
+    _opt_step(trainer.module.authenticator_opt)
     return (loss.detach(), loss_on_real.detach().mean(), loss_on_fake.detach().mean(), reg.detach().mean(),
             out_on_real.detach().mean(), out_on_fake.detach().mean(),
             pred_on_real.detach(), pred_on_fake.detach(), fake_sample.detach())
@@ -116,12 +133,12 @@ def gim_step(trainer, leaked_sample, real_sample, si_sample, z=None, overlap=Non
     # generator: backward on the caller's stream (enqueued first: it is the longer dependency chain; enqueueing the discriminator's
     # FORWARD ahead of it - so that lane 1 starts ~8 ms of host time earlier - was measured 4 % SLOWER, 406 vs 423 episodes/s over
     # three alternating pairs on one box: lane 1's early kernels take the chip from the critical lane; profiles/r04_d_*)
-    _backward(loss)
+    _backward(loss, mod.impersonator_opt)
     ops.mark_phase("G backward done")
     gbwd_done = cur.record_event()
     # generator's Adam right away: nothing on lane 1 reads the generator's weights, and with several GPUs its gradient
     # all-reduce (the larger bucket, 246 MB) then runs under the discriminator step instead of after it
-    mod.impersonator_opt.step(grad_scale=1.0 / ops.loss_scale())
+    _opt_step(mod.impersonator_opt)
     ops.mark_phase("G update done")
     im = (loss.detach(), fake_d, au_out.detach())
 
@@ -135,10 +152,10 @@ def gim_step(trainer, leaked_sample, real_sample, si_sample, z=None, overlap=Non
                                      si_sample=si_sample)
         dloss = dloss.mean()
         ops.mark_phase("D forward done")
-        _backward(dloss)
+        _backward(dloss, mod.authenticator_opt)
         ops.mark_phase("D backward done")
         dstream.wait_event(gbwd_done)   # the generator's backward reads the weights this update overwrites
-        mod.authenticator_opt.step(grad_scale=1.0 / ops.loss_scale())
+        _opt_step(mod.authenticator_opt)
         ops.mark_phase("D update done")
         au = (dloss.detach(), loss_on_real.detach().mean(), loss_on_fake.detach().mean(), reg.detach().mean(),
               out_on_real.detach().mean(), out_on_fake.detach().mean(),
@@ -273,6 +290,11 @@ def train_epoch(device, logger, epoch, trainer, train_ds, val_ds, train_batch_si
                      ('train losses', 'gen loss'))
             for (category, k_), v in zip(names, vals):
                 logger.add_scalar(category=category, k=k_, v=v, global_step=global_step)
+            if ops.matrix_path() == "fp16" and ops.loss_scale_mode() == "dynamic":   # only then: the other modes' call stream stays as it is
+                for agent, opt in (("au", trainer.module.authenticator_opt), ("im", trainer.module.impersonator_opt)):
+                    st = opt.dynamic_scaler().state()
+                    logger.add_scalar(category='loss_scale', k=agent, v=st["scale"], global_step=global_step)
+                    logger.add_scalar(category='loss_scale', k=agent + '_skipped', v=st["skipped"], global_step=global_step)
             for k_ in buf:
                 buf[k_] = []
 

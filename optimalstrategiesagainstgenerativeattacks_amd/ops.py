@@ -6,8 +6,10 @@ must be CUDA(HIP) float32.  Activations are NHWC.
 """
 import collections
 import ctypes
+import math
 import os
 import struct
+import warnings
 import weakref
 
 import torch
@@ -205,11 +207,82 @@ def matrix_path():
 # therefore differentiate loss * S and the fused Adam kernel multiplies the gradient bucket by 1 / S (a power of two: exact in
 # fp32, every backward operator is linear in the incoming gradient) - the standard mixed-precision recipe; not in the reference,
 # which has no 16-bit path.  Too-large values saturate at +-65504 when they are rounded (conv_f16.inc).  1 on the fp32 path.
-_LOSS_SCALE = [float(os.environ.get("GIM_FP16_LOSS_SCALE", "4096"))]
+#
+# GIM_FP16_LOSS_SCALE=dynamic / set_loss_scale("dynamic"): the scale lives in device memory, one optim.LossScaler per optimizer.
+# The backward pass of a step function then runs its fp16 launches with the IEEE conversion (gim_conv_shape.prec = 2: a value
+# beyond the fp16 range becomes an infinity instead of +-65504), the optimizer step looks for a non-finite value in its gradient
+# bucket, skips the update when it finds one and halves the scale; growth_interval clean steps in a row double it
+# (gim_adam_step_scaled; nothing of this is read back by the host).  Forward passes keep the saturating kernels: their values are
+# not scaled, so no scale can bring them back into range.
+_DYNAMIC_DEFAULTS = dict(init=4096.0, growth_interval=2000, min_scale=1.0)   # init: the static default; interval: torch.amp.GradScaler's
+_warned_scales = set()
+
+
+def _parse_loss_scale(value, what):
+    """-> "dynamic" or a positive float; ValueError for anything else, one warning per value that is not a power of two (the
+    "1 / S is exact" argument above needs one)."""
+    if isinstance(value, str) and value.strip().lower() == "dynamic":
+        return "dynamic"
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError("%s: %r is neither a number nor 'dynamic'" % (what, value)) from None
+    if not (v > 0.0) or v == float("inf"):   # (also NaN)
+        raise ValueError("%s must be a positive finite number or 'dynamic', got %r" % (what, value))
+    if math.frexp(v)[0] != 0.5 and v not in _warned_scales:
+        _warned_scales.add(v)
+        warnings.warn("%s = %r is not a power of two: scaling and un-scaling the gradients then rounds" % (what, value), stacklevel=3)
+    return v
+
+
+_LOSS_SCALE = [_parse_loss_scale(os.environ.get("GIM_FP16_LOSS_SCALE", "4096"), "GIM_FP16_LOSS_SCALE")]
+_DYNAMIC = dict(_DYNAMIC_DEFAULTS)   # what new optim.LossScaler objects start from in dynamic mode
+_ARMED = [0]                         # inside the backward pass of a step function in dynamic mode: fp16 launches take prec 2
+
+
+def loss_scale_mode():
+    """"dynamic" (GIM_FP16_LOSS_SCALE=dynamic / set_loss_scale("dynamic"); in force on the fp16 matrix path only) or "static"."""
+    return "dynamic" if _LOSS_SCALE[0] == "dynamic" else "static"
 
 
 def loss_scale():
-    return _LOSS_SCALE[0] if _PREC[0] else 1.0
+    """The static loss scale: 1 on the fp32 path; in dynamic mode the scalers' INITIAL scale (the current one lives on the device:
+    optim.LossScaler.state())."""
+    if not _PREC[0]:
+        return 1.0
+    return _DYNAMIC["init"] if _LOSS_SCALE[0] == "dynamic" else _LOSS_SCALE[0]
+
+
+def dynamic_loss_scale_defaults():
+    return dict(_DYNAMIC)
+
+
+def set_loss_scale(value, init=4096, growth_interval=2000, min_scale=1.0):
+    """A number (static scale) or "dynamic" (then init / growth_interval / min_scale are what new optim.LossScaler objects start
+    from); returns the previous setting (a number or "dynamic")."""
+    v = _parse_loss_scale(value, "loss scale")
+    if v == "dynamic":
+        i0, m0 = _parse_loss_scale(init, "init"), _parse_loss_scale(min_scale, "min_scale")
+        if i0 == "dynamic" or m0 == "dynamic" or int(growth_interval) < 1:
+            raise ValueError("dynamic loss scale: init and min_scale are positive numbers, growth_interval >= 1")
+        _DYNAMIC.update(init=i0, growth_interval=int(growth_interval), min_scale=m0)
+    prev = _LOSS_SCALE[0]
+    _LOSS_SCALE[0] = v
+    return prev
+
+
+class armed_backward:
+    """Context of a backward pass whose gradients a dynamic LossScaler will test: eligible fp16 launches inside (the second-order ones
+    of the R1 term too) convert without the clamp.  A no-op for scaler None."""
+
+    def __init__(self, scaler):
+        self.on = 1 if scaler is not None else 0
+
+    def __enter__(self):
+        _ARMED[0] += self.on
+
+    def __exit__(self, *exc):
+        _ARMED[0] -= self.on
 
 
 def set_matrix_path(name):
@@ -227,11 +300,12 @@ _SHAPES = {}   # argument tuple -> template struct (a 17-field ctypes constructo
 
 
 def _shape(N, H, W, Cin, Cout, KH, ups, pre_slope, pool=0, wfold=0, res_ups=0):
-    key = (N, H, W, Cin, Cout, KH, ups, pre_slope, pool, wfold, res_ups, _DETERMINISTIC[0], _PREC[0])
+    prec = 2 if (_PREC[0] and _ARMED[0]) else _PREC[0]
+    key = (N, H, W, Cin, Cout, KH, ups, pre_slope, pool, wfold, res_ups, _DETERMINISTIC[0], prec)
     t = _SHAPES.get(key)
     if t is None:
         t = _SHAPES[key] = GimConvShape(N, H, W, Cin, Cout, KH, ups, pre_slope, pool, wfold, res_ups, 0, 1 if _DETERMINISTIC[0] else 0, 0, 0, 0.0,
-                                        _PREC[0] if H * W > 1 else 0)   # (linears - 1 x 1 maps - stay fp32: tiny, and the head's logits are built there)
+                                        prec if H * W > 1 else 0)   # (linears - 1 x 1 maps - stay fp32: tiny, and the head's logits are built there)
     return GimConvShape.from_buffer_copy(t)    # callers set tune_* / post_slope / out_zeroed on their own copy
 
 
@@ -672,7 +746,7 @@ def _dgrad_route(g, prec, has_w, has_res_half=False):
     of the fp16 path, whose kernel exists in this form only; "xfold": those image layers when plain, J adjacent dx pixels as the output
     columns of one stride-(1, J) convolution; "ups": 1x1 behind up2; "plain".  has_res_half (0.25 * up2(res_half) is to be added):
     "res", the plain form with the addition in its epilogue - or the launch's own route and add_res (gim_add_avgpool2_bwd follows)."""
-    f16_t = prec == 1 and g.Cout % 32 == 0 and g.Cin >= 32
+    f16_t = prec >= 1 and g.Cout % 32 == 0 and g.Cin >= 32
     J = 0
     if has_w and g.Cout % 16 == 0 and not (g.ups and not g.fold) and ((g.Cin <= 8 and _NARROW_DGRAD_T) or f16_t):
         if g.KH >= 3 and not (g.ups or g.pool or g.fold) and _NARROW_XFOLD and not f16_t:

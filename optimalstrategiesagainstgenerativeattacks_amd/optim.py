@@ -71,6 +71,50 @@ def all_reduce_grads_(flat_g, timing=None):
     return 1.0
 
 
+class LossScaler:
+    """Dynamic loss scale of the fp16 matrix path, resident on the device (layout: include/gim_hip.h, gim_adam_step_scaled).
+    The step functions differentiate scale_loss(loss); FusedAdam.step (loss_scaler set) tests the gradient bucket, skips the
+    update on inf / NaN and halves the scale, and doubles it after growth_interval clean steps in a row.  Nothing here reads
+    the device except state() (and state_dict(), which calls it)."""
+    WORDS = 8
+
+    def __init__(self, device, init=4096.0, growth_interval=2000, min_scale=1.0):
+        self.device = torch.device(device)
+        self.words = torch.zeros(self.WORDS, dtype=torch.int32, device=self.device)
+        self._set(float(init), int(growth_interval), 0, 0, float(min_scale), 0)
+
+    def _set(self, scale, interval, clean, skipped, min_scale, last_overflow):
+        if not (scale > 0 and min_scale > 0 and interval >= 1):
+            raise ValueError("LossScaler: scale and min_scale must be positive, growth_interval >= 1")
+        host = torch.zeros(self.WORDS, dtype=torch.int32)
+        host[:2].view(torch.float32).copy_(torch.tensor([scale, 1.0 / scale]))
+        host[6:7].view(torch.float32).fill_(min_scale)
+        host[2], host[3], host[5], host[7] = interval, clean, skipped, last_overflow
+        self.words.copy_(host)
+        self._scale = self.words[0:1].view(torch.float32)   # the device scalar scale_loss multiplies by
+
+    def scale_loss(self, loss):
+        """loss * scale as an engine op on the device scalar (no host read, graph-capture safe)."""
+        from . import ops
+        return ops.MulScalarFn.apply(loss.reshape(1), self._scale).reshape(loss.shape)
+
+    def state(self):
+        """{"scale", "clean_steps", "skipped", "last_overflow", "growth_interval", "min_scale"} - synchronises."""
+        w = self.words.cpu()
+        f = w.view(torch.float32)
+        return {"scale": float(f[0]), "clean_steps": int(w[3]), "skipped": int(w[5]), "last_overflow": bool(w[7]),
+                "growth_interval": int(w[2]), "min_scale": float(f[6])}
+
+    def state_dict(self):
+        return self.state()
+
+    def load_state_dict(self, sd):
+        cur = self.state()
+        cur.update(sd)
+        self._set(float(cur["scale"]), int(cur["growth_interval"]), int(cur["clean_steps"]), int(cur["skipped"]),
+                  float(cur["min_scale"]), int(bool(cur["last_overflow"])))
+
+
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False)
@@ -79,7 +123,18 @@ class FusedAdam(torch.optim.Optimizer):
         self._host_step = 0
         self._lr_cache = None
         self.grad_divisor = None  # set by dp: world size for the post-all-reduce average
+        self.loss_scaler = None        # a LossScaler: step() tests the bucket, skips on inf / NaN and un-scales by the DEVICE scale
         self.allreduce_timing = None   # a list: step() appends the (before, after) events of its gradient all-reduce (bench.py)
+
+    def dynamic_scaler(self):
+        """The LossScaler the step functions use (created on first use from ops.set_loss_scale's settings), or None when the loss
+        scale is static or the matrix path fp32."""
+        from . import ops
+        if ops.matrix_path() != "fp16" or ops.loss_scale_mode() != "dynamic":
+            return None
+        if self.loss_scaler is None:
+            self.loss_scaler = LossScaler(self._all_params()[0].device, **ops.dynamic_loss_scale_defaults())
+        return self.loss_scaler
 
     # ------------------------------------------------------------------ flat storage
     def _all_params(self):
@@ -140,9 +195,15 @@ class FusedAdam(torch.optim.Optimizer):
             return
         for p, (o, n) in self._offsets.items():
             if p.data_ptr() != self.flat_p.data_ptr() + 4 * o:  # e.g. module.to() / load after build
+                self._sync_host_step()
                 self._built = False
                 self._build()
                 return
+
+    def _sync_host_step(self):
+        """With a loss scaler only the device counter knows how many steps were applied (a skipped one does not count)."""
+        if self.loss_scaler is not None:
+            self._host_step = int(self._step_dev.item())
 
     def _sync_grads(self):
         """Gradients normally accumulate in place into the flat buffer; re-home any that did not."""
@@ -178,7 +239,9 @@ class FusedAdam(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None, grad_scale=1.0):
         """grad_scale multiplies the gradient bucket inside the Adam kernel (together with the 1 / world_size of the data-parallel
-        average): 1 / S after a backward pass of S * loss (the loss scale of the fp16 matrix path, ops.loss_scale)."""
+        average): 1 / S after a backward pass of S * loss (the loss scale of the fp16 matrix path, ops.loss_scale).  With a
+        loss_scaler the kernel takes 1 / S from the scaler's device state (pass grad_scale = 1) and the update is skipped when the
+        bucket - after the all-reduce, so on every rank alike - holds an inf or a NaN."""
         assert closure is None
         lib = _lib.load()
         self._ensure()
@@ -188,10 +251,13 @@ class FusedAdam(torch.optim.Optimizer):
         g0 = self.param_groups[0]
         for g in self.param_groups:
             assert g["betas"] == g0["betas"] and g["eps"] == g0["eps"], "one (betas, eps) per optimizer"
-        check(lib.gim_adam_step(self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.flat_m.data_ptr(), self.flat_v.data_ptr(),
-                                self.flat_p.numel(), self._seg_end.data_ptr(), self._lr_dev.data_ptr(), len(self.param_groups),
-                                g0["betas"][0], g0["betas"][1], g0["eps"], scale * grad_scale, self._step_dev.data_ptr(),
-                                torch.cuda.current_stream().cuda_stream), "adam_step")
+        args = (self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.flat_m.data_ptr(), self.flat_v.data_ptr(),
+                self.flat_p.numel(), self._seg_end.data_ptr(), self._lr_dev.data_ptr(), len(self.param_groups),
+                g0["betas"][0], g0["betas"][1], g0["eps"], scale * grad_scale, self._step_dev.data_ptr())
+        if self.loss_scaler is not None:
+            check(lib.gim_adam_step_scaled(*args, self.loss_scaler.words.data_ptr(), torch.cuda.current_stream().cuda_stream), "adam_step_scaled")
+        else:
+            check(lib.gim_adam_step(*args, torch.cuda.current_stream().cuda_stream), "adam_step")
         self.note_steps(1)
 
     def note_steps(self, k):
@@ -204,6 +270,7 @@ class FusedAdam(torch.optim.Optimizer):
     # ------------------------------------------------------------------ checkpoint format
     def state_dict(self):
         if self._built:
+            self._sync_host_step()   # "step" from the device counter: _host_step would count a skipped step
             self._publish_state()
         return super().state_dict()
 

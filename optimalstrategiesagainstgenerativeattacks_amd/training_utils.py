@@ -143,14 +143,24 @@ class CheckpointIO:
     def __init__(self, checkpoint_dir, **modules):
         self.checkpoint_dir = checkpoint_dir
         self.module_dict = dict(modules)
+        self.optional_dict = {}
         os.makedirs(checkpoint_dir, exist_ok=True)
 
     def register_modules(self, **modules):
         self.module_dict.update(modules)
 
+    def register_optional(self, **modules):
+        """Entries beyond the reference's format: written only while state_dict() returns something, restored when the file
+        has them, and no warning when it does not."""
+        self.optional_dict.update(modules)
+
     def save(self, global_step, last_epoch, filename):
         payload = {"global_step": global_step, "last_epoch": last_epoch}
         payload.update((name, obj.state_dict()) for name, obj in self.module_dict.items())
+        for name, obj in self.optional_dict.items():
+            sd = obj.state_dict()
+            if sd is not None:
+                payload[name] = sd
         path = os.path.join(self.checkpoint_dir, filename)
         tmp = path + ".tmp.%d" % os.getpid()
         torch.save(payload, tmp)
@@ -167,6 +177,9 @@ class CheckpointIO:
                 obj.load_state_dict(payload[name])
             else:
                 print("Warning: Could not find %s in checkpoint!" % name)
+        for name, obj in self.optional_dict.items():
+            if name in payload:
+                obj.load_state_dict(payload[name])
         return payload["global_step"], payload["last_epoch"]
 
 
