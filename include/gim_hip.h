@@ -388,6 +388,25 @@ int gim_sqsum_rows_bwd(const float* x, const float* dout, float* dx, int B, int6
 int gim_episode_gather(const uint8_t* bank, const int32_t* idx, const uint8_t* flip, float* out, int n_out, int H, int W, int C,
                        void* stream);
 
+/* Ingest: the resize in front of that bank.  Native-size uint8 images -> out_h x out_w uint8, bit for bit what PIL's
+ * Image.resize((out_w, out_h), Image.BILINEAR) gives (process_pil_image, data_handling/img_datasets.py:298), after convert('L')
+ * when to_gray is set (load_image(img_mode='L'), :286).  PIL's BILINEAR is an antialiased two-pass resampler: per axis every
+ * output index has a window [min, min + count) of source indices and `ksize` 22-bit fixed-point weights; a pass computes
+ * clamp((2^21 + sum_t src[min + t] * coef[t]) >> 22, 0, 255), the horizontal pass runs first and its result is rounded to uint8
+ * before the vertical one.  The tables are the caller's (device arrays, ingest.resample_table builds them on the host):
+ *   bounds int32 [out][2] = (min, count), coef int32 [out][ksize];  NULL, NULL, 0 = that axis keeps its size and is copied.
+ * src uint8 NHWC [n_img][H][W][C_in], dst uint8 [n_img][out_h][out_w][C_out], C_out = to_gray ? 1 : C_in; C_in is 1 or 3 and
+ * to_gray needs 3: L = (R*19595 + G*38470 + B*7471 + 0x8000) >> 16.  Integer arithmetic only; all offsets are 64-bit and n_img
+ * is not bound by a grid dimension.  H, W, out_h, out_w are any positive sizes (not powers of two).
+ * One workgroup resamples one band of output rows of one image through an LDS tile of the horizontally resampled source rows.
+ * Limits (GIM_E_BADARG beyond them): W * C_in <= 16384 bytes (a source row is staged whole), and the tile of a ONE-row band,
+ * min(y_ksize, H) * out_w * C_out bytes, must fit in 49120 bytes - y_ksize = 2 * ceil(H / out_h) + 1, so at out_w = 128, C_out = 3
+ * that is a vertical shrink factor of up to 63, at 64 px up to 127.
+ * Table entries are clamped to the image before use: a wrong table gives wrong pixels, not a wild access. */
+int gim_resize_bilinear_u8(const uint8_t* src, int64_t n_img, int H, int W, int C_in, int to_gray, uint8_t* dst, int out_h, int out_w,
+                           const int32_t* x_bounds, const int32_t* x_coef, int x_ksize, const int32_t* y_bounds, const int32_t* y_coef,
+                           int y_ksize, void* stream);
+
 /* ImgAttention mix (models/model_blocks.py:598-608; only with use_img_att): per pixel (P pixels, C channels, NHWC)
  * s1 = sum_c q1*k1, s2 = sum_c q2*k2, (a1, a2) = softmax(s1, s2), out = x1*a1 + v2*a2; att [P] keeps a1. */
 int gim_img_att_mix_fwd(const float* q1, const float* k1, const float* q2, const float* k2, const float* x1, const float* v2,

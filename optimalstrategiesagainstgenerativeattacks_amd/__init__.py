@@ -41,6 +41,7 @@ from .gim_gaussian_trainer import GIMGaussianTrainer
 from .gim_gaussian_training import train_gim_gaussian
 from .gim_img_trainer import GIMImgTrainer
 from .data import EpisodeBank, OmniglotEpisodeBank, synthetic_bank
+from .ingest import ImagePack, pack_directory, pack_omniglot, resample_table, resize_images
 from .gim_img_training import (au_eval_step, au_train_step, eval_step, gim_step, im_eval_step, im_train_step, train_epoch,
                                train_gim_imgs)
 from .baselines import ArcFace, Backbone, ProtonetEmbeddingNet, SiameseNet
@@ -53,4 +54,5 @@ __all__ = [
     "GIMFaceImpersonator", "GIMImgTrainer", "GIMGaussianTrainer", "im_train_step", "au_train_step", "im_eval_step", "au_eval_step",
     "gim_step", "train_epoch", "eval_step", "train_gim_imgs", "train_gim_gaussian", "EpisodeBank", "OmniglotEpisodeBank", "synthetic_bank", "Logger", "FusedAdam", "DataParallelMock", "EpisodeParallel", "GlobalStep", "CheckpointIO", "adjust_batch_size",
     "pin_rank_to_cores", "stream_concurrency_check", "hw_queues_state", "ProtonetEmbeddingNet", "SiameseNet", "Backbone", "ArcFace",
+    "ImagePack", "pack_directory", "pack_omniglot", "resample_table", "resize_images",
 ]

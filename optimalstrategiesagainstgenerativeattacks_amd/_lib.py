@@ -107,6 +107,7 @@ SIGNATURES = {
     "gim_conv2d_xfold_weights": [P, P, c_int, c_int, c_int, c_int, P],
     "gim_conv2d_dgrad_xfold": [P, P, P, P, P, SP, c_int, P],
     "gim_episode_gather": [P, P, P, P, c_int, c_int, c_int, c_int, P],
+    "gim_resize_bilinear_u8": [P, c_int64, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, c_int, P, P, c_int, P],
     "gim_maxpool_gather": [P, P, P, P, c_int, c_int, c_int, c_float, P],
     "gim_softmax_dim1_bwd_dp": [P, P, P, P, c_int, c_int, c_int, P],
     "gim_set_stats_bwd_bwd": [P, P, P, P, P, P, c_int, c_int, c_int, c_int64, c_int64, P],

@@ -3,8 +3,9 @@
 "class", "class_name"}`` in [-1, 1], m+n+k DISTINCT images of one class, independent random horizontal flips) served from
 a uint8 image bank that lives in HBM, so that the engine (hundreds of episodes per second) is not starved by JPEG
 decoding and host-side collation.  The bank holds the images already resized to S x S (the reference resizes with PIL at
-load time, img_datasets.py:298); conversion to float, the (0,1) -> (-1,1) range map and the flip run in one HIP kernel
-(``gim_episode_gather``).  288 GB of HBM hold 24 M images of 64x64x3.
+load time, img_datasets.py:298; ``from_pack`` builds the bank from native-size images with the same resize, ingest.py);
+conversion to float, the (0,1) -> (-1,1) range map and the flip run in one HIP kernel (``gim_episode_gather``).  288 GB of HBM
+hold 24 M images of 64x64x3.
 
 Index sampling stays on the host (a few dozen integers per episode); ``EpisodeBank`` is also a ``torch.utils.data.Dataset``
 with the reference's per-index semantics (``index // example_cnt_per_class`` = class), so the reference's DataLoader-based
@@ -91,6 +92,16 @@ class EpisodeBank(torch.utils.data.Dataset):
         self.class_names = class_names
         self.S, self.C = images_u8.shape[1], images_u8.shape[3]
 
+    @classmethod
+    def from_pack(cls, pack, img_size, m, n, k, img_channels=None, device="cuda", example_cnt_per_class=1, mirror=True, seed=0,
+                  chunk_bytes=256 << 20):
+        """The bank of an ``ingest.ImagePack`` (native-size images decoded on the host): every image resized to img_size on the GPU
+        exactly as the reference's ``load_image`` resizes it, classes and class names as packed.  img_channels defaults to the
+        pack's; 1 on an RGB pack converts to grayscale before the resize."""
+        img_channels = int(pack.shapes[0, 2]) if img_channels is None else img_channels
+        bank = pack.to_bank(img_size, img_channels, device, chunk_bytes)
+        return cls(bank, pack.class_offsets, m, n, k, example_cnt_per_class, mirror, [str(c) for c in pack.class_names], seed)
+
     def __len__(self):
         return len(self.sampler)
 
@@ -152,6 +163,14 @@ class OmniglotEpisodeBank(EpisodeBank):
         if images_u8.dim() == 4 and images_u8.shape[3] != 1:
             raise RuntimeError("OmniglotEpisodeBank: one-channel images expected (the reference loads Omniglot in mode 'L')")
         super().__init__(images_u8, class_offsets, m, n, si, example_cnt_per_class, mirror=False, class_names=class_names, seed=seed)
+
+    @classmethod
+    def from_pack(cls, pack, img_size, m, n, si, device="cuda", example_cnt_per_class=1, seed=0, chunk_bytes=256 << 20):
+        """The bank of ``ingest.pack_omniglot``'s pack: one channel ('L'), class names "alphabet/character"."""
+        if m + n + si > cls.NUM_EXAMPLES_PER_CLASS:
+            raise ValueError("Max allowed value for m+n+si is {}".format(cls.NUM_EXAMPLES_PER_CLASS))
+        bank = pack.to_bank(img_size, 1, device, chunk_bytes)
+        return cls(bank, pack.class_offsets, m, n, si, example_cnt_per_class, [str(c) for c in pack.class_names], seed)
 
 
 def synthetic_bank(n_classes, imgs_per_class, S, C, device, seed=0):
