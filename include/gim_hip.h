@@ -476,6 +476,41 @@ int gim_pair_score(const float* a, const float* b, float* out, int B, int D, voi
 int gim_l2norm_rows(const float* x, float* y, int B, int D, void* stream);
 int gim_absdiff(const float* a, const float* b, float* y, int64_t n, void* stream);
 
+/* ---- Training the siamese baseline (baseline_training.py): BatchNorm2d with BATCH statistics fused with the ReLU and the
+ * MaxPool2d(2) behind it (one block of ProtonetEmbeddingNet, siamese/models.py:50-56), forward and backward, and the backward of
+ * |a - b| (siamese/models.py:107).  csrc/bn_train.hip.  fp32 NHWC maps z [N][H][W][C] of M = N * H * W rows, C % 4 == 0, H and W even,
+ * every pointer 16-byte aligned; all launches on `stream`.  Nothing allocates and nothing uses float atomics: a sum over the rows of
+ * a map goes through `partials` (gim_bn_partials_floats(rows, C) floats, owned by the caller) - one partial per channel and slab of
+ * rows, gim_bn_slabs(rows) <= 1024 slabs, added by a second small launch in a fixed order: two runs are bit-identical.
+ *
+ *   gim_bn_stats (ops.bn_stats): mean[C], invstd[C] = 1 / sqrt(var + eps), var the BIASED variance over the M rows (M >= 2); with
+ *       running_mean / running_var (both or neither): rm = (1 - momentum) * rm + momentum * mean, rv likewise with the UNBIASED
+ *       var * M / (M - 1); num_batches_tracked (int64, may be NULL) += 1.  The variance is not E[x^2] - E[x]^2: a slab sums about
+ *       a shift taken from its own first row, the slabs' (count, mean, M2) are combined with Chan's formula.
+ *   gim_bn_relu_maxpool2_fwd (ops.BnReluMaxPool2Fn.forward): p [N][H/2][W/2][C] = maxpool2(relu((z - mean) * gamma * invstd + beta)).
+ *       The affine is applied to each of the four window elements before the maximum (gamma may be negative); ties: the first
+ *       maximum in row-major window order (torch.nn.MaxPool2d).  The normalised full-resolution map is never stored.
+ *   gim_bn_pool_bwd_reduce (ops.BnReluMaxPool2Fn.backward): dbeta[c] = sum dyhat, dgamma[c] = sum dyhat * xhat, where dyhat is dp
+ *       routed to the window's arg-max pixel (recomputed from z) if that maximum is > 0 and zero elsewhere; acc_dgamma / acc_dbeta
+ *       (each may be NULL): the same sums are also ADDED there (the parameters' .grad in the optimizer's bucket).
+ *   gim_bn_pool_bwd_dx (ops.BnReluMaxPool2Fn.backward): dz = gamma * invstd * (dyhat - dbeta / M - xhat * dgamma / M), the
+ *       convolution's dY, for all four pixels of every window.
+ *   gim_absdiff_bwd (ops.AbsDiffFn.backward): da = sign(a - b) * d, db = -da, sign(0) = 0; n % 4 == 0.
+ *   gim_logit_accuracy (baseline_training.SiameseTrainer.train_step): out[0] = share of the n logits with (logit >= 0) == (row < n_pos). */
+int gim_bn_slabs(int64_t rows);
+int gim_bn_partials_floats(int64_t rows, int C);
+int gim_bn_stats(const float* z, float* partials, float* mean, float* invstd, float* running_mean, float* running_var,
+                 int64_t* num_batches_tracked, int64_t M, int C, float momentum, float eps, void* stream);
+int gim_bn_relu_maxpool2_fwd(const float* z, const float* gamma, const float* beta, const float* mean, const float* invstd, float* p,
+                             int N, int H, int W, int C, void* stream);
+int gim_bn_pool_bwd_reduce(const float* dp, const float* z, const float* gamma, const float* beta, const float* mean,
+                           const float* invstd, float* partials, float* dgamma, float* dbeta, float* acc_dgamma, float* acc_dbeta,
+                           int N, int H, int W, int C, void* stream);
+int gim_bn_pool_bwd_dx(const float* dp, const float* z, const float* gamma, const float* beta, const float* mean, const float* invstd,
+                       const float* dgamma, const float* dbeta, float* dz, int N, int H, int W, int C, void* stream);
+int gim_absdiff_bwd(const float* a, const float* b, const float* d, float* da, float* db, int64_t n, void* stream);
+int gim_logit_accuracy(const float* logits, int n_pos, int n, float* out, void* stream);
+
 /* Stream self-check: one wave busy for `usec` microseconds (1 .. 5000, constant 100 MHz wall clock) on `stream`.  The host
  * launches one per engine stream at the same moment and event-times the total: streams that share a HIP hardware queue serialize
  * (nn.DataParallel's one-thread-per-device streams of training/gim_img_training.py:406-411 have no such aliasing to check). */

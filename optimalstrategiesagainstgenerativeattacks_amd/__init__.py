@@ -45,6 +45,7 @@ from .ingest import ImagePack, pack_directory, pack_omniglot, resample_table, re
 from .gim_img_training import (au_eval_step, au_train_step, eval_step, gim_step, im_eval_step, im_train_step, train_epoch,
                                train_gim_imgs)
 from .baselines import ArcFace, Backbone, ProtonetEmbeddingNet, SiameseNet
+from .baseline_training import PairSampler, SiameseTrainer, siamese_forward_train, train_siamese
 from .training_logger import Logger
 from .optim import FusedAdam
 from .training_utils import CheckpointIO, DataParallelMock, EpisodeParallel, GlobalStep, adjust_batch_size, pin_rank_to_cores
@@ -55,4 +56,5 @@ __all__ = [
     "gim_step", "train_epoch", "eval_step", "train_gim_imgs", "train_gim_gaussian", "EpisodeBank", "OmniglotEpisodeBank", "synthetic_bank", "Logger", "FusedAdam", "DataParallelMock", "EpisodeParallel", "GlobalStep", "CheckpointIO", "adjust_batch_size",
     "pin_rank_to_cores", "stream_concurrency_check", "hw_queues_state", "ProtonetEmbeddingNet", "SiameseNet", "Backbone", "ArcFace",
     "ImagePack", "pack_directory", "pack_omniglot", "resample_table", "resize_images",
+    "PairSampler", "SiameseTrainer", "siamese_forward_train", "train_siamese",
 ]

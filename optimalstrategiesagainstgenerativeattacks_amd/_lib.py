@@ -132,6 +132,14 @@ SIGNATURES = {
     "gim_pair_score": [P, P, P, c_int, c_int, P],
     "gim_l2norm_rows": [P, P, c_int, c_int, P],
     "gim_absdiff": [P, P, P, c_int64, P],
+    "gim_bn_slabs": [c_int64],
+    "gim_bn_partials_floats": [c_int64, c_int],
+    "gim_bn_stats": [P, P, P, P, P, P, P, c_int64, c_int, c_float, c_float, P],
+    "gim_bn_relu_maxpool2_fwd": [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
+    "gim_bn_pool_bwd_reduce": [P, P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
+    "gim_bn_pool_bwd_dx": [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
+    "gim_absdiff_bwd": [P, P, P, P, P, c_int64, P],
+    "gim_logit_accuracy": [P, c_int, c_int, P, P],
     "gim_version": [],
 }
 

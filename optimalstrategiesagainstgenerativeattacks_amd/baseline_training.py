@@ -1,0 +1,263 @@
+"""Training the siamese baseline authenticator (``baselines.SiameseNet``: ``baselines/siamese/models.py:14-56,97-114``) on the engine.
+
+The reference ships the model but neither a training loop nor a checkpoint; its evaluation (``eval_gim_on_authentication.py:47-58``)
+loads ``ckpts/model_*.pt['model']`` of an experiment directory with an ``args.json``.  ``train_siamese`` writes exactly that, so
+``authentication_eval.eval_authentication_task(baseline_type='siamese', baseline_exp_dir=out_dir)`` runs on its output unchanged.
+
+The training forward does not go through ``model.forward`` (the inference path on folded parameters, which keeps raising in training
+mode): ``siamese_forward_train`` runs the four blocks as ``ops.conv2d`` + ``ops.bn_relu_maxpool2`` (BatchNorm with batch statistics,
+ReLU and MaxPool2d(2) in one pass, csrc/bn_train.hip), brings the last map into the reference's (c, h, w) flatten order with the
+existing NHWC -> NCHW kernel, then ``ops.absdiff_halves`` and ``ops.linear``.  Because the embedding is in the reference's order, every
+parameter - ``fc.weight`` included - is trained in the reference's own layout: ``state_dict()`` has the reference's names, shapes, order
+and values, with no permutation to undo.  (The inference path reads the (h, w, c) embedding and permutes the fc columns when it derives
+its parameters, baselines.SiameseNet._derive.)
+
+Both inputs of a pair batch go through the encoder in ONE pass, so the batch statistics are over 2B images:
+``classify(*encode(cat([x1, x2])).chunk(2))`` on the reference's modules.  Single GPU, fp32 matrix path."""
+import json
+import os
+
+import numpy as np
+import torch
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
+
+from . import _lib, ops
+from ._lib import check
+from .baselines import ProtonetEmbeddingNet, SiameseNet
+from .optim import FusedAdam
+from .training_logger import Logger
+from .training_utils import get_latest_ckpt
+
+CHECKPOINT_DIR = "ckpts"
+
+
+def _pair_batch(x1, x2):
+    """[2B, C, S, S]: x1 on top of x2.  The two halves of one tensor (PairSampler.batch) are recognised and not copied."""
+    if x1.shape != x2.shape:
+        raise RuntimeError("siamese training: x1 %s and x2 %s differ in shape" % (tuple(x1.shape), tuple(x2.shape)))
+    base = x1._base
+    if (base is not None and base is x2._base and x1.is_contiguous() and x2.is_contiguous() and base.is_contiguous()
+            and base.numel() == 2 * x1.numel() and base.data_ptr() == x1.data_ptr()
+            and x2.data_ptr() == x1.data_ptr() + x1.numel() * x1.element_size()):
+        return base.view(2 * x1.shape[0], *x1.shape[1:])
+    return torch.cat([x1, x2], 0)
+
+
+def _forward_pairs(model, x):
+    """Logits [B, 1] of the pair batch x = [x1; x2] ([2B, C, S, S])."""
+    net = model.embedding_net
+    dims = (net.inp_n_channels, net.inp_img_size, net.inp_img_size)
+    x = ops._req(x, "x")
+    if x.dim() != 4 or tuple(x.shape[1:]) != dims or x.shape[0] % 2:
+        raise RuntimeError("expected [2B, %d, %d, %d] images, got %s" % (dims + (tuple(x.shape),)))
+    h = ops.to_nhwc(x)
+    for conv, bn in net.encoder:
+        z = ops.conv2d(h, conv.weight, conv.bias)
+        h = ops.bn_relu_maxpool2(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps)
+    e = ops.to_nchw(h).view(h.shape[0], -1)      # the reference's (c, h, w) flatten order
+    return ops.linear(ops.absdiff_halves(e), model.fc.weight, model.fc.bias)
+
+
+def siamese_forward_train(model, x1, x2):
+    """Training-mode logits [B, 1] of a baselines.SiameseNet: batch statistics over the 2B images of one encoder pass, running
+    statistics updated; differentiable in every parameter.  The model's ``training`` flag is neither read nor changed."""
+    return _forward_pairs(model, _pair_batch(x1, x2))
+
+
+class _PairLossFn(Function):
+    """(sum_{i < n_pos} bce(x_i, 1) + sum_{i >= n_pos} bce(x_i, 0)) / B as a [1] tensor: the BCE kernel with its scalar target on each
+    half of the logits, then the row-sum kernel - and their transposes going back."""
+
+    @staticmethod
+    def forward(ctx, logits, n_pos):
+        lib = _lib.load()
+        x = ops._req(logits, "logits")
+        B = x.numel()
+        st = ops._stream()
+        per = torch.empty(B, device=x.device, dtype=torch.float32)
+        for off, n, target in ((0, n_pos, 1.0), (n_pos, B - n_pos, 0.0)):
+            if n:
+                check(lib.gim_bce_logits_fwd(ops._p(x, off), ops._p(per, off), target, n, st), "bce_logits_fwd")
+        loss = torch.empty(1, device=x.device, dtype=torch.float32)
+        check(lib.gim_sum_dim1(ops._p(per), ops._p(loss), 1, B, 1, 1.0 / B, st), "sum_dim1")
+        ctx.save_for_backward(x)
+        ctx.n_pos = n_pos
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dl):
+        lib = _lib.load()
+        (x,) = ctx.saved_tensors
+        B, n_pos = x.numel(), ctx.n_pos
+        st = ops._stream()
+        dl = ops._req(dl, "dloss")
+        dper = torch.empty(B, device=x.device, dtype=torch.float32)
+        check(lib.gim_repeat_dim1(ops._p(dl), ops._p(dper), 1, B, 1, 1.0 / B, st), "repeat_dim1")
+        dx = torch.empty_like(x)
+        for off, n, target in ((0, n_pos, 1.0), (n_pos, B - n_pos, 0.0)):
+            if n:
+                check(lib.gim_bce_logits_bwd(ops._p(dper, off), ops._p(x, off), ops._p(dx, off), target, n, st), "bce_logits_bwd")
+        return dx, None
+
+
+def pair_loss(logits, n_pos):
+    """Mean BCE-with-logits of a pair batch whose first n_pos rows are same-class pairs (target 1), the rest target 0; a [1] tensor."""
+    if not 0 <= n_pos <= logits.numel():
+        raise ValueError("n_pos = %d outside [0, %d]" % (n_pos, logits.numel()))
+    return _PairLossFn.apply(logits, n_pos)
+
+
+def pair_accuracy(logits, n_pos):
+    """Share of the logits on the right side of 0 (prediction: logit >= 0, as agents.Authenticator with th = 0); a device scalar."""
+    x = ops._req(logits.detach(), "logits")
+    out = torch.empty(1, device=x.device, dtype=torch.float32)
+    check(_lib.load().gim_logit_accuracy(ops._p(x), n_pos, x.numel(), ops._p(out), ops._stream()), "logit_accuracy")
+    return out.view(())
+
+
+class SiameseTrainer:
+    """One FusedAdam over every parameter of a baselines.SiameseNet, in the reference's parameter order."""
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999)):
+        if not isinstance(model, SiameseNet):
+            raise TypeError("SiameseTrainer trains a baselines.SiameseNet")
+        self.model = model
+        self.opt = FusedAdam(model.parameters(), lr=lr, betas=betas)
+        self._one = None
+        self.last_logits = None      # [B, 1] logits of the latest train_step (before its update), detached
+
+    def _drop_inference_caches(self):
+        self.model._derived = None
+        self.model.embedding_net._derived = None
+
+    def train_step(self, x1, x2, n_pos):
+        """One Adam update on the pair batch (x1[i], x2[i]); rows < n_pos are same-class pairs.  Returns (loss, accuracy) of the
+        batch before the update, as device scalars: nothing is read back here."""
+        if ops.matrix_path() != "fp32":
+            raise RuntimeError("SiameseTrainer runs on the fp32 matrix path only (ops.set_matrix_path('fp32')): the fp16 path and its "
+                               "loss scale are not implemented for the baseline")
+        self.opt.zero_grad()
+        logits = siamese_forward_train(self.model, x1, x2)
+        loss = pair_loss(logits, n_pos)
+        if self._one is None or self._one.device != loss.device:
+            self._one = torch.ones(1, device=loss.device, dtype=torch.float32)
+        with ops.caller_thread_backward():
+            loss.backward(self._one)
+        self.opt.step()
+        self._drop_inference_caches()
+        self.last_logits = logits.detach()
+        return loss.detach().view(()), pair_accuracy(logits, n_pos)
+
+    def state_dict(self):
+        """{'model': the reference's SiameseNet state dict (names, shapes, order; on the host), 'opt': torch.optim.Adam's format}."""
+        return {"model": {k: v.detach().to("cpu").contiguous() for k, v in self.model.state_dict().items()}, "opt": self.opt.state_dict()}
+
+    def load_state_dict(self, sd):
+        self.model.load_state_dict(sd["model"], strict=True)
+        if sd.get("opt") is not None:
+            self.opt.load_state_dict(sd["opt"])
+        self._drop_inference_caches()
+
+
+class PairSampler:
+    """Pair batches over a data.EpisodeBank: batch_size // 2 positive pairs (two DISTINCT images of one class) first, then negative
+    pairs (one image each of two different classes).  Host logic only (a few dozen integers per batch); images are served by
+    bank.gather, flips follow bank.mirror.  The draws of iteration `it` depend on (seed, it) alone: a resumed run sees the batches the
+    uninterrupted run saw.  Reads bank.offsets and bank.mirror (and bank.gather in batch())."""
+
+    def __init__(self, bank, batch_size, seed=0):
+        self.bank = bank
+        self.offsets = np.asarray(bank.offsets, dtype=np.int64)
+        sizes = np.diff(self.offsets)
+        self.classes = np.nonzero(sizes >= 1)[0]
+        self.pos_classes = np.nonzero(sizes >= 2)[0]        # a class of one image is never drawn for a positive pair
+        self.batch_size, self.n_pos, self.seed = int(batch_size), int(batch_size) // 2, int(seed)
+        self.mirror = bool(bank.mirror)
+        if self.batch_size < 1:
+            raise ValueError("PairSampler: batch_size must be positive")
+        if len(self.classes) < 2:
+            raise ValueError("PairSampler: negative pairs need at least two classes, the bank has %d" % len(self.classes))
+        if self.n_pos and not len(self.pos_classes):
+            raise ValueError("PairSampler: positive pairs need a class with at least two images")
+
+    def draw(self, it):
+        """(idx [B, 2] int32 image indices, flip [B, 2] uint8, classes [B, 2]) of iteration `it`."""
+        rng = np.random.default_rng([self.seed, 0x5A1A, int(it)])
+        B = self.batch_size
+        idx, cls = np.empty((B, 2), dtype=np.int32), np.empty((B, 2), dtype=np.int64)
+        for b in range(B):
+            if b < self.n_pos:
+                c = int(self.pos_classes[rng.integers(len(self.pos_classes))])
+                lo, hi = self.offsets[c], self.offsets[c + 1]
+                idx[b] = lo + rng.choice(hi - lo, size=2, replace=False)
+                cls[b] = c
+            else:
+                c2 = self.classes[rng.choice(len(self.classes), size=2, replace=False)]
+                idx[b] = [self.offsets[c] + rng.integers(self.offsets[c + 1] - self.offsets[c]) for c in c2]
+                cls[b] = c2
+        flip = (rng.random((B, 2)) < 0.5) if self.mirror else np.zeros((B, 2), dtype=bool)
+        return idx, flip.astype(np.uint8), cls
+
+    def batch(self, it):
+        """(x1, x2, n_pos): the two halves of ONE gathered [2B, C, S, S] tensor."""
+        idx, flip, _ = self.draw(it)
+        x = self.bank.gather(idx.T, flip.T)      # all first images, then all second images
+        B = self.batch_size
+        return x[:B], x[B:], self.n_pos
+
+
+def _save(trainer, out_dir, step):
+    ckpt_dir = os.path.join(out_dir, CHECKPOINT_DIR)
+    os.makedirs(ckpt_dir, exist_ok=True)
+    path = os.path.join(ckpt_dir, "model_%08d.pt" % step)
+    tmp = path + ".tmp.%d" % os.getpid()
+    torch.save(dict(trainer.state_dict(), global_step=step), tmp)
+    os.replace(tmp, path)
+    return path
+
+
+def train_siamese(device, bank, out_dir, n_iters, batch_size=128, lr=1e-3, log_every=100, save_every=1000, seed=0, logger=None):
+    """Train a siamese baseline on the pair batches of `bank` up to iteration n_iters; resumes from the latest checkpoint of out_dir.
+    Writes out_dir/args.json and out_dir/ckpts/model_%08d.pt = {'model', 'opt', 'global_step'} every save_every iterations and at
+    the end; logs ('siamese', 'loss' / 'acc') every log_every iterations (one host read per log point).  Returns the trainer."""
+    device = torch.device(device)
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "args.json"), "w") as f:
+        json.dump({"baseline_type": "siamese", "img_size": int(bank.S), "img_channels": int(bank.C), "batch_size": int(batch_size),
+                   "lr": float(lr), "seed": int(seed), "n_iters": int(n_iters)}, f)
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(seed)
+        net = ProtonetEmbeddingNet(inp_n_channels=bank.C, inp_img_size=bank.S)
+        model = SiameseNet(net, net.embedding_dim)
+    trainer = SiameseTrainer(model.to(device), lr=lr)
+    step = 0
+    ckpt_dir = os.path.join(out_dir, CHECKPOINT_DIR)
+    if os.path.isdir(ckpt_dir):
+        try:
+            latest = get_latest_ckpt(ckpt_dir)
+        except FileNotFoundError:
+            latest = None
+        if latest is not None:
+            sd = torch.load(latest, map_location="cpu", weights_only=False)
+            trainer.load_state_dict(sd)
+            step = int(sd["global_step"])
+            print("Resuming siamese training from iteration {}".format(step))
+    if logger is None:
+        logger = Logger(log_dir=os.path.join(out_dir, "logs"), img_dir=os.path.join(out_dir, "imgs"))
+    sampler = PairSampler(bank, batch_size, seed)
+    saved = step
+    while step < n_iters:
+        loss, acc = trainer.train_step(*sampler.batch(step))
+        step += 1
+        if log_every and step % log_every == 0:
+            loss_v, acc_v = torch.stack([loss, acc]).tolist()
+            logger.add_scalar(category="siamese", k="loss", v=loss_v, global_step=step)
+            logger.add_scalar(category="siamese", k="acc", v=acc_v, global_step=step)
+        if save_every and step % save_every == 0:
+            _save(trainer, out_dir, step)
+            saved = step
+    if saved != step or not os.path.isdir(ckpt_dir):
+        _save(trainer, out_dir, step)
+    return trainer

@@ -1,7 +1,8 @@
 """Baseline authenticators of the reference's authentication evaluation on the engine, inference only:
 the siamese net (``baselines/siamese/models.py:14-56,97-114``) and ArcFace on the IR-SE backbone
 (``baselines/arcface/models.py:16-164,214-237``), as ``eval_gim_on_authentication.py:47-72,109-128`` runs them
-(``train(mode=False)`` + ``torch.no_grad()``).
+(``train(mode=False)`` + ``torch.no_grad()``).  Training the siamese net (batch statistics, its own forward over these modules'
+parameters) is ``baseline_training.py``; the classes here keep raising in training mode.
 
 The ``nn`` module tree exists for the ``state_dict`` only: names, shapes and order of its entries are the reference's, so
 that a checkpoint written there loads with ``strict=True``.  No torch module ever computes: the forwards run on the

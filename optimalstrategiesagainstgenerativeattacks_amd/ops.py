@@ -2230,3 +2230,158 @@ def l2norm_rows(x):
     y = torch.empty_like(x)
     check(lib.gim_l2norm_rows(_p(x), _p(y), x.shape[0], x.shape[1], _stream()), "l2norm_rows")
     return y
+
+
+# --------------------------------------------------------------------------------------------
+# training the siamese baseline (baseline_training.py): BatchNorm with batch statistics + ReLU + MaxPool2d(2), |a - b|
+# --------------------------------------------------------------------------------------------
+def _bn_partials(rows, C, device):
+    n = _lib.load().gim_bn_partials_floats(rows, C)
+    if n <= 0:
+        check(n, "bn_partials_floats")
+    return torch.empty(n, device=device, dtype=torch.float32)
+
+
+def bn_slabs(rows):
+    """Number of row slabs the two-stage sums of the BatchNorm kernels cut a map of `rows` rows into."""
+    n = _lib.load().gim_bn_slabs(rows)
+    if n <= 0:
+        check(n, "bn_slabs")
+    return n
+
+
+def _req_map(z, what):
+    z = _req(z, what)
+    if z.dim() != 4 or z.shape[3] % 4 or z.shape[1] % 2 or z.shape[2] % 2:
+        raise RuntimeError("%s must be an NHWC map [N, H, W, C] with H, W even and C %% 4 == 0, got %s" % (what, tuple(z.shape)))
+    return z
+
+
+def bn_stats(z, eps=1e-5, running_mean=None, running_var=None, num_batches_tracked=None, momentum=0.1):
+    """(mean [C], invstd [C]) of an NHWC map over its N * H * W rows (biased variance, as nn.BatchNorm2d normalises in training mode);
+    with running_mean / running_var / num_batches_tracked these are updated in place as nn.BatchNorm2d does (unbiased variance)."""
+    lib = _lib.load()
+    z = _req_map(z, "z")
+    C = z.shape[3]
+    M = z.numel() // C
+    if momentum is None:
+        raise NotImplementedError("bn_stats: momentum=None (cumulative moving average) is not implemented")
+    for name, v in (("running_mean", running_mean), ("running_var", running_var)):
+        if v is not None and (tuple(_req(v, name).shape) != (C,) or not v.is_contiguous()):
+            raise RuntimeError("bn_stats: %s must be a contiguous [C] tensor" % name)
+    if num_batches_tracked is not None and not (num_batches_tracked.is_cuda and num_batches_tracked.dtype == torch.int64):
+        raise RuntimeError("bn_stats: num_batches_tracked must be a CUDA int64 tensor")
+    stats = torch.empty((2, C), device=z.device, dtype=torch.float32)
+    partials = _bn_partials(M, C, z.device)
+    nbt = None if num_batches_tracked is None else num_batches_tracked.data_ptr()
+    check(lib.gim_bn_stats(_p(z), _p(partials), _p(stats), _p(stats, C), _p(running_mean), _p(running_var), nbt, M, C,
+                           float(momentum), float(eps), _stream()), "bn_stats")
+    return stats[0], stats[1]
+
+
+class BnReluMaxPool2Fn(Function):
+    """p = maxpool2(relu(batch_norm(z))) with BATCH statistics: nn.BatchNorm2d in training mode -> nn.ReLU -> nn.MaxPool2d(2) on an
+    NHWC map, the running statistics updated in place.  Saved for backward: z and the two [C] statistics - neither the normalised map
+    nor the arg-max positions (the backward recomputes them from z).  dweight / dbias are ADDED into the parameters' .grad where that
+    is the optimizer's bucket (then None goes back to autograd), as the convolutions' weight gradients are."""
+
+    @staticmethod
+    def forward(ctx, z, weight, bias, running_mean, running_var, num_batches_tracked, momentum, eps):
+        lib = _lib.load()
+        z = _req_map(z, "z")
+        N, H, W, C = z.shape
+        weight, bias = _req(weight, "weight"), _req(bias, "bias")
+        if tuple(weight.shape) != (C,) or tuple(bias.shape) != (C,):
+            raise RuntimeError("bn_relu_maxpool2: weight and bias must be [C = %d]" % C)
+        mean, invstd = bn_stats(z, eps, running_mean, running_var, num_batches_tracked, momentum)
+        p = torch.empty((N, H // 2, W // 2, C), device=z.device, dtype=torch.float32)
+        check(lib.gim_bn_relu_maxpool2_fwd(_p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(p), N, H, W, C, _stream()),
+              "bn_relu_maxpool2_fwd")
+        ctx.save_for_backward(z, weight, bias, mean, invstd)
+        return p
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dp):
+        lib = _lib.load()
+        z, weight, bias, mean, invstd = ctx.saved_tensors
+        N, H, W, C = z.shape
+        dp = _req(dp, "dp")
+        st = _stream()
+        sums = torch.empty((2, C), device=z.device, dtype=torch.float32)      # dgamma, dbeta
+        partials = _bn_partials(N * (H // 2) * (W // 2), C, z.device)
+        need = ctx.needs_input_grad
+        acc_w = _grad_target(weight) if need[1] else None
+        acc_b = _grad_target(bias) if need[2] else None
+        check(lib.gim_bn_pool_bwd_reduce(_p(dp), _p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(partials), _p(sums), _p(sums, C),
+                                         _p(acc_w), _p(acc_b), N, H, W, C, st), "bn_pool_bwd_reduce")
+        dz = None
+        if need[0]:
+            dz = torch.empty_like(z)
+            check(lib.gim_bn_pool_bwd_dx(_p(dp), _p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(sums), _p(sums, C), _p(dz),
+                                         N, H, W, C, st), "bn_pool_bwd_dx")
+        dw = sums[0] if (need[1] and acc_w is None) else None
+        db = sums[1] if (need[2] and acc_b is None) else None
+        return dz, dw, db, None, None, None, None, None
+
+
+def bn_relu_maxpool2(z, weight, bias, running_mean, running_var, num_batches_tracked, momentum=0.1, eps=1e-5):
+    """maxpool2(relu(batch_norm(z, batch statistics))) of an NHWC map -> [N, H/2, W/2, C]; differentiable in z, weight and bias
+    (once); the running statistics and num_batches_tracked move as nn.BatchNorm2d's do in training mode."""
+    return BnReluMaxPool2Fn.apply(z, weight, bias, running_mean, running_var, num_batches_tracked, momentum, eps)
+
+
+class AbsDiffFn(Function):
+    """|a - b| with torch's gradient: sign(a - b) * d for a, its negative for b, 0 where a == b.  halves: a and b are the two
+    halves of ONE [2B, D] matrix (the pair batch encoded in one pass), whose gradient is written as one buffer."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        lib = _lib.load()
+        halves = b is None
+        if halves:
+            e = _req(a, "e")
+            if e.dim() != 2 or e.shape[0] % 2:
+                raise RuntimeError("absdiff_halves: a [2B, D] matrix expected, got %s" % (tuple(e.shape),))
+            B = e.shape[0] // 2
+            a, b = e[:B], e[B:]
+        else:
+            a, b = _req(a, "a"), _req(b, "b")
+            if a.shape != b.shape:
+                raise RuntimeError("absdiff_train: shapes differ")
+        y = torch.empty_like(a)
+        check(lib.gim_absdiff(_p(a), _p(b), _p(y), a.numel(), _stream()), "absdiff")
+        if halves:
+            ctx.save_for_backward(e)
+        else:
+            ctx.save_for_backward(a, b)
+        ctx.halves = halves
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d):
+        lib = _lib.load()
+        d = _req(d, "d")
+        if ctx.halves:
+            (e,) = ctx.saved_tensors
+            a, b = e[:e.shape[0] // 2], e[e.shape[0] // 2:]
+        else:
+            a, b = ctx.saved_tensors
+        if ctx.halves:
+            g = torch.empty((2 * a.shape[0], a.shape[1]), device=a.device, dtype=torch.float32)
+            da, db = g[:a.shape[0]], g[a.shape[0]:]
+        else:
+            da, db = torch.empty_like(a), torch.empty_like(a)
+        check(lib.gim_absdiff_bwd(_p(a), _p(b), _p(d), _p(da), _p(db), a.numel(), _stream()), "absdiff_bwd")
+        return (g, None) if ctx.halves else (da, db)
+
+
+def absdiff_train(a, b):
+    """|a - b|, elementwise and differentiable (ops.absdiff is the inference operator)."""
+    return AbsDiffFn.apply(a, b)
+
+
+def absdiff_halves(e):
+    """|e[:B] - e[B:]| of a [2B, D] matrix, differentiable; the gradient w.r.t. e is produced as one buffer."""
+    return AbsDiffFn.apply(e, None)
