@@ -511,6 +511,63 @@ int gim_bn_pool_bwd_dx(const float* dp, const float* z, const float* gamma, cons
 int gim_absdiff_bwd(const float* a, const float* b, const float* d, float* da, float* db, int64_t n, void* stream);
 int gim_logit_accuracy(const float* logits, int n_pos, int n, float* out, void* stream);
 
+/* ---- Training the ArcFace baseline on the IR-SE backbone (baseline_training.py; arcface/models.py:16-84,120-208): every pass of a
+ * training step that is not a convolution.  csrc/irse_train.hip.  Maps are fp32 NHWC, given as M rows of C channels (M = N * H * W;
+ * BatchNorm1d: M = B), C % 4 == 0, every map / per-channel pointer 16-byte aligned; the head's matrices are [rows][cols] with any
+ * column count.  All launches on `stream`; nothing allocates, nothing uses float atomics: a sum over the rows of a map goes
+ * through `partials` (3 * gim_bn_slabs(M) * C floats, owned by the caller) as in bn_train.hip, so two runs are bit-identical.
+ * Labels are int64, one per row; a label outside [0, N) selects no column (its loss is NaN).
+ *
+ *   gim_bn_apply_fwd  : y = (z - mean) * invstd * gamma + beta with the statistics of gim_bn_stats(M, C); slope != NULL: the per-
+ *       channel PReLU behind it (input_layer: conv -> BN -> PReLU), y = y > 0 ? y : slope[c] * y.
+ *   gim_bn_bwd_reduce : dbeta[c] = sum dyhat, dgamma[c] = sum dyhat * xhat, dyhat = dy (through the PReLU when slope != NULL, then
+ *       also dslope[c] = sum_{yhat <= 0} dy * yhat); acc_* (each may be NULL): the same sums are also ADDED there (a parameter's
+ *       .grad in the optimizer's bucket).
+ *   gim_bn_bwd_dx     : dz = gamma * invstd * (dyhat - dbeta / M - xhat * dgamma / M).
+ *   gim_prelu_fwd / gim_prelu_bwd : y = x > 0 ? x : slope[c] * x (slopes of any sign; slope == NULL: ReLU); backward in one pass:
+ *       dx = dy * (x > 0 ? 1 : slope[c]) (x == 0 takes the slope, as torch does) and dslope[c] = sum_{x <= 0} dy * x
+ *       (partials / dslope / acc_dslope only with a slope).
+ *   gim_se_tail_bwd   : backward of gim_se_tail's out = res * sigmoid(gate[n][c]) + shortcut: dres = dout * sigmoid(gate),
+ *       dgate[n][c] = sig (1 - sig) * sum_pixels dout * res; one workgroup per (image, 64 channels).  The shortcut's gradient is
+ *       dout itself (sstride 1) or gim_subsample2_bwd(dout) (sstride 2).
+ *   gim_subsample2_fwd / _bwd : y[n][i][j] = x[n][2 i][2 j]; H, W (even) are the size of x / dx.  The backward writes every element
+ *       of dx exactly once, zeros included.
+ *   gim_dropout       : y = x * keep / (1 - p), keep = (hash(seed, offset + element index) >= p) computed in registers; the
+ *       backward is the same call on dy.  p == 0 copies x exactly.  n % 4 == 0.
+ *   gim_l2norm_rows_bwd : backward of gim_l2norm_rows: dx = (dy - x <dy, x> / |x|^2) / |x| per row of [B][D], D % 4 == 0.
+ *   gim_col_l2norm_fwd / _bwd : l2_norm(kernel, axis = 0) of the head's [E][N] matrix: out[:, j] = k[:, j] / |k[:, j]|;
+ *       dk = (dn - n * sum_rows dn * n) / |k|.
+ *   gim_arcface_margin_fwd / _bwd : ArcfaceHead.forward on the [B][N] cosine matrix: c = clamp(cos, -1, 1); the label column becomes
+ *       c * cos_m - sqrt(1 - c^2) * sin_m, or c - mm where c - threshold <= 0; everything times s.  Backward: 0 outside [-1, 1],
+ *       s * (cos_m + sin_m * c / sqrt(1 - c^2)) on the first branch, s elsewhere.
+ *   gim_softmax_ce_fwd / _bwd : one workgroup per row: loss[b] = lse[b] - logits[b][label[b]], correct[b] = (first arg-max ==
+ *       label[b]) as 0 / 1, lse[b] kept for the backward dlogits = (exp(logits - lse) - onehot) * dloss[b]. */
+int gim_bn_apply_fwd(const float* z, const float* gamma, const float* beta, const float* mean, const float* invstd, const float* slope,
+                     float* y, int64_t M, int C, void* stream);
+int gim_bn_bwd_reduce(const float* dy, const float* z, const float* gamma, const float* beta, const float* mean, const float* invstd,
+                      const float* slope, float* partials, float* dgamma, float* dbeta, float* dslope, float* acc_dgamma,
+                      float* acc_dbeta, float* acc_dslope, int64_t M, int C, void* stream);
+int gim_bn_bwd_dx(const float* dy, const float* z, const float* gamma, const float* beta, const float* mean, const float* invstd,
+                  const float* slope, const float* dgamma, const float* dbeta, float* dz, int64_t M, int C, void* stream);
+int gim_prelu_fwd(const float* x, const float* slope, float* y, int64_t M, int C, void* stream);
+int gim_prelu_bwd(const float* dy, const float* x, const float* slope, float* dx, float* partials, float* dslope, float* acc_dslope,
+                  int64_t M, int C, void* stream);
+int gim_se_tail_bwd(const float* dout, const float* res, const float* gate, float* dres, float* dgate, int N, int Ho, int Wo, int C,
+                    void* stream);
+int gim_subsample2_fwd(const float* x, float* y, int N, int H, int W, int C, void* stream);
+int gim_subsample2_bwd(const float* dy, float* dx, int N, int H, int W, int C, void* stream);
+int gim_dropout(const float* x, float* y, int64_t n, float p, uint64_t seed, uint64_t offset, void* stream);
+int gim_l2norm_rows_bwd(const float* dy, const float* x, float* dx, int B, int D, void* stream);
+int gim_col_l2norm_fwd(const float* k, float* out, int E, int N, void* stream);
+int gim_col_l2norm_bwd(const float* dn, const float* k, float* dk, int E, int N, void* stream);
+int gim_arcface_margin_fwd(const float* cosv, const int64_t* label, float* out, int B, int N, float s, float cos_m, float sin_m, float mm,
+                           float threshold, void* stream);
+int gim_arcface_margin_bwd(const float* dout, const float* cosv, const int64_t* label, float* dcos, int B, int N, float s, float cos_m,
+                           float sin_m, float mm, float threshold, void* stream);
+int gim_softmax_ce_fwd(const float* logits, const int64_t* label, float* loss, float* correct, float* lse, int B, int N, void* stream);
+int gim_softmax_ce_bwd(const float* dloss, const float* logits, const int64_t* label, const float* lse, float* dlogits, int B, int N,
+                       void* stream);
+
 /* Stream self-check: one wave busy for `usec` microseconds (1 .. 5000, constant 100 MHz wall clock) on `stream`.  The host
  * launches one per engine stream at the same moment and event-times the total: streams that share a HIP hardware queue serialize
  * (nn.DataParallel's one-thread-per-device streams of training/gim_img_training.py:406-411 have no such aliasing to check). */

@@ -45,7 +45,8 @@ from .ingest import ImagePack, pack_directory, pack_omniglot, resample_table, re
 from .gim_img_training import (au_eval_step, au_train_step, eval_step, gim_step, im_eval_step, im_train_step, train_epoch,
                                train_gim_imgs)
 from .baselines import ArcFace, Backbone, ProtonetEmbeddingNet, SiameseNet
-from .baseline_training import PairSampler, SiameseTrainer, siamese_forward_train, train_siamese
+from .baseline_training import (ArcFaceTrainer, IdentitySampler, PairSampler, SiameseTrainer, arcface_forward_train, margin_softmax_loss,
+                                siamese_forward_train, top1_accuracy, train_arcface, train_siamese)
 from .training_logger import Logger
 from .optim import FusedAdam
 from .training_utils import CheckpointIO, DataParallelMock, EpisodeParallel, GlobalStep, adjust_batch_size, pin_rank_to_cores
@@ -57,4 +58,5 @@ __all__ = [
     "pin_rank_to_cores", "stream_concurrency_check", "hw_queues_state", "ProtonetEmbeddingNet", "SiameseNet", "Backbone", "ArcFace",
     "ImagePack", "pack_directory", "pack_omniglot", "resample_table", "resize_images",
     "PairSampler", "SiameseTrainer", "siamese_forward_train", "train_siamese",
+    "IdentitySampler", "ArcFaceTrainer", "arcface_forward_train", "margin_softmax_loss", "top1_accuracy", "train_arcface",
 ]

@@ -6,7 +6,7 @@ tensor the call raises.  Build the library with ``python -c "import __graft_entr
 """
 import ctypes
 import os
-from ctypes import POINTER, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import POINTER, c_float, c_int, c_int32, c_int64, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GIM_LIB_PATH") or os.path.join(_HERE, "csrc", "libgim_hip.so")  # override: timing experiments
@@ -140,6 +140,22 @@ SIGNATURES = {
     "gim_bn_pool_bwd_dx": [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "gim_absdiff_bwd": [P, P, P, P, P, c_int64, P],
     "gim_logit_accuracy": [P, c_int, c_int, P, P],
+    "gim_bn_apply_fwd": [P, P, P, P, P, P, P, c_int64, c_int, P],
+    "gim_bn_bwd_reduce": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int, P],
+    "gim_bn_bwd_dx": [P, P, P, P, P, P, P, P, P, P, c_int64, c_int, P],
+    "gim_prelu_fwd": [P, P, P, c_int64, c_int, P],
+    "gim_prelu_bwd": [P, P, P, P, P, P, P, c_int64, c_int, P],
+    "gim_se_tail_bwd": [P, P, P, P, P, c_int, c_int, c_int, c_int, P],
+    "gim_subsample2_fwd": [P, P, c_int, c_int, c_int, c_int, P],
+    "gim_subsample2_bwd": [P, P, c_int, c_int, c_int, c_int, P],
+    "gim_dropout": [P, P, c_int64, c_float, c_uint64, c_uint64, P],
+    "gim_l2norm_rows_bwd": [P, P, P, c_int, c_int, P],
+    "gim_col_l2norm_fwd": [P, P, c_int, c_int, P],
+    "gim_col_l2norm_bwd": [P, P, P, c_int, c_int, P],
+    "gim_arcface_margin_fwd": [P, P, P, c_int, c_int, c_float, c_float, c_float, c_float, c_float, P],
+    "gim_arcface_margin_bwd": [P, P, P, P, c_int, c_int, c_float, c_float, c_float, c_float, c_float, P],
+    "gim_softmax_ce_fwd": [P, P, P, P, P, c_int, c_int, P],
+    "gim_softmax_ce_bwd": [P, P, P, P, P, c_int, c_int, P],
     "gim_version": [],
 }
 

@@ -13,7 +13,12 @@ and values, with no permutation to undo.  (The inference path reads the (h, w, c
 its parameters, baselines.SiameseNet._derive.)
 
 Both inputs of a pair batch go through the encoder in ONE pass, so the batch statistics are over 2B images:
-``classify(*encode(cat([x1, x2])).chunk(2))`` on the reference's modules.  Single GPU, fp32 matrix path."""
+``classify(*encode(cat([x1, x2])).chunk(2))`` on the reference's modules.  Single GPU, fp32 matrix path.
+
+The second half of the file trains the ArcFace baseline (``baselines.ArcFace`` on the IR-SE ``Backbone``: ``baselines/arcface/models.py``)
+the same way: ``arcface_forward_train`` is the reference's ``ArcFace.forward(x, label)`` in training mode over the inference classes'
+parameters (csrc/irse_train.hip for everything but the convolutions, which all run at stride 1 through ``ops.conv2d``),
+``train_arcface`` writes ``ckpts/model_*.pt['arcface']`` and the ``args.json`` that ``get_arcface_authenticator`` reads."""
 import json
 import os
 
@@ -24,7 +29,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib, ops
 from ._lib import check
-from .baselines import ProtonetEmbeddingNet, SiameseNet
+from .baselines import ArcFace, Backbone, ProtonetEmbeddingNet, SiameseNet
 from .optim import FusedAdam
 from .training_logger import Logger
 from .training_utils import get_latest_ckpt
@@ -260,4 +265,259 @@ def train_siamese(device, bank, out_dir, n_iters, batch_size=128, lr=1e-3, log_e
             saved = step
     if saved != step or not os.path.isdir(ckpt_dir):
         _save(trainer, out_dir, step)
+    return trainer
+
+
+# ------------------------------------------------------------------------------------------------------
+# ArcFace on the IR-SE backbone (baselines.ArcFace: arcface/models.py:62-84,120-164,170-229), training mode
+# ------------------------------------------------------------------------------------------------------
+ARC_S, ARC_M = 64.0, 0.5      # ArcfaceHead's scale and margin (arcface/models.py:172)
+
+
+def _bn_train(x, bn, slope=None):
+    return ops.batch_norm(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps, slope)
+
+
+def irse_unit_train(unit, x):
+    """One bottleneck_IR_SE (a baselines._Unit) with batch statistics on an NHWC map.  Every convolution runs at stride 1: the
+    stride-2 3x3 convolution (padding 1) is the even-position subsample of the stride-1 one, the strided 1x1 shortcut convolution
+    the 1x1 convolution of the subsampled input.  The SE bottleneck's two 1x1 convolutions run on the [N, 1, 1, C] squeeze with the
+    nn.Conv2d parameters themselves (their gradients land in the optimizer's bucket), the ReLU between them as ops.prelu without a
+    slope."""
+    r = unit.res_layer
+    h = ops.conv2d(_bn_train(x, r[0]), r[1].weight)
+    h = ops.conv2d(ops.prelu(h, r[2].weight), r[3].weight)
+    if unit.stride == 2:
+        h = ops.subsample2(h)
+    h = _bn_train(h, r[4])
+    N, Ho, Wo, C = h.shape
+    z = ops.mean_dim1(h.view(N, Ho * Wo, C)).view(N, 1, 1, C)
+    gate = ops.conv2d(ops.prelu(ops.conv2d(z, r[5].fc1.weight), None), r[5].fc2.weight).view(N, C)
+    if unit.cin == unit.depth:
+        return ops.se_tail_train(h, gate, x, unit.stride)
+    xs = ops.subsample2(x) if unit.stride == 2 else x
+    sc = _bn_train(ops.conv2d(xs, unit.shortcut_layer[0].weight), unit.shortcut_layer[1])
+    return ops.se_tail_train(h, gate, sc, 1)
+
+
+def arcface_forward_train(model, x, label, dropout=None):
+    """(emb [B, 512], logits [B, classes]) of a baselines.ArcFace as the reference's ``ArcFace.forward(x, label)`` gives them in
+    training mode: batch statistics in every BatchNorm (running statistics updated), the margin head on the normalised embedding.
+    dropout: (seed, it) - the mask of ``output_layer.1`` is a hash of (seed, it, element), nothing is stored; None: no dropout
+    (required when the backbone's drop ratio is 0, an error otherwise).  Differentiable in every parameter; the model's ``training``
+    flag is neither read nor changed.  label: int64 [B] on the device."""
+    if not isinstance(model, ArcFace) or not isinstance(model.emb_model, Backbone):
+        raise TypeError("arcface_forward_train runs a baselines.ArcFace on a baselines.Backbone")
+    net = model.emb_model
+    dims = (net.img_channels, net.img_size, net.img_size)
+    x = ops._req(x, "x")
+    if x.dim() != 4 or tuple(x.shape[1:]) != dims:
+        raise RuntimeError("expected [B, %d, %d, %d] images, got %s" % (dims + (tuple(x.shape),)))
+    B = x.shape[0]
+    if B < 2:
+        raise RuntimeError("batch statistics need at least two images")
+    if not (torch.is_tensor(label) and label.is_cuda and label.dtype == torch.int64 and tuple(label.shape) == (B,)):
+        raise RuntimeError("label must be a CUDA int64 tensor of shape [B = %d]" % B)
+    p = float(net.output_layer[1].p)
+    if p > 0.0 and dropout is None:
+        raise RuntimeError("the backbone drops %.2f of output_layer.1: pass dropout=(seed, it)" % p)
+    h = ops.conv2d(ops.to_nhwc(x), net.input_layer[0].weight)
+    h = _bn_train(h, net.input_layer[1], net.input_layer[2].weight)
+    for unit in net.body:
+        h = irse_unit_train(unit, h)
+    out = net.output_layer
+    h = _bn_train(h, out[0])
+    if p > 0.0:
+        seed, it = dropout
+        h = ops.dropout(h, p, int(seed), int(it) * h.numel())
+    e = ops.to_nchw(h).view(B, -1)      # the reference's (c, h, w) flatten order
+    e = _bn_train(ops.linear(e, out[3].weight, out[3].bias), out[4])
+    emb = ops.l2norm_rows_train(e)
+    cos = ops.BgemmFn.apply(emb[None], ops.col_l2norm(model.head.kernel)[None], 0, 0)[0]
+    return emb, ops.arc_margin(cos, label, ARC_S, ARC_M)
+
+
+def _row_mean(v):
+    return ops.SumDim1Fn.apply(v.view(1, -1, 1), 1.0 / v.numel())
+
+
+def margin_softmax_loss_and_accuracy(logits, label):
+    """(mean cross-entropy of the margin logits, a differentiable [1] tensor; top-1 accuracy, a device scalar) from ONE pass over
+    the logits: the cross-entropy kernel also writes whether each row's first largest logit is the label's."""
+    per, correct = ops.softmax_ce(logits, label)
+    return _row_mean(per).view(1), _row_mean(correct).view(())
+
+
+def margin_softmax_loss(logits, label):
+    """Mean cross-entropy of the margin logits over the batch: a [1] tensor."""
+    return margin_softmax_loss_and_accuracy(logits, label)[0]
+
+
+def top1_accuracy(logits, label):
+    """Share of rows whose first largest logit is the label's; a device scalar."""
+    return margin_softmax_loss_and_accuracy(logits.detach(), label)[1]
+
+
+class ArcFaceTrainer:
+    """One FusedAdam over every parameter of a baselines.ArcFace, in the reference's parameter order (head.kernel last).
+    seed (>= 0): the dropout mask of output_layer.1 is a hash of (seed, iteration, element); train_arcface passes its own seed."""
+
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), seed=0):
+        if not isinstance(model, ArcFace):
+            raise TypeError("ArcFaceTrainer trains a baselines.ArcFace")
+        self.model = model
+        self.opt = FusedAdam(model.parameters(), lr=lr, betas=betas)
+        if int(seed) < 0:
+            raise ValueError("ArcFaceTrainer: seed must not be negative (it keys the dropout hash)")
+        self.seed = int(seed)
+        self._one = None
+        self.last_logits = None      # [B, classes] margin logits of the latest train_step (before its update), detached
+        self.last_emb = None
+
+    def _drop_inference_caches(self):
+        self.model.emb_model._derived = None
+
+    def train_step(self, x, label, it):
+        """One Adam update on the class-labelled batch (x, label); `it` keys the dropout mask.  Returns (loss, accuracy) of the batch
+        before the update, as device scalars: nothing is read back here."""
+        if ops.matrix_path() != "fp32":
+            raise RuntimeError("ArcFaceTrainer runs on the fp32 matrix path only (ops.set_matrix_path('fp32')): the fp16 path and its "
+                               "loss scale are not implemented for the baseline")
+        self.opt.zero_grad()
+        p = float(self.model.emb_model.output_layer[1].p)
+        emb, logits = arcface_forward_train(self.model, x, label, (self.seed, it) if p > 0.0 else None)
+        loss, acc = margin_softmax_loss_and_accuracy(logits, label)
+        if self._one is None or self._one.device != loss.device:
+            self._one = torch.ones(1, device=loss.device, dtype=torch.float32)
+        with ops.caller_thread_backward():
+            loss.backward(self._one)
+        self.opt.step()
+        self._drop_inference_caches()
+        self.last_logits, self.last_emb = logits.detach(), emb.detach()
+        return loss.detach().view(()), acc
+
+    def state_dict(self):
+        """{'model': the reference's ArcFace state dict (names, shapes, order; on the host), 'opt': torch.optim.Adam's format}."""
+        return {"model": {k: v.detach().to("cpu").contiguous() for k, v in self.model.state_dict().items()}, "opt": self.opt.state_dict()}
+
+    def load_state_dict(self, sd):
+        self.model.load_state_dict(sd["model"], strict=True)
+        if sd.get("opt") is not None:
+            self.opt.load_state_dict(sd["opt"])
+        self._drop_inference_caches()
+
+
+class IdentitySampler:
+    """Class-labelled batches over a data.EpisodeBank, the ``ArcfaceDataSet.__getitem__`` contract (data_handling/img_datasets.py:
+    217-270): the class uniform over the bank's (non-empty) classes, the image uniform within the class, a horizontal flip with
+    probability 1/2 when bank.mirror.  Host logic only; the draws of iteration `it` depend on (seed, it) alone.  Labels are positions
+    in the bank's class list (0 .. n_classes - 1).  Reads bank.offsets and bank.mirror (and bank.gather in batch())."""
+
+    def __init__(self, bank, batch_size, seed=0):
+        self.bank = bank
+        self.offsets = np.asarray(bank.offsets, dtype=np.int64)
+        self.sizes = np.diff(self.offsets)
+        self.n_classes = len(self.sizes)
+        self.classes = np.nonzero(self.sizes >= 1)[0]
+        self.batch_size, self.seed = int(batch_size), int(seed)
+        self.mirror = bool(bank.mirror)
+        if self.batch_size < 2:
+            raise ValueError("IdentitySampler: batch_size must be at least 2 (batch statistics)")
+        if not len(self.classes):
+            raise ValueError("IdentitySampler: the bank has no images")
+
+    def draw(self, it):
+        """(idx [B] int32 image indices, flip [B] uint8, label [B] int64) of iteration `it`."""
+        rng = np.random.default_rng([self.seed, 0xA2CF, int(it)])
+        B = self.batch_size
+        label = self.classes[rng.integers(len(self.classes), size=B)].astype(np.int64)
+        pos = rng.integers(self.sizes[label])      # one bound per row: uniform within the row's class
+        idx = (self.offsets[label] + pos).astype(np.int32)
+        flip = (rng.random(B) < 0.5) if self.mirror else np.zeros(B, dtype=bool)
+        return idx, flip.astype(np.uint8), label
+
+    def batch(self, it):
+        """(x [B, C, S, S], label int64 [B]) on the bank's device."""
+        idx, flip, label = self.draw(it)
+        x = self.bank.gather(idx, flip)
+        return x, torch.from_numpy(label).to(x.device, non_blocking=True)
+
+
+def _save_arcface(trainer, out_dir, step):
+    ckpt_dir = os.path.join(out_dir, CHECKPOINT_DIR)
+    os.makedirs(ckpt_dir, exist_ok=True)
+    path = os.path.join(ckpt_dir, "model_%08d.pt" % step)
+    tmp = path + ".tmp.%d" % os.getpid()
+    sd = trainer.state_dict()
+    torch.save({"arcface": sd["model"], "opt": sd["opt"], "global_step": step}, tmp)
+    os.replace(tmp, path)
+    return path
+
+
+def train_arcface(device, bank, out_dir, n_iters, num_layers=50, batch_size=128, lr=1e-4, drop_ratio=0.6, th=1.5, log_every=100,
+                  save_every=1000, seed=0, logger=None):
+    """Train an ArcFace baseline (IR-SE backbone, 512-d embedding, one class per class of `bank`) on the class-labelled batches of
+    `bank` up to iteration n_iters; resumes from the latest checkpoint of out_dir and then sees the batches and dropout masks the
+    uninterrupted run saw.  Writes out_dir/args.json (what authentication_eval.get_arcface_authenticator reads: img_size,
+    img_channels, num_layers, dropout, emb_dim, th) and out_dir/ckpts/model_%08d.pt = {'arcface', 'opt', 'global_step'} every
+    save_every iterations and at the end; logs ('arcface', 'loss' / 'acc') every log_every iterations.  Returns the trainer.
+
+    th is stored as given: the decision threshold of ArcFace.predict on the score -|e1 - e2|^2 <= 0.  The reference's default of 1.5
+    can never be reached by such a score; calibrating it (on held-out pairs) is not part of the training."""
+    device = torch.device(device)
+    if num_layers not in (50, 100, 152):
+        raise ValueError("train_arcface: num_layers should be 50, 100 or 152")
+    if int(bank.S) not in (32, 64):
+        raise ValueError("train_arcface: the backbone takes 32 x 32 or 64 x 64 images, the bank has %d" % int(bank.S))
+    if not 0.0 <= drop_ratio < 1.0:
+        raise ValueError("train_arcface: drop_ratio must be in [0, 1)")
+    if int(batch_size) < 2:
+        raise ValueError("train_arcface: batch_size must be at least 2 (batch statistics)")
+    if n_iters < 0:
+        raise ValueError("train_arcface: n_iters must not be negative")
+    if int(seed) < 0:
+        raise ValueError("train_arcface: seed must not be negative (it keys the sampler and the dropout hash)")
+    n_classes = len(bank.offsets) - 1
+    if n_classes < 2:
+        raise ValueError("train_arcface: the margin softmax needs at least two classes, the bank has %d" % n_classes)
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "args.json"), "w") as f:
+        json.dump({"baseline_type": "arcface", "img_size": int(bank.S), "img_channels": int(bank.C), "num_layers": int(num_layers),
+                   "dropout": float(drop_ratio), "emb_dim": 512, "th": float(th), "n_classes": n_classes, "batch_size": int(batch_size),
+                   "lr": float(lr), "seed": int(seed), "n_iters": int(n_iters)}, f)
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(seed)
+        model = ArcFace(Backbone(num_layers, drop_ratio, 'ir_se', int(bank.S), int(bank.C)), 512, n_classes, th=th)
+        with torch.no_grad():      # ArcfaceHead's initial kernel (arcface/models.py:177): uniform columns of unit norm
+            model.head.kernel.uniform_(-1, 1).renorm_(2, 1, 1e-5).mul_(1e5)
+    trainer = ArcFaceTrainer(model.to(device), lr=lr, seed=seed)
+    step = 0
+    ckpt_dir = os.path.join(out_dir, CHECKPOINT_DIR)
+    if os.path.isdir(ckpt_dir):
+        try:
+            latest = get_latest_ckpt(ckpt_dir)
+        except FileNotFoundError:
+            latest = None
+        if latest is not None:
+            sd = torch.load(latest, map_location="cpu", weights_only=False)
+            trainer.load_state_dict({"model": sd["arcface"], "opt": sd.get("opt")})
+            step = int(sd["global_step"])
+            print("Resuming arcface training from iteration {}".format(step))
+    if logger is None:
+        logger = Logger(log_dir=os.path.join(out_dir, "logs"), img_dir=os.path.join(out_dir, "imgs"))
+    sampler = IdentitySampler(bank, batch_size, seed)
+    saved = step
+    while step < n_iters:
+        x, label = sampler.batch(step)
+        loss, acc = trainer.train_step(x, label, step)
+        step += 1
+        if log_every and step % log_every == 0:
+            loss_v, acc_v = torch.stack([loss, acc]).tolist()
+            logger.add_scalar(category="arcface", k="loss", v=loss_v, global_step=step)
+            logger.add_scalar(category="arcface", k="acc", v=acc_v, global_step=step)
+        if save_every and step % save_every == 0:
+            _save_arcface(trainer, out_dir, step)
+            saved = step
+    if saved != step or not os.path.isdir(ckpt_dir):
+        _save_arcface(trainer, out_dir, step)
     return trainer

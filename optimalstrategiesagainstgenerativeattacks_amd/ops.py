@@ -2385,3 +2385,370 @@ def absdiff_train(a, b):
 def absdiff_halves(e):
     """|e[:B] - e[B:]| of a [2B, D] matrix, differentiable; the gradient w.r.t. e is produced as one buffer."""
     return AbsDiffFn.apply(e, None)
+
+
+# --------------------------------------------------------------------------------------------
+# training the ArcFace baseline (baseline_training.py): the passes of an IR-SE training step that are not convolutions, and the
+# margin head (csrc/irse_train.hip).  fp32, one autograd.Function per pass, each once differentiable.  Gradients of per-channel
+# parameters (gamma, beta, PReLU slope) are ADDED into the parameter's .grad where that is the optimizer's bucket (_grad_target),
+# and None goes back to autograd - as BnReluMaxPool2Fn does.
+# --------------------------------------------------------------------------------------------
+def _req_rows(x, what):
+    """x [..., C] with C % 4 == 0, contiguous -> (x, rows, C)."""
+    x = _req(x, what)
+    C = x.shape[-1]
+    if x.dim() < 2 or C % 4:
+        raise RuntimeError("%s must be [..., C] with C %% 4 == 0, got %s" % (what, tuple(x.shape)))
+    return x, x.numel() // C, C
+
+
+def _req_chan(v, name, C):
+    v = _req(v, name)
+    if tuple(v.shape) != (C,):
+        raise RuntimeError("%s must be [C = %d], got %s" % (name, C, tuple(v.shape)))
+    return v
+
+
+def _sum_partials(rows, C, device):
+    return torch.empty(3 * bn_slabs(rows) * C, device=device, dtype=torch.float32)
+
+
+def _req_label(label, B):
+    if not (torch.is_tensor(label) and label.is_cuda and label.dtype == torch.int64 and tuple(label.shape) == (B,)):
+        raise RuntimeError("label must be a CUDA int64 tensor of shape [%d]" % B)
+    return label if label.is_contiguous() else label.contiguous()
+
+
+def bn_stats_rows(z, eps=1e-5, running_mean=None, running_var=None, num_batches_tracked=None, momentum=0.1):
+    """ops.bn_stats for any [..., C] tensor of M >= 2 rows (maps of odd size, BatchNorm1d): (mean [C], invstd [C])."""
+    lib = _lib.load()
+    z, M, C = _req_rows(z, "z")
+    if M < 2:
+        raise RuntimeError("batch statistics need at least two rows, got %s" % (tuple(z.shape),))
+    if momentum is None:
+        raise NotImplementedError("bn_stats_rows: momentum=None (cumulative moving average) is not implemented")
+    for name, v in (("running_mean", running_mean), ("running_var", running_var)):
+        if v is not None and (tuple(_req(v, name).shape) != (C,) or not v.is_contiguous()):
+            raise RuntimeError("bn_stats_rows: %s must be a contiguous [C] tensor" % name)
+    if num_batches_tracked is not None and not (num_batches_tracked.is_cuda and num_batches_tracked.dtype == torch.int64):
+        raise RuntimeError("bn_stats_rows: num_batches_tracked must be a CUDA int64 tensor")
+    stats = torch.empty((2, C), device=z.device, dtype=torch.float32)
+    partials = _bn_partials(M, C, z.device)
+    nbt = None if num_batches_tracked is None else num_batches_tracked.data_ptr()
+    check(lib.gim_bn_stats(_p(z), _p(partials), _p(stats), _p(stats, C), _p(running_mean), _p(running_var), nbt, M, C,
+                           float(momentum), float(eps), _stream()), "bn_stats")
+    return stats[0], stats[1]
+
+
+class BatchNormFn(Function):
+    """y = batch_norm(z) with BATCH statistics over the rows of z [..., C] (nn.BatchNorm2d on an NHWC map, nn.BatchNorm1d on [B, C]
+    in training mode), the running statistics updated in place; slope: the per-channel PReLU behind it, in the same pass.  Saved
+    for backward: z and the two [C] statistics, not the normalised map."""
+
+    @staticmethod
+    def forward(ctx, z, weight, bias, slope, running_mean, running_var, num_batches_tracked, momentum, eps):
+        lib = _lib.load()
+        z, M, C = _req_rows(z, "z")
+        weight, bias = _req_chan(weight, "weight", C), _req_chan(bias, "bias", C)
+        slope = None if slope is None else _req_chan(slope, "slope", C)
+        mean, invstd = bn_stats_rows(z, eps, running_mean, running_var, num_batches_tracked, momentum)
+        y = torch.empty_like(z)
+        check(lib.gim_bn_apply_fwd(_p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(slope), _p(y), M, C, _stream()), "bn_apply_fwd")
+        ctx.save_for_backward(z, weight, bias, mean, invstd, slope)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        lib = _lib.load()
+        z, weight, bias, mean, invstd, slope = ctx.saved_tensors
+        C = z.shape[-1]
+        M = z.numel() // C
+        dy = _req(dy, "dy")
+        st = _stream()
+        sums = torch.empty((3, C), device=z.device, dtype=torch.float32)      # dgamma, dbeta, dslope
+        partials = _sum_partials(M, C, z.device)
+        need = ctx.needs_input_grad
+        acc_w = _grad_target(weight) if need[1] else None
+        acc_b = _grad_target(bias) if need[2] else None
+        acc_s = _grad_target(slope) if (slope is not None and need[3]) else None
+        check(lib.gim_bn_bwd_reduce(_p(dy), _p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(slope), _p(partials), _p(sums),
+                                    _p(sums, C), _p(sums, 2 * C) if slope is not None else None, _p(acc_w), _p(acc_b), _p(acc_s), M, C, st),
+              "bn_bwd_reduce")
+        dz = None
+        if need[0]:
+            dz = torch.empty_like(z)
+            check(lib.gim_bn_bwd_dx(_p(dy), _p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(slope), _p(sums), _p(sums, C), _p(dz),
+                                    M, C, st), "bn_bwd_dx")
+        dw = sums[0] if (need[1] and acc_w is None) else None
+        db = sums[1] if (need[2] and acc_b is None) else None
+        ds = sums[2] if (slope is not None and need[3] and acc_s is None) else None
+        return dz, dw, db, ds, None, None, None, None, None
+
+
+def batch_norm(z, weight, bias, running_mean, running_var, num_batches_tracked, momentum=0.1, eps=1e-5, slope=None):
+    """batch_norm(z, batch statistics) over the rows of z [..., C], optionally followed by prelu(., slope); differentiable in z, weight,
+    bias and slope (once); the running statistics and num_batches_tracked move as nn.BatchNorm's do in training mode."""
+    return BatchNormFn.apply(z, weight, bias, slope, running_mean, running_var, num_batches_tracked, momentum, eps)
+
+
+class PReLUFn(Function):
+    """y = x > 0 ? x : slope[c] * x over the last dim of x [..., C]; slope None: ReLU."""
+
+    @staticmethod
+    def forward(ctx, x, slope):
+        lib = _lib.load()
+        x, M, C = _req_rows(x, "x")
+        slope = None if slope is None else _req_chan(slope, "slope", C)
+        y = torch.empty_like(x)
+        check(lib.gim_prelu_fwd(_p(x), _p(slope), _p(y), M, C, _stream()), "prelu_fwd")
+        ctx.save_for_backward(x, slope)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, slope = ctx.saved_tensors
+        C = x.shape[-1]
+        M = x.numel() // C
+        dy = _req(dy, "dy")
+        dx = torch.empty_like(x)
+        ds = partials = acc = None
+        if slope is not None:
+            ds = torch.empty(C, device=x.device, dtype=torch.float32)
+            partials = _sum_partials(M, C, x.device)
+            acc = _grad_target(slope) if ctx.needs_input_grad[1] else None
+        check(lib.gim_prelu_bwd(_p(dy), _p(x), _p(slope), _p(dx), _p(partials), _p(ds), _p(acc), M, C, _stream()), "prelu_bwd")
+        return dx, (ds if (slope is not None and ctx.needs_input_grad[1] and acc is None) else None)
+
+
+def prelu(x, slope):
+    """nn.PReLU(C) on the last dim (slope [C], any sign), or nn.ReLU when slope is None; differentiable (once)."""
+    return PReLUFn.apply(x, slope)
+
+
+class Subsample2Fn(Function):
+    """y[n, i, j] = x[n, 2 i, 2 j] of an NHWC map with even H and W (MaxPool2d(1, 2); what a stride-2 convolution keeps of the
+    stride-1 one).  The backward scatters into zeros in one pass."""
+
+    @staticmethod
+    def forward(ctx, x):
+        lib = _lib.load()
+        x = _req(x, "x")
+        if x.dim() != 4 or x.shape[1] % 2 or x.shape[2] % 2 or x.shape[3] % 4:
+            raise RuntimeError("subsample2: an NHWC map with even H, W and C %% 4 == 0 expected, got %s" % (tuple(x.shape),))
+        N, H, W, C = x.shape
+        y = torch.empty((N, H // 2, W // 2, C), device=x.device, dtype=torch.float32)
+        check(lib.gim_subsample2_fwd(_p(x), _p(y), N, H, W, C, _stream()), "subsample2_fwd")
+        ctx.cfg = (N, H, W, C)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        N, H, W, C = ctx.cfg
+        dy = _req(dy, "dy")
+        dx = torch.empty((N, H, W, C), device=dy.device, dtype=torch.float32)
+        check(_lib.load().gim_subsample2_bwd(_p(dy), _p(dx), N, H, W, C, _stream()), "subsample2_bwd")
+        return dx
+
+
+def subsample2(x):
+    return Subsample2Fn.apply(x)
+
+
+class SETailFn(Function):
+    """out = res * sigmoid(gate[n, c]) + shortcut[n, ::sstride, ::sstride, c] (the forward is the inference kernel gim_se_tail)."""
+
+    @staticmethod
+    def forward(ctx, res, gate, shortcut, sstride):
+        lib = _lib.load()
+        res, gate, shortcut = _req(res, "res"), _req(gate, "gate"), _req(shortcut, "shortcut")
+        N, Ho, Wo, C = res.shape
+        if sstride not in (1, 2) or tuple(shortcut.shape) != (N, Ho * sstride, Wo * sstride, C) or tuple(gate.shape) != (N, C):
+            raise RuntimeError("se_tail_train: shortcut %s / gate %s do not match res %s at sstride %s"
+                               % (tuple(shortcut.shape), tuple(gate.shape), tuple(res.shape), sstride))
+        out = torch.empty_like(res)
+        check(lib.gim_se_tail(_p(res), _p(gate), _p(shortcut), None, None, _p(out), None, N, Ho, Wo, C, sstride, _stream()), "se_tail")
+        ctx.save_for_backward(res, gate)
+        ctx.sstride = sstride
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        lib = _lib.load()
+        res, gate = ctx.saved_tensors
+        N, Ho, Wo, C = res.shape
+        dout = _req(dout, "dout")
+        st = _stream()
+        dres, dgate = torch.empty_like(res), torch.empty_like(gate)
+        check(lib.gim_se_tail_bwd(_p(dout), _p(res), _p(gate), _p(dres), _p(dgate), N, Ho, Wo, C, st), "se_tail_bwd")
+        dsc = None
+        if ctx.needs_input_grad[2]:
+            if ctx.sstride == 1:
+                dsc = dout
+            else:
+                dsc = torch.empty((N, 2 * Ho, 2 * Wo, C), device=dout.device, dtype=torch.float32)
+                check(lib.gim_subsample2_bwd(_p(dout), _p(dsc), N, 2 * Ho, 2 * Wo, C, st), "subsample2_bwd")
+        return dres, dgate, dsc, None
+
+
+def se_tail_train(res, gate, shortcut, sstride=1):
+    """The end of an IR-SE unit, differentiable in res, gate and shortcut (ops.se_tail is the inference operator)."""
+    return SETailFn.apply(res, gate, shortcut, sstride)
+
+
+class DropoutFn(Function):
+    """y = x * keep / (1 - p); keep is a hash of (seed, offset + element index): the backward recomputes it, no mask is stored."""
+
+    @staticmethod
+    def forward(ctx, x, p, seed, offset):
+        x = _req(x, "x")
+        if not 0.0 <= p < 1.0 or x.numel() % 4 or seed < 0 or offset < 0:
+            raise RuntimeError("dropout: p in [0, 1), numel %% 4 == 0 and non-negative seed / offset expected")
+        y = torch.empty_like(x)
+        check(_lib.load().gim_dropout(_p(x), _p(y), x.numel(), p, seed, offset, _stream()), "dropout")
+        ctx.cfg = (p, seed, offset)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        p, seed, offset = ctx.cfg
+        dy = _req(dy, "dy")
+        dx = torch.empty_like(dy)
+        check(_lib.load().gim_dropout(_p(dy), _p(dx), dy.numel(), p, seed, offset, _stream()), "dropout")
+        return dx, None, None, None
+
+
+def dropout(x, p, seed, offset=0):
+    """nn.Dropout(p) in training mode with the mask keyed by (seed, offset + element index); p == 0 copies x."""
+    return DropoutFn.apply(x, float(p), int(seed), int(offset))
+
+
+class L2NormRowsFn(Function):
+    """x / |x| per row of [B, D]."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = _req(x, "x")
+        if x.dim() != 2 or x.shape[1] % 4:
+            raise RuntimeError("l2norm_rows_train: [B, D] with D %% 4 == 0 expected, got %s" % (tuple(x.shape),))
+        y = torch.empty_like(x)
+        check(_lib.load().gim_l2norm_rows(_p(x), _p(y), x.shape[0], x.shape[1], _stream()), "l2norm_rows")
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        dy = _req(dy, "dy")
+        dx = torch.empty_like(x)
+        check(_lib.load().gim_l2norm_rows_bwd(_p(dy), _p(x), _p(dx), x.shape[0], x.shape[1], _stream()), "l2norm_rows_bwd")
+        return dx
+
+
+def l2norm_rows_train(x):
+    """x / |x| per row, differentiable (ops.l2norm_rows is the inference operator)."""
+    return L2NormRowsFn.apply(x)
+
+
+class ColL2NormFn(Function):
+    """k / |k[:, j]| per COLUMN of k [E, N] (l2_norm(kernel, axis=0) of the ArcFace head)."""
+
+    @staticmethod
+    def forward(ctx, k):
+        k = _req(k, "kernel")
+        if k.dim() != 2:
+            raise RuntimeError("col_l2norm: an [E, N] matrix expected, got %s" % (tuple(k.shape),))
+        out = torch.empty_like(k)
+        check(_lib.load().gim_col_l2norm_fwd(_p(k), _p(out), k.shape[0], k.shape[1], _stream()), "col_l2norm_fwd")
+        ctx.save_for_backward(k)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dn):
+        (k,) = ctx.saved_tensors
+        dn = _req(dn, "dn")
+        dk = torch.empty_like(k)
+        check(_lib.load().gim_col_l2norm_bwd(_p(dn), _p(k), _p(dk), k.shape[0], k.shape[1], _stream()), "col_l2norm_bwd")
+        return dk
+
+
+def col_l2norm(k):
+    return ColL2NormFn.apply(k)
+
+
+def _margin_consts(s, m):
+    return float(s), math.cos(m), math.sin(m), math.sin(m) * m, math.cos(math.pi - m)
+
+
+class ArcMarginFn(Function):
+    """ArcfaceHead.forward behind the cosine matrix: clamp to [-1, 1], the label column through the additive angular margin m
+    (cos(theta + m), or cos - m sin m where theta + m would leave [0, pi]), everything times s."""
+
+    @staticmethod
+    def forward(ctx, cos, label, s, m):
+        cos = _req(cos, "cos")
+        if cos.dim() != 2:
+            raise RuntimeError("arc_margin: a [B, classes] cosine matrix expected, got %s" % (tuple(cos.shape),))
+        B, N = cos.shape
+        label = _req_label(label, B)
+        out = torch.empty_like(cos)
+        check(_lib.load().gim_arcface_margin_fwd(_p(cos), label.data_ptr(), _p(out), B, N, *_margin_consts(s, m), _stream()), "arcface_margin_fwd")
+        ctx.save_for_backward(cos, label)
+        ctx.cfg = (s, m)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        cos, label = ctx.saved_tensors
+        B, N = cos.shape
+        dout = _req(dout, "dout")
+        dcos = torch.empty_like(cos)
+        check(_lib.load().gim_arcface_margin_bwd(_p(dout), _p(cos), label.data_ptr(), _p(dcos), B, N, *_margin_consts(*ctx.cfg), _stream()),
+              "arcface_margin_bwd")
+        return dcos, None, None, None
+
+
+def arc_margin(cos, label, s=64.0, m=0.5):
+    return ArcMarginFn.apply(cos, label, s, m)
+
+
+class SoftmaxCEFn(Function):
+    """(loss [B], correct [B]) of logits [B, classes] and int64 labels [B]: loss_b = logsumexp(row) - row[label], correct_b = 1.0
+    where the row's first largest logit is the label's.  Only loss is differentiable."""
+
+    @staticmethod
+    def forward(ctx, logits, label):
+        logits = _req(logits, "logits")
+        if logits.dim() != 2:
+            raise RuntimeError("softmax_ce: [B, classes] logits expected, got %s" % (tuple(logits.shape),))
+        B, N = logits.shape
+        label = _req_label(label, B)
+        out = torch.empty((3, B), device=logits.device, dtype=torch.float32)      # loss, correct, lse
+        check(_lib.load().gim_softmax_ce_fwd(_p(logits), label.data_ptr(), _p(out), _p(out, B), _p(out, 2 * B), B, N, _stream()), "softmax_ce_fwd")
+        loss, correct = out[0], out[1]
+        ctx.save_for_backward(logits, label, out[2])
+        ctx.mark_non_differentiable(correct)
+        return loss, correct
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dloss, _dcorrect):
+        logits, label, lse = ctx.saved_tensors
+        B, N = logits.shape
+        dloss = _req(dloss, "dloss")
+        dlogits = torch.empty_like(logits)
+        check(_lib.load().gim_softmax_ce_bwd(_p(dloss), _p(logits), label.data_ptr(), _p(lse), _p(dlogits), B, N, _stream()), "softmax_ce_bwd")
+        return dlogits, None
+
+
+def softmax_ce(logits, label):
+    """-> (loss [B], correct [B])."""
+    return SoftmaxCEFn.apply(logits, label)
