@@ -122,41 +122,41 @@ def pair_accuracy(logits, n_pos):
     return out.view(())
 
 
-class SiameseTrainer:
-    """One FusedAdam over every parameter of a baselines.SiameseNet, in the reference's parameter order."""
+class _BaselineTrainer:
+    """One FusedAdam over every parameter of a baseline model, in the reference's parameter order.  A subclass names its model class
+    (MODEL) and supplies _loss_and_accuracy (the training forward; it may keep what it wants of it, as last_logits) and
+    _inference_caches (the modules whose derived inference parameters an update makes stale)."""
 
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999)):
-        if not isinstance(model, SiameseNet):
-            raise TypeError("SiameseTrainer trains a baselines.SiameseNet")
+    MODEL = None
+
+    def __init__(self, model, lr, betas):
+        if not isinstance(model, self.MODEL):
+            raise TypeError("%s trains a baselines.%s" % (type(self).__name__, self.MODEL.__name__))
         self.model = model
         self.opt = FusedAdam(model.parameters(), lr=lr, betas=betas)
         self._one = None
-        self.last_logits = None      # [B, 1] logits of the latest train_step (before its update), detached
 
     def _drop_inference_caches(self):
-        self.model._derived = None
-        self.model.embedding_net._derived = None
+        for m in self._inference_caches():
+            m._derived = None
 
-    def train_step(self, x1, x2, n_pos):
-        """One Adam update on the pair batch (x1[i], x2[i]); rows < n_pos are same-class pairs.  Returns (loss, accuracy) of the
-        batch before the update, as device scalars: nothing is read back here."""
+    def _update(self, *batch):
+        """One Adam update; (loss, accuracy) of the batch before it, as device scalars: nothing is read back here."""
         if ops.matrix_path() != "fp32":
-            raise RuntimeError("SiameseTrainer runs on the fp32 matrix path only (ops.set_matrix_path('fp32')): the fp16 path and its "
-                               "loss scale are not implemented for the baseline")
+            raise RuntimeError("%s runs on the fp32 matrix path only (ops.set_matrix_path('fp32')): the fp16 path and its "
+                               "loss scale are not implemented for the baseline" % type(self).__name__)
         self.opt.zero_grad()
-        logits = siamese_forward_train(self.model, x1, x2)
-        loss = pair_loss(logits, n_pos)
+        loss, acc = self._loss_and_accuracy(*batch)
         if self._one is None or self._one.device != loss.device:
             self._one = torch.ones(1, device=loss.device, dtype=torch.float32)
         with ops.caller_thread_backward():
             loss.backward(self._one)
         self.opt.step()
         self._drop_inference_caches()
-        self.last_logits = logits.detach()
-        return loss.detach().view(()), pair_accuracy(logits, n_pos)
+        return loss.detach().view(()), acc
 
     def state_dict(self):
-        """{'model': the reference's SiameseNet state dict (names, shapes, order; on the host), 'opt': torch.optim.Adam's format}."""
+        """{'model': the reference's state dict of the model (names, shapes, order; on the host), 'opt': torch.optim.Adam's format}."""
         return {"model": {k: v.detach().to("cpu").contiguous() for k, v in self.model.state_dict().items()}, "opt": self.opt.state_dict()}
 
     def load_state_dict(self, sd):
@@ -164,6 +164,29 @@ class SiameseTrainer:
         if sd.get("opt") is not None:
             self.opt.load_state_dict(sd["opt"])
         self._drop_inference_caches()
+
+
+class SiameseTrainer(_BaselineTrainer):
+    """One FusedAdam over every parameter of a baselines.SiameseNet, in the reference's parameter order."""
+
+    MODEL = SiameseNet
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999)):
+        super().__init__(model, lr, betas)
+        self.last_logits = None      # [B, 1] logits of the latest train_step (before its update), detached
+
+    def _inference_caches(self):
+        return self.model, self.model.embedding_net
+
+    def _loss_and_accuracy(self, x1, x2, n_pos):
+        logits = siamese_forward_train(self.model, x1, x2)
+        self.last_logits = logits.detach()
+        return pair_loss(logits, n_pos), pair_accuracy(logits, n_pos)
+
+    def train_step(self, x1, x2, n_pos):
+        """One Adam update on the pair batch (x1[i], x2[i]); rows < n_pos are same-class pairs.  Returns (loss, accuracy) of the
+        batch before the update, as device scalars: nothing is read back here."""
+        return self._update(x1, x2, n_pos)
 
 
 class PairSampler:
@@ -213,30 +236,25 @@ class PairSampler:
         return x[:B], x[B:], self.n_pos
 
 
-def _save(trainer, out_dir, step):
+def _save(trainer, out_dir, step, model_key):
     ckpt_dir = os.path.join(out_dir, CHECKPOINT_DIR)
     os.makedirs(ckpt_dir, exist_ok=True)
     path = os.path.join(ckpt_dir, "model_%08d.pt" % step)
     tmp = path + ".tmp.%d" % os.getpid()
-    torch.save(dict(trainer.state_dict(), global_step=step), tmp)
+    sd = trainer.state_dict()
+    torch.save({model_key: sd["model"], "opt": sd["opt"], "global_step": step}, tmp)
     os.replace(tmp, path)
     return path
 
 
-def train_siamese(device, bank, out_dir, n_iters, batch_size=128, lr=1e-3, log_every=100, save_every=1000, seed=0, logger=None):
-    """Train a siamese baseline on the pair batches of `bank` up to iteration n_iters; resumes from the latest checkpoint of out_dir.
-    Writes out_dir/args.json and out_dir/ckpts/model_%08d.pt = {'model', 'opt', 'global_step'} every save_every iterations and at
-    the end; logs ('siamese', 'loss' / 'acc') every log_every iterations (one host read per log point).  Returns the trainer."""
-    device = torch.device(device)
+def _train_loop(trainer, step_args, category, model_key, out_dir, args, n_iters, log_every, save_every, logger):
+    """The loop of train_siamese and train_arcface: writes out_dir/args.json, resumes from the latest checkpoint of out_dir, runs
+    trainer.train_step(*step_args(it)) up to iteration n_iters, logs (category, 'loss' / 'acc') every log_every iterations (one stacked
+    host read per log point) and saves out_dir/ckpts/model_%08d.pt = {model_key, 'opt', 'global_step'} every save_every iterations and
+    at the end.  Returns the trainer."""
     os.makedirs(out_dir, exist_ok=True)
     with open(os.path.join(out_dir, "args.json"), "w") as f:
-        json.dump({"baseline_type": "siamese", "img_size": int(bank.S), "img_channels": int(bank.C), "batch_size": int(batch_size),
-                   "lr": float(lr), "seed": int(seed), "n_iters": int(n_iters)}, f)
-    with torch.random.fork_rng(devices=[]):
-        torch.manual_seed(seed)
-        net = ProtonetEmbeddingNet(inp_n_channels=bank.C, inp_img_size=bank.S)
-        model = SiameseNet(net, net.embedding_dim)
-    trainer = SiameseTrainer(model.to(device), lr=lr)
+        json.dump(args, f)
     step = 0
     ckpt_dir = os.path.join(out_dir, CHECKPOINT_DIR)
     if os.path.isdir(ckpt_dir):
@@ -246,26 +264,41 @@ def train_siamese(device, bank, out_dir, n_iters, batch_size=128, lr=1e-3, log_e
             latest = None
         if latest is not None:
             sd = torch.load(latest, map_location="cpu", weights_only=False)
-            trainer.load_state_dict(sd)
+            trainer.load_state_dict({"model": sd[model_key], "opt": sd.get("opt")})
             step = int(sd["global_step"])
-            print("Resuming siamese training from iteration {}".format(step))
+            print("Resuming {} training from iteration {}".format(category, step))
     if logger is None:
         logger = Logger(log_dir=os.path.join(out_dir, "logs"), img_dir=os.path.join(out_dir, "imgs"))
-    sampler = PairSampler(bank, batch_size, seed)
     saved = step
     while step < n_iters:
-        loss, acc = trainer.train_step(*sampler.batch(step))
+        loss, acc = trainer.train_step(*step_args(step))
         step += 1
         if log_every and step % log_every == 0:
             loss_v, acc_v = torch.stack([loss, acc]).tolist()
-            logger.add_scalar(category="siamese", k="loss", v=loss_v, global_step=step)
-            logger.add_scalar(category="siamese", k="acc", v=acc_v, global_step=step)
+            logger.add_scalar(category=category, k="loss", v=loss_v, global_step=step)
+            logger.add_scalar(category=category, k="acc", v=acc_v, global_step=step)
         if save_every and step % save_every == 0:
-            _save(trainer, out_dir, step)
+            _save(trainer, out_dir, step, model_key)
             saved = step
     if saved != step or not os.path.isdir(ckpt_dir):
-        _save(trainer, out_dir, step)
+        _save(trainer, out_dir, step, model_key)
     return trainer
+
+
+def train_siamese(device, bank, out_dir, n_iters, batch_size=128, lr=1e-3, log_every=100, save_every=1000, seed=0, logger=None):
+    """Train a siamese baseline on the pair batches of `bank` up to iteration n_iters; resumes from the latest checkpoint of out_dir.
+    Writes out_dir/args.json and out_dir/ckpts/model_%08d.pt = {'model', 'opt', 'global_step'} every save_every iterations and at
+    the end; logs ('siamese', 'loss' / 'acc') every log_every iterations (one host read per log point).  Returns the trainer."""
+    device = torch.device(device)
+    args = {"baseline_type": "siamese", "img_size": int(bank.S), "img_channels": int(bank.C), "batch_size": int(batch_size),
+            "lr": float(lr), "seed": int(seed), "n_iters": int(n_iters)}
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(seed)
+        net = ProtonetEmbeddingNet(inp_n_channels=bank.C, inp_img_size=bank.S)
+        model = SiameseNet(net, net.embedding_dim)
+    trainer = SiameseTrainer(model.to(device), lr=lr)
+    sampler = PairSampler(bank, batch_size, seed)
+    return _train_loop(trainer, sampler.batch, "siamese", "model", out_dir, args, n_iters, log_every, save_every, logger)
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -316,8 +349,7 @@ def arcface_forward_train(model, x, label, dropout=None):
     B = x.shape[0]
     if B < 2:
         raise RuntimeError("batch statistics need at least two images")
-    if not (torch.is_tensor(label) and label.is_cuda and label.dtype == torch.int64 and tuple(label.shape) == (B,)):
-        raise RuntimeError("label must be a CUDA int64 tensor of shape [B = %d]" % B)
+    label = ops._req_label(label, B)
     p = float(net.output_layer[1].p)
     if p > 0.0 and dropout is None:
         raise RuntimeError("the backbone drops %.2f of output_layer.1: pass dropout=(seed, it)" % p)
@@ -358,53 +390,33 @@ def top1_accuracy(logits, label):
     return margin_softmax_loss_and_accuracy(logits.detach(), label)[1]
 
 
-class ArcFaceTrainer:
+class ArcFaceTrainer(_BaselineTrainer):
     """One FusedAdam over every parameter of a baselines.ArcFace, in the reference's parameter order (head.kernel last).
     seed (>= 0): the dropout mask of output_layer.1 is a hash of (seed, iteration, element); train_arcface passes its own seed."""
 
+    MODEL = ArcFace
+
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), seed=0):
-        if not isinstance(model, ArcFace):
-            raise TypeError("ArcFaceTrainer trains a baselines.ArcFace")
-        self.model = model
-        self.opt = FusedAdam(model.parameters(), lr=lr, betas=betas)
+        super().__init__(model, lr, betas)
         if int(seed) < 0:
             raise ValueError("ArcFaceTrainer: seed must not be negative (it keys the dropout hash)")
         self.seed = int(seed)
-        self._one = None
         self.last_logits = None      # [B, classes] margin logits of the latest train_step (before its update), detached
         self.last_emb = None
 
-    def _drop_inference_caches(self):
-        self.model.emb_model._derived = None
+    def _inference_caches(self):
+        return (self.model.emb_model,)
+
+    def _loss_and_accuracy(self, x, label, it):
+        p = float(self.model.emb_model.output_layer[1].p)
+        emb, logits = arcface_forward_train(self.model, x, label, (self.seed, it) if p > 0.0 else None)
+        self.last_logits, self.last_emb = logits.detach(), emb.detach()
+        return margin_softmax_loss_and_accuracy(logits, label)
 
     def train_step(self, x, label, it):
         """One Adam update on the class-labelled batch (x, label); `it` keys the dropout mask.  Returns (loss, accuracy) of the batch
         before the update, as device scalars: nothing is read back here."""
-        if ops.matrix_path() != "fp32":
-            raise RuntimeError("ArcFaceTrainer runs on the fp32 matrix path only (ops.set_matrix_path('fp32')): the fp16 path and its "
-                               "loss scale are not implemented for the baseline")
-        self.opt.zero_grad()
-        p = float(self.model.emb_model.output_layer[1].p)
-        emb, logits = arcface_forward_train(self.model, x, label, (self.seed, it) if p > 0.0 else None)
-        loss, acc = margin_softmax_loss_and_accuracy(logits, label)
-        if self._one is None or self._one.device != loss.device:
-            self._one = torch.ones(1, device=loss.device, dtype=torch.float32)
-        with ops.caller_thread_backward():
-            loss.backward(self._one)
-        self.opt.step()
-        self._drop_inference_caches()
-        self.last_logits, self.last_emb = logits.detach(), emb.detach()
-        return loss.detach().view(()), acc
-
-    def state_dict(self):
-        """{'model': the reference's ArcFace state dict (names, shapes, order; on the host), 'opt': torch.optim.Adam's format}."""
-        return {"model": {k: v.detach().to("cpu").contiguous() for k, v in self.model.state_dict().items()}, "opt": self.opt.state_dict()}
-
-    def load_state_dict(self, sd):
-        self.model.load_state_dict(sd["model"], strict=True)
-        if sd.get("opt") is not None:
-            self.opt.load_state_dict(sd["opt"])
-        self._drop_inference_caches()
+        return self._update(x, label, it)
 
 
 class IdentitySampler:
@@ -443,17 +455,6 @@ class IdentitySampler:
         return x, torch.from_numpy(label).to(x.device, non_blocking=True)
 
 
-def _save_arcface(trainer, out_dir, step):
-    ckpt_dir = os.path.join(out_dir, CHECKPOINT_DIR)
-    os.makedirs(ckpt_dir, exist_ok=True)
-    path = os.path.join(ckpt_dir, "model_%08d.pt" % step)
-    tmp = path + ".tmp.%d" % os.getpid()
-    sd = trainer.state_dict()
-    torch.save({"arcface": sd["model"], "opt": sd["opt"], "global_step": step}, tmp)
-    os.replace(tmp, path)
-    return path
-
-
 def train_arcface(device, bank, out_dir, n_iters, num_layers=50, batch_size=128, lr=1e-4, drop_ratio=0.6, th=1.5, log_every=100,
                   save_every=1000, seed=0, logger=None):
     """Train an ArcFace baseline (IR-SE backbone, 512-d embedding, one class per class of `bank`) on the class-labelled batches of
@@ -480,44 +481,15 @@ def train_arcface(device, bank, out_dir, n_iters, num_layers=50, batch_size=128,
     n_classes = len(bank.offsets) - 1
     if n_classes < 2:
         raise ValueError("train_arcface: the margin softmax needs at least two classes, the bank has %d" % n_classes)
-    os.makedirs(out_dir, exist_ok=True)
-    with open(os.path.join(out_dir, "args.json"), "w") as f:
-        json.dump({"baseline_type": "arcface", "img_size": int(bank.S), "img_channels": int(bank.C), "num_layers": int(num_layers),
-                   "dropout": float(drop_ratio), "emb_dim": 512, "th": float(th), "n_classes": n_classes, "batch_size": int(batch_size),
-                   "lr": float(lr), "seed": int(seed), "n_iters": int(n_iters)}, f)
+    args = {"baseline_type": "arcface", "img_size": int(bank.S), "img_channels": int(bank.C), "num_layers": int(num_layers),
+            "dropout": float(drop_ratio), "emb_dim": 512, "th": float(th), "n_classes": n_classes, "batch_size": int(batch_size),
+            "lr": float(lr), "seed": int(seed), "n_iters": int(n_iters)}
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
         model = ArcFace(Backbone(num_layers, drop_ratio, 'ir_se', int(bank.S), int(bank.C)), 512, n_classes, th=th)
         with torch.no_grad():      # ArcfaceHead's initial kernel (arcface/models.py:177): uniform columns of unit norm
             model.head.kernel.uniform_(-1, 1).renorm_(2, 1, 1e-5).mul_(1e5)
     trainer = ArcFaceTrainer(model.to(device), lr=lr, seed=seed)
-    step = 0
-    ckpt_dir = os.path.join(out_dir, CHECKPOINT_DIR)
-    if os.path.isdir(ckpt_dir):
-        try:
-            latest = get_latest_ckpt(ckpt_dir)
-        except FileNotFoundError:
-            latest = None
-        if latest is not None:
-            sd = torch.load(latest, map_location="cpu", weights_only=False)
-            trainer.load_state_dict({"model": sd["arcface"], "opt": sd.get("opt")})
-            step = int(sd["global_step"])
-            print("Resuming arcface training from iteration {}".format(step))
-    if logger is None:
-        logger = Logger(log_dir=os.path.join(out_dir, "logs"), img_dir=os.path.join(out_dir, "imgs"))
     sampler = IdentitySampler(bank, batch_size, seed)
-    saved = step
-    while step < n_iters:
-        x, label = sampler.batch(step)
-        loss, acc = trainer.train_step(x, label, step)
-        step += 1
-        if log_every and step % log_every == 0:
-            loss_v, acc_v = torch.stack([loss, acc]).tolist()
-            logger.add_scalar(category="arcface", k="loss", v=loss_v, global_step=step)
-            logger.add_scalar(category="arcface", k="acc", v=acc_v, global_step=step)
-        if save_every and step % save_every == 0:
-            _save_arcface(trainer, out_dir, step)
-            saved = step
-    if saved != step or not os.path.isdir(ckpt_dir):
-        _save_arcface(trainer, out_dir, step)
-    return trainer
+    return _train_loop(trainer, lambda it: sampler.batch(it) + (it,), "arcface", "arcface", out_dir, args, n_iters, log_every, save_every,
+                       logger)

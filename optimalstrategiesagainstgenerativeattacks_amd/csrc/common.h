@@ -54,6 +54,16 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
 
 __device__ __forceinline__ float lrelu_f(float v, float slope) { return v > 0.f ? v : v * slope; }
 
+// 16-byte accesses of the NHWC fp32 passes (bn_train.hip, irse_train.hip, infer.hip): 4 channels per thread, base pointers
+// checked by the entry points; capped grid of 256-thread blocks for their grid-strided kernels
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static inline int blocks256(long long n) {
+    const long long b = (n + 255) / 256;
+    return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
+}
+
 // conv_tiny.hip: direct convolution of the 3 -> 3 / 1 -> 1 image layers (3x3, 9x9; plain geometry): one workgroup per
 // GIM_TINY_TILE x GIM_TINY_TILE output tile of one image.  gim_tiny_shape is the eligibility test and gim_tiny_grid the launch grid
 // of all three directions (the planners in conv_igemm.hip report them); the launchers run eligible shapes only.

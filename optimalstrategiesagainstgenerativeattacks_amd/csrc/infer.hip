@@ -4,19 +4,7 @@
 // entry points), grids are capped and grid-strided.
 #include "common.h"
 
-#define INF_MAX_BLOCKS 4096
-
-static inline int inf_blocks(long long n) {
-    long long b = (n + 255) / 256;
-    if (b > INF_MAX_BLOCKS) b = INF_MAX_BLOCKS;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-static inline bool inf_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
 #define GRID_STRIDE(i, n) for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < (n); i += (long long)gridDim.x * 256)
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
 // ---------------------------------------------------------------- 2x2 max pool (+ ReLU)
 __global__ __launch_bounds__(256) void maxpool2_act_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int H, int W, int C4,
@@ -44,9 +32,9 @@ __global__ __launch_bounds__(256) void maxpool2_act_kernel(const float* __restri
 
 extern "C" int gim_maxpool2_act(const float* x, float* y, int N, int H, int W, int C, int relu, void* stream) {
     GIM_CHECK_ARG(x && y && N > 0 && H >= 2 && W >= 2 && !(H & 1) && !(W & 1) && C > 0 && C % 4 == 0, "maxpool2_act: bad args (C % 4 == 0)");
-    GIM_CHECK_ARG(inf_aligned(x) && inf_aligned(y), "maxpool2_act: pointers must be 16-byte aligned");
+    GIM_CHECK_ARG(aligned16(x) && aligned16(y), "maxpool2_act: pointers must be 16-byte aligned");
     const long long n = (long long)N * (H / 2) * (W / 2) * (C / 4);
-    hipLaunchKernelGGL(maxpool2_act_kernel, dim3(inf_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, y, N, H, W, C / 4, relu);
+    hipLaunchKernelGGL(maxpool2_act_kernel, dim3(blocks256(n)), dim3(256), 0, (hipStream_t)stream, x, y, N, H, W, C / 4, relu);
     return gim_check_launch("gim_maxpool2_act");
 }
 
@@ -65,9 +53,9 @@ __global__ __launch_bounds__(256) void channel_affine_kernel(const float* __rest
 
 extern "C" int gim_channel_affine(const float* x, const float* scale, const float* shift, float* y, int64_t rows, int C, void* stream) {
     GIM_CHECK_ARG(x && scale && shift && y && rows > 0 && C > 0 && C % 4 == 0, "channel_affine: bad args (C % 4 == 0)");
-    GIM_CHECK_ARG(inf_aligned(x) && inf_aligned(y) && inf_aligned(scale) && inf_aligned(shift), "channel_affine: pointers must be 16-byte aligned");
+    GIM_CHECK_ARG(aligned16(x) && aligned16(y) && aligned16(scale) && aligned16(shift), "channel_affine: pointers must be 16-byte aligned");
     const long long n4 = (long long)rows * (C / 4);
-    hipLaunchKernelGGL(channel_affine_kernel, dim3(inf_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x, scale, shift, y, n4, C / 4);
+    hipLaunchKernelGGL(channel_affine_kernel, dim3(blocks256(n4)), dim3(256), 0, (hipStream_t)stream, x, scale, shift, y, n4, C / 4);
     return gim_check_launch("gim_channel_affine");
 }
 
@@ -107,14 +95,14 @@ extern "C" int gim_se_tail(const float* res, const float* gate, const float* sho
     GIM_CHECK_ARG(res && gate && shortcut && out && N > 0 && Ho > 0 && Wo > 0 && C > 0 && C % 4 == 0, "se_tail: bad args (C % 4 == 0)");
     GIM_CHECK_ARG(sstride == 1 || sstride == 2, "se_tail: sstride must be 1 or 2");
     GIM_CHECK_ARG((out_bn != nullptr) == (scale != nullptr) && (scale != nullptr) == (shift != nullptr), "se_tail: out_bn, scale and shift come together");
-    GIM_CHECK_ARG(inf_aligned(res) && inf_aligned(gate) && inf_aligned(shortcut) && inf_aligned(out) && inf_aligned(out_bn) && inf_aligned(scale) &&
-                      inf_aligned(shift), "se_tail: pointers must be 16-byte aligned");
+    GIM_CHECK_ARG(aligned16(res) && aligned16(gate) && aligned16(shortcut) && aligned16(out) && aligned16(out_bn) && aligned16(scale) &&
+                      aligned16(shift), "se_tail: pointers must be 16-byte aligned");
     const long long n4 = (long long)N * Ho * Wo * (C / 4);
     if (out_bn)
-        hipLaunchKernelGGL(se_tail_kernel<true>, dim3(inf_blocks(n4)), dim3(256), 0, (hipStream_t)stream, res, gate, shortcut, scale, shift, out,
+        hipLaunchKernelGGL(se_tail_kernel<true>, dim3(blocks256(n4)), dim3(256), 0, (hipStream_t)stream, res, gate, shortcut, scale, shift, out,
                            out_bn, N, Ho, Wo, C / 4, sstride);
     else
-        hipLaunchKernelGGL(se_tail_kernel<false>, dim3(inf_blocks(n4)), dim3(256), 0, (hipStream_t)stream, res, gate, shortcut, scale, shift, out,
+        hipLaunchKernelGGL(se_tail_kernel<false>, dim3(blocks256(n4)), dim3(256), 0, (hipStream_t)stream, res, gate, shortcut, scale, shift, out,
                            out_bn, N, Ho, Wo, C / 4, sstride);
     return gim_check_launch("gim_se_tail");
 }
@@ -148,7 +136,7 @@ __global__ __launch_bounds__(256) void pair_score_kernel(const float* __restrict
 
 extern "C" int gim_pair_score(const float* a, const float* b, float* out, int B, int D, void* stream) {
     GIM_CHECK_ARG(a && b && out && B > 0 && D > 0 && D % 4 == 0, "pair_score: bad args (D % 4 == 0)");
-    GIM_CHECK_ARG(inf_aligned(a) && inf_aligned(b), "pair_score: pointers must be 16-byte aligned");
+    GIM_CHECK_ARG(aligned16(a) && aligned16(b), "pair_score: pointers must be 16-byte aligned");
     hipLaunchKernelGGL(pair_score_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, a, b, out, B, D / 4);
     return gim_check_launch("gim_pair_score");
 }
@@ -176,7 +164,7 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* __restric
 
 extern "C" int gim_l2norm_rows(const float* x, float* y, int B, int D, void* stream) {
     GIM_CHECK_ARG(x && y && B > 0 && D > 0 && D % 4 == 0, "l2norm_rows: bad args (D % 4 == 0)");
-    GIM_CHECK_ARG(inf_aligned(x) && inf_aligned(y), "l2norm_rows: pointers must be 16-byte aligned");
+    GIM_CHECK_ARG(aligned16(x) && aligned16(y), "l2norm_rows: pointers must be 16-byte aligned");
     hipLaunchKernelGGL(l2norm_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, y, B, D / 4);
     return gim_check_launch("gim_l2norm_rows");
 }
@@ -194,7 +182,7 @@ __global__ __launch_bounds__(256) void absdiff_kernel(const float* __restrict__ 
 
 extern "C" int gim_absdiff(const float* a, const float* b, float* y, int64_t n, void* stream) {
     GIM_CHECK_ARG(a && b && y && n > 0 && n % 4 == 0, "absdiff: bad args (n % 4 == 0)");
-    GIM_CHECK_ARG(inf_aligned(a) && inf_aligned(b) && inf_aligned(y), "absdiff: pointers must be 16-byte aligned");
-    hipLaunchKernelGGL(absdiff_kernel, dim3(inf_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, a, b, y, (long long)(n / 4));
+    GIM_CHECK_ARG(aligned16(a) && aligned16(b) && aligned16(y), "absdiff: pointers must be 16-byte aligned");
+    hipLaunchKernelGGL(absdiff_kernel, dim3(blocks256(n / 4)), dim3(256), 0, (hipStream_t)stream, a, b, y, (long long)(n / 4));
     return gim_check_launch("gim_absdiff");
 }

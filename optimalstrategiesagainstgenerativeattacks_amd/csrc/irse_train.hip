@@ -6,97 +6,12 @@
 // Maps are NHWC fp32 with C % 4 == 0 and 16-byte aligned base pointers (checked by the entry points): one thread moves 16 bytes
 // (4 channels) per access, lanes run along the channel axis.  The head's matrices are [rows][cols] with any column count (scalar).
 //
-// No float atomics and no allocation.  A sum over the rows of a map follows the two-stage slab scheme of bn_train.hip: stage 1 gives
+// No float atomics and no allocation.  A sum over the rows of a map follows the two-stage slab scheme of rowsum.h: stage 1 gives
 // each workgroup a slab of rows (gim_bn_slabs(rows) slabs) and writes one partial per channel into the caller's `partials`
-// ([3][slabs][C] floats), stage 2 adds the partials of a channel in a fixed order.  Two runs are bit-identical.
-#include "common.h"
-
-constexpr int IR_CB = 64;             // channels per workgroup of a slab kernel
-constexpr int IR_CL = IR_CB / 4;      // lanes along channels (16 bytes each)
-constexpr int IR_HG = 256 / IR_CL;    // thread groups along rows
-constexpr int IR_MAX_BLOCKS = 4096;
-
-static inline bool ir_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
-static inline int ir_blocks(long long n) {
-    long long b = (n + 255) / 256;
-    return (int)(b > IR_MAX_BLOCKS ? IR_MAX_BLOCKS : (b < 1 ? 1 : b));
-}
-// rows per slab for the slab count gim_bn_slabs(rows) gives (the same cut as bn_train.hip: no slab is empty)
-static inline long long ir_slab_rows(long long rows, int* n_slabs) {
-    const int ns = gim_bn_slabs(rows);
-    long long rps = (rows + ns - 1) / ns;
-    while ((rows + rps - 1) / rps > ns) ++rps;
-    *n_slabs = (int)((rows + rps - 1) / rps);
-    return rps;
-}
-
-__device__ __forceinline__ f32x4 ir_ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void ir_st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-
-// sums of NS quads per thread over the IR_HG thread groups, in group order; valid in the threads of group 0
-template <int NS>
-__device__ __forceinline__ void ir_group_sum(f32x4 (&s)[NS], float (*red)[IR_HG * IR_CB], int cl, int hg) {
-#pragma unroll
-    for (int k = 0; k < NS; ++k)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) red[k][hg * IR_CB + cl * 4 + e] = s[k][e];
-    __syncthreads();
-    if (hg == 0) {
-#pragma unroll
-        for (int k = 0; k < NS; ++k)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float a = 0.f;
-                for (int g = 0; g < IR_HG; ++g) a += red[k][g * IR_CB + cl * 4 + e];
-                s[k][e] = a;
-            }
-    }
-}
-template <int NS>
-__device__ __forceinline__ void ir_store_partials(const f32x4 (&s)[NS], float* partials, int n_slabs, int slab, int C, int c) {
-#pragma unroll
-    for (int k = 0; k < NS; ++k) ir_st4(partials + ((long long)k * n_slabs + slab) * C + c, s[k]);
-}
-
-// ---------------------------------------------------------------- stage 2: out[k][c] = sum over slabs, in a fixed order
-// grid (ceil(C / 4), sums); 4 channels x 64 slab lanes: a lane adds its slabs lane, lane + 64, ... in that order, then one thread
-// per channel the 64 lane sums in lane order.  acc[k] (may be NULL): the total is also ADDED there (a parameter's .grad).
-struct IrSums {
-    float* out[3];
-    float* acc[3];
-};
-__global__ __launch_bounds__(256) void ir_finalize_kernel(const float* __restrict__ partials, int n_slabs, int C, IrSums o) {
-    __shared__ float red[64 * 4];
-    const int ci = threadIdx.x & 3, lane = threadIdx.x >> 2;
-    const int c = blockIdx.x * 4 + ci, k = blockIdx.y;
-    float a = 0.f;
-    if (c < C)
-        for (int s = lane; s < n_slabs; s += 64) a += partials[((long long)k * n_slabs + s) * C + c];
-    red[lane * 4 + ci] = a;
-    __syncthreads();
-    if (lane != 0 || c >= C) return;
-    float t = 0.f;
-    for (int l = 0; l < 64; ++l) t += red[l * 4 + ci];
-    o.out[k][c] = t;
-    if (o.acc[k]) o.acc[k][c] += t;
-}
+// ([3][slabs][C] floats), stage 2 (rowsum_finalize) adds the partials of a channel in a fixed order.  Two runs are bit-identical.
+#include "rowsum.h"
 
 // ---------------------------------------------------------------- BatchNorm with batch statistics (+ PReLU)
-struct IrChan {
-    f32x4 mean, invstd, s, beta, a;   // s = gamma * invstd, a = PReLU slope
-};
-template <bool PRELU>
-__device__ __forceinline__ IrChan ir_chan(const float* gamma, const float* beta, const float* mean, const float* invstd, const float* slope,
-                                          int c) {
-    IrChan p;
-    p.mean = ir_ld4(mean + c);
-    p.invstd = ir_ld4(invstd + c);
-    p.s = ir_ld4(gamma + c) * p.invstd;
-    p.beta = ir_ld4(beta + c);
-    if (PRELU) p.a = ir_ld4(slope + c);
-    return p;
-}
-
 template <bool PRELU>
 __global__ __launch_bounds__(256) void bn_apply_fwd_kernel(const float* __restrict__ z, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, const float* __restrict__ mean,
@@ -104,15 +19,15 @@ __global__ __launch_bounds__(256) void bn_apply_fwd_kernel(const float* __restri
                                                            float* __restrict__ y, long long n4, int C4) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
         const int c = (int)(i % C4) * 4;
-        const IrChan p = ir_chan<PRELU>(gamma, beta, mean, invstd, slope, c);
-        const f32x4 v = ir_ld4(z + i * 4);
+        const BnChan p = bn_chan<PRELU>(gamma, beta, mean, invstd, slope, c);
+        const f32x4 v = ld4(z + i * 4);
         f32x4 o;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             o[q] = fmaf(v[q] - p.mean[q], p.s[q], p.beta[q]);
             if (PRELU) o[q] = o[q] > 0.f ? o[q] : o[q] * p.a[q];
         }
-        ir_st4(y + i * 4, o);
+        st4(y + i * 4, o);
     }
 }
 
@@ -123,19 +38,19 @@ __global__ __launch_bounds__(256) void bn_bwd_slab_kernel(const float* __restric
                                                           const float* __restrict__ mean, const float* __restrict__ invstd,
                                                           const float* __restrict__ slope, float* __restrict__ partials, long long M, int C,
                                                           long long rps, int n_slabs) {
-    __shared__ float red[3][IR_HG * IR_CB];
-    const int cl = threadIdx.x % IR_CL, hg = threadIdx.x / IR_CL;
-    const int c = blockIdx.x * IR_CB + cl * 4;
+    __shared__ float red[3][RS_HG * RS_CB];
+    const int cl = threadIdx.x % RS_CL, hg = threadIdx.x / RS_CL;
+    const int c = blockIdx.x * RS_CB + cl * 4;
     const long long r0 = (long long)blockIdx.y * rps;
     const long long r1 = (r0 + rps < M) ? r0 + rps : M;
     const bool ok = c < C;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     f32x4 s[3] = {zero, zero, zero};
     if (ok) {
-        const IrChan p = ir_chan<PRELU>(gamma, beta, mean, invstd, slope, c);
+        const BnChan p = bn_chan<PRELU>(gamma, beta, mean, invstd, slope, c);
 #pragma unroll 4
-        for (long long r = r0 + hg; r < r1; r += IR_HG) {
-            const f32x4 g = ir_ld4(dy + r * C + c), v = ir_ld4(z + r * C + c);
+        for (long long r = r0 + hg; r < r1; r += RS_HG) {
+            const f32x4 g = ld4(dy + r * C + c), v = ld4(z + r * C + c);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const float xc = v[q] - p.mean[q];
@@ -152,8 +67,8 @@ __global__ __launch_bounds__(256) void bn_bwd_slab_kernel(const float* __restric
             }
         }
     }
-    ir_group_sum<3>(s, red, cl, hg);
-    if (ok && hg == 0) ir_store_partials<3>(s, partials, n_slabs, blockIdx.y, C, c);
+    group_sum<3>(s, red, cl, hg);
+    if (ok && hg == 0) store_partials<3>(s, partials, n_slabs, blockIdx.y, C, c);
 }
 
 // dz = gamma * invstd * (dyhat - dbeta / M - xhat * dgamma / M)
@@ -166,9 +81,9 @@ __global__ __launch_bounds__(256) void bn_bwd_dx_kernel(const float* __restrict_
                                                         float inv_m) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
         const int c = (int)(i % C4) * 4;
-        const IrChan p = ir_chan<PRELU>(gamma, beta, mean, invstd, slope, c);
-        const f32x4 mb = ir_ld4(dbeta + c) * inv_m, mg = ir_ld4(dgamma + c) * inv_m;
-        const f32x4 g = ir_ld4(dy + i * 4), v = ir_ld4(z + i * 4);
+        const BnChan p = bn_chan<PRELU>(gamma, beta, mean, invstd, slope, c);
+        const f32x4 mb = ld4(dbeta + c) * inv_m, mg = ld4(dgamma + c) * inv_m;
+        const f32x4 g = ld4(dy + i * 4), v = ld4(z + i * 4);
         f32x4 o;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -177,7 +92,7 @@ __global__ __launch_bounds__(256) void bn_bwd_dx_kernel(const float* __restrict_
             if (PRELU) d = fmaf(xc, p.s[q], p.beta[q]) > 0.f ? d : d * p.a[q];
             o[q] = p.s[q] * (d - mb[q] - xc * p.invstd[q] * mg[q]);
         }
-        ir_st4(dz + i * 4, o);
+        st4(dz + i * 4, o);
     }
 }
 
@@ -186,12 +101,12 @@ template <bool SLOPE>
 __global__ __launch_bounds__(256) void prelu_fwd_kernel(const float* __restrict__ x, const float* __restrict__ slope, float* __restrict__ y,
                                                         long long n4, int C4) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-        const f32x4 v = ir_ld4(x + i * 4);
+        const f32x4 v = ld4(x + i * 4);
         f32x4 a = {0.f, 0.f, 0.f, 0.f}, o;
-        if (SLOPE) a = ir_ld4(slope + (int)(i % C4) * 4);
+        if (SLOPE) a = ld4(slope + (int)(i % C4) * 4);
 #pragma unroll
         for (int q = 0; q < 4; ++q) o[q] = v[q] > 0.f ? v[q] : v[q] * a[q];
-        ir_st4(y + i * 4, o);
+        st4(y + i * 4, o);
     }
 }
 
@@ -200,19 +115,19 @@ template <bool SLOPE>
 __global__ __launch_bounds__(256) void prelu_bwd_slab_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                              const float* __restrict__ slope, float* __restrict__ dx,
                                                              float* __restrict__ partials, long long M, int C, long long rps, int n_slabs) {
-    __shared__ float red[1][IR_HG * IR_CB];
-    const int cl = threadIdx.x % IR_CL, hg = threadIdx.x / IR_CL;
-    const int c = blockIdx.x * IR_CB + cl * 4;
+    __shared__ float red[1][RS_HG * RS_CB];
+    const int cl = threadIdx.x % RS_CL, hg = threadIdx.x / RS_CL;
+    const int c = blockIdx.x * RS_CB + cl * 4;
     const long long r0 = (long long)blockIdx.y * rps;
     const long long r1 = (r0 + rps < M) ? r0 + rps : M;
     const bool ok = c < C;
     f32x4 s[1] = {{0.f, 0.f, 0.f, 0.f}};
     if (ok) {
         f32x4 a = {0.f, 0.f, 0.f, 0.f};
-        if (SLOPE) a = ir_ld4(slope + c);
+        if (SLOPE) a = ld4(slope + c);
 #pragma unroll 4
-        for (long long r = r0 + hg; r < r1; r += IR_HG) {
-            const f32x4 g = ir_ld4(dy + r * C + c), v = ir_ld4(x + r * C + c);
+        for (long long r = r0 + hg; r < r1; r += RS_HG) {
+            const f32x4 g = ld4(dy + r * C + c), v = ld4(x + r * C + c);
             f32x4 o;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -220,12 +135,12 @@ __global__ __launch_bounds__(256) void prelu_bwd_slab_kernel(const float* __rest
                 o[q] = pos ? g[q] : g[q] * a[q];
                 if (SLOPE) s[0][q] += pos ? 0.f : g[q] * v[q];
             }
-            ir_st4(dx + r * C + c, o);
+            st4(dx + r * C + c, o);
         }
     }
     if (!SLOPE) return;
-    ir_group_sum<1>(s, red, cl, hg);
-    if (ok && hg == 0) ir_store_partials<1>(s, partials, n_slabs, blockIdx.y, C, c);
+    group_sum<1>(s, red, cl, hg);
+    if (ok && hg == 0) store_partials<1>(s, partials, n_slabs, blockIdx.y, C, c);
 }
 
 // ---------------------------------------------------------------- backward of out = res * sigmoid(gate[n, c]) + shortcut
@@ -233,27 +148,27 @@ __global__ __launch_bounds__(256) void prelu_bwd_slab_kernel(const float* __rest
 __global__ __launch_bounds__(256) void se_tail_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ res,
                                                           const float* __restrict__ gate, float* __restrict__ dres,
                                                           float* __restrict__ dgate, int P, int C) {
-    __shared__ float red[1][IR_HG * IR_CB];
-    const int cl = threadIdx.x % IR_CL, hg = threadIdx.x / IR_CL;
-    const int c = blockIdx.x * IR_CB + cl * 4;
+    __shared__ float red[1][RS_HG * RS_CB];
+    const int cl = threadIdx.x % RS_CL, hg = threadIdx.x / RS_CL;
+    const int c = blockIdx.x * RS_CB + cl * 4;
     const long long n = blockIdx.y;
     const bool ok = c < C;
     f32x4 s[1] = {{0.f, 0.f, 0.f, 0.f}};
     f32x4 sig = {0.f, 0.f, 0.f, 0.f};
     if (ok) {
-        const f32x4 g = ir_ld4(gate + n * C + c);
+        const f32x4 g = ld4(gate + n * C + c);
 #pragma unroll
         for (int q = 0; q < 4; ++q) sig[q] = 1.0f / (1.0f + expf(-g[q]));
         const long long base = n * P * C + c;
 #pragma unroll 4
-        for (int p = hg; p < P; p += IR_HG) {
-            const f32x4 d = ir_ld4(dout + base + (long long)p * C), r = ir_ld4(res + base + (long long)p * C);
+        for (int p = hg; p < P; p += RS_HG) {
+            const f32x4 d = ld4(dout + base + (long long)p * C), r = ld4(res + base + (long long)p * C);
             s[0] += d * r;
-            ir_st4(dres + base + (long long)p * C, d * sig);
+            st4(dres + base + (long long)p * C, d * sig);
         }
     }
-    ir_group_sum<1>(s, red, cl, hg);
-    if (ok && hg == 0) ir_st4(dgate + n * C + c, s[0] * sig * (1.0f - sig));
+    group_sum<1>(s, red, cl, hg);
+    if (ok && hg == 0) st4(dgate + n * C + c, s[0] * sig * (1.0f - sig));
 }
 
 // ---------------------------------------------------------------- y[n, i, j] = x[n, 2 i, 2 j] and its transpose
@@ -266,7 +181,7 @@ __global__ __launch_bounds__(256) void subsample2_fwd_kernel(const float* __rest
         r /= Wo;
         const int oy = (int)(r % Ho);
         const long long n = r / Ho;
-        ir_st4(y + i * 4, ir_ld4(x + ((((n * Ho + oy) * 2) * (2 * Wo) + 2 * ox) * C4 + c) * 4));
+        st4(y + i * 4, ld4(x + ((((n * Ho + oy) * 2) * (2 * Wo) + 2 * ox) * C4 + c) * 4));
     }
 }
 // every element of dx is written exactly once: dy at the even positions, zero elsewhere
@@ -280,8 +195,8 @@ __global__ __launch_bounds__(256) void subsample2_bwd_kernel(const float* __rest
         const int iy = (int)(r % H);
         const long long n = r / H;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (!((ix | iy) & 1)) v = ir_ld4(dy + (((n * (H / 2) + iy / 2) * (W / 2) + ix / 2) * C4 + c) * 4);
-        ir_st4(dx + i * 4, v);
+        if (!((ix | iy) & 1)) v = ld4(dy + (((n * (H / 2) + iy / 2) * (W / 2) + ix / 2) * C4 + c) * 4);
+        st4(dx + i * 4, v);
     }
 }
 
@@ -304,11 +219,11 @@ __device__ __forceinline__ float ir_uniform(uint64_t seed, uint64_t ctr) {      
 __global__ __launch_bounds__(256) void dropout_kernel(const float* __restrict__ x, float* __restrict__ y, long long n4, float p, float scale,
                                                       uint64_t seed, uint64_t offset) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-        const f32x4 v = ir_ld4(x + i * 4);
+        const f32x4 v = ld4(x + i * 4);
         f32x4 o;
 #pragma unroll
         for (int q = 0; q < 4; ++q) o[q] = ir_uniform(seed, offset + (uint64_t)(i * 4 + q)) >= p ? v[q] * scale : 0.f;
-        ir_st4(y + i * 4, o);
+        st4(y + i * 4, o);
     }
 }
 
@@ -322,7 +237,7 @@ __global__ __launch_bounds__(256) void l2norm_rows_bwd_kernel(const float* __res
     const float* pg = dy + (long long)row * D4 * 4;
     float ss = 0.f, sg = 0.f;
     for (int i = lane; i < D4; i += 64) {
-        const f32x4 u = ir_ld4(px + i * 4), g = ir_ld4(pg + i * 4);
+        const f32x4 u = ld4(px + i * 4), g = ld4(pg + i * 4);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             ss += u[q] * u[q];
@@ -333,8 +248,8 @@ __global__ __launch_bounds__(256) void l2norm_rows_bwd_kernel(const float* __res
     sg = wave_sum(sg);
     const float inv = 1.0f / sqrtf(ss), t = sg / ss;      // dx = (dy - x * <dy, x> / |x|^2) / |x|
     for (int i = lane; i < D4; i += 64) {
-        const f32x4 u = ir_ld4(px + i * 4), g = ir_ld4(pg + i * 4);
-        ir_st4(dx + ((long long)row * D4 + i) * 4, (g - u * t) * inv);
+        const f32x4 u = ld4(px + i * 4), g = ld4(pg + i * 4);
+        st4(dx + ((long long)row * D4 + i) * 4, (g - u * t) * inv);
     }
 }
 
@@ -454,24 +369,18 @@ static int ir_check_rows(const char* what, int64_t M, int C) {
     return GIM_OK;
 }
 
-static void ir_finalize(const float* partials, int ns, int C, int sums, float* o0, float* o1, float* o2, float* a0, float* a1, float* a2,
-                        hipStream_t st) {
-    IrSums o = {{o0, o1, o2}, {a0, a1, a2}};
-    hipLaunchKernelGGL(ir_finalize_kernel, dim3((C + 3) / 4, sums), dim3(256), 0, st, partials, ns, C, o);
-}
-
 extern "C" int gim_bn_apply_fwd(const float* z, const float* gamma, const float* beta, const float* mean, const float* invstd,
                                 const float* slope, float* y, int64_t M, int C, void* stream) {
     GIM_CHECK_ARG(z && gamma && beta && mean && invstd && y, "bn_apply_fwd: null pointer");
     if (ir_check_rows("bn_apply_fwd: bad dims (M > 0 rows, C % 4 == 0)", M, C)) return GIM_E_BADARG;
-    GIM_CHECK_ARG(ir_aligned(z) && ir_aligned(gamma) && ir_aligned(beta) && ir_aligned(mean) && ir_aligned(invstd) && ir_aligned(slope) &&
-                      ir_aligned(y), "bn_apply_fwd: pointers must be 16-byte aligned");
+    GIM_CHECK_ARG(aligned16(z) && aligned16(gamma) && aligned16(beta) && aligned16(mean) && aligned16(invstd) && aligned16(slope) &&
+                      aligned16(y), "bn_apply_fwd: pointers must be 16-byte aligned");
     const long long n4 = (long long)M * (C / 4);
     if (slope)
-        hipLaunchKernelGGL(bn_apply_fwd_kernel<true>, dim3(ir_blocks(n4)), dim3(256), 0, (hipStream_t)stream, z, gamma, beta, mean, invstd,
+        hipLaunchKernelGGL(bn_apply_fwd_kernel<true>, dim3(blocks256(n4)), dim3(256), 0, (hipStream_t)stream, z, gamma, beta, mean, invstd,
                            slope, y, n4, C / 4);
     else
-        hipLaunchKernelGGL(bn_apply_fwd_kernel<false>, dim3(ir_blocks(n4)), dim3(256), 0, (hipStream_t)stream, z, gamma, beta, mean, invstd,
+        hipLaunchKernelGGL(bn_apply_fwd_kernel<false>, dim3(blocks256(n4)), dim3(256), 0, (hipStream_t)stream, z, gamma, beta, mean, invstd,
                            slope, y, n4, C / 4);
     return gim_check_launch("gim_bn_apply_fwd");
 }
@@ -482,19 +391,19 @@ extern "C" int gim_bn_bwd_reduce(const float* dy, const float* z, const float* g
     GIM_CHECK_ARG(dy && z && gamma && beta && mean && invstd && partials && dgamma && dbeta, "bn_bwd_reduce: null pointer");
     GIM_CHECK_ARG(!slope == !dslope && (slope || !acc_dslope), "bn_bwd_reduce: slope and dslope are given together or not at all");
     if (ir_check_rows("bn_bwd_reduce: bad dims (M > 0 rows, C % 4 == 0)", M, C)) return GIM_E_BADARG;
-    GIM_CHECK_ARG(ir_aligned(dy) && ir_aligned(z) && ir_aligned(gamma) && ir_aligned(beta) && ir_aligned(mean) && ir_aligned(invstd) &&
-                      ir_aligned(slope) && ir_aligned(partials), "bn_bwd_reduce: pointers must be 16-byte aligned");
+    GIM_CHECK_ARG(aligned16(dy) && aligned16(z) && aligned16(gamma) && aligned16(beta) && aligned16(mean) && aligned16(invstd) &&
+                      aligned16(slope) && aligned16(partials), "bn_bwd_reduce: pointers must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    int ns;
-    const long long rps = ir_slab_rows(M, &ns);
-    const dim3 grid((C + IR_CB - 1) / IR_CB, ns);
+    const long long rps = slab_rows(M);
+    const int ns = slab_count(M);
+    const dim3 grid((C + RS_CB - 1) / RS_CB, ns);
     if (slope)
         hipLaunchKernelGGL(bn_bwd_slab_kernel<true>, grid, dim3(256), 0, st, dy, z, gamma, beta, mean, invstd, slope, partials, (long long)M, C,
                            rps, ns);
     else
         hipLaunchKernelGGL(bn_bwd_slab_kernel<false>, grid, dim3(256), 0, st, dy, z, gamma, beta, mean, invstd, slope, partials, (long long)M,
                            C, rps, ns);
-    ir_finalize(partials, ns, C, slope ? 3 : 2, dbeta, dgamma, dslope, acc_dbeta, acc_dgamma, acc_dslope, st);
+    rowsum_finalize(partials, ns, C, slope ? 3 : 2, dbeta, dgamma, dslope, acc_dbeta, acc_dgamma, acc_dslope, st);
     return gim_check_launch("gim_bn_bwd_reduce");
 }
 
@@ -502,16 +411,16 @@ extern "C" int gim_bn_bwd_dx(const float* dy, const float* z, const float* gamma
                              const float* slope, const float* dgamma, const float* dbeta, float* dz, int64_t M, int C, void* stream) {
     GIM_CHECK_ARG(dy && z && gamma && beta && mean && invstd && dgamma && dbeta && dz, "bn_bwd_dx: null pointer");
     if (ir_check_rows("bn_bwd_dx: bad dims (M > 0 rows, C % 4 == 0)", M, C)) return GIM_E_BADARG;
-    GIM_CHECK_ARG(ir_aligned(dy) && ir_aligned(z) && ir_aligned(gamma) && ir_aligned(beta) && ir_aligned(mean) && ir_aligned(invstd) &&
-                      ir_aligned(slope) && ir_aligned(dgamma) && ir_aligned(dbeta) && ir_aligned(dz),
+    GIM_CHECK_ARG(aligned16(dy) && aligned16(z) && aligned16(gamma) && aligned16(beta) && aligned16(mean) && aligned16(invstd) &&
+                      aligned16(slope) && aligned16(dgamma) && aligned16(dbeta) && aligned16(dz),
                   "bn_bwd_dx: pointers must be 16-byte aligned");
     const long long n4 = (long long)M * (C / 4);
     const float inv_m = 1.0f / (float)M;
     if (slope)
-        hipLaunchKernelGGL(bn_bwd_dx_kernel<true>, dim3(ir_blocks(n4)), dim3(256), 0, (hipStream_t)stream, dy, z, gamma, beta, mean, invstd,
+        hipLaunchKernelGGL(bn_bwd_dx_kernel<true>, dim3(blocks256(n4)), dim3(256), 0, (hipStream_t)stream, dy, z, gamma, beta, mean, invstd,
                            slope, dgamma, dbeta, dz, n4, C / 4, inv_m);
     else
-        hipLaunchKernelGGL(bn_bwd_dx_kernel<false>, dim3(ir_blocks(n4)), dim3(256), 0, (hipStream_t)stream, dy, z, gamma, beta, mean, invstd,
+        hipLaunchKernelGGL(bn_bwd_dx_kernel<false>, dim3(blocks256(n4)), dim3(256), 0, (hipStream_t)stream, dy, z, gamma, beta, mean, invstd,
                            slope, dgamma, dbeta, dz, n4, C / 4, inv_m);
     return gim_check_launch("gim_bn_bwd_dx");
 }
@@ -519,12 +428,12 @@ extern "C" int gim_bn_bwd_dx(const float* dy, const float* z, const float* gamma
 extern "C" int gim_prelu_fwd(const float* x, const float* slope, float* y, int64_t M, int C, void* stream) {
     GIM_CHECK_ARG(x && y, "prelu_fwd: null pointer");
     if (ir_check_rows("prelu_fwd: bad dims (M > 0 rows, C % 4 == 0)", M, C)) return GIM_E_BADARG;
-    GIM_CHECK_ARG(ir_aligned(x) && ir_aligned(slope) && ir_aligned(y), "prelu_fwd: pointers must be 16-byte aligned");
+    GIM_CHECK_ARG(aligned16(x) && aligned16(slope) && aligned16(y), "prelu_fwd: pointers must be 16-byte aligned");
     const long long n4 = (long long)M * (C / 4);
     if (slope)
-        hipLaunchKernelGGL(prelu_fwd_kernel<true>, dim3(ir_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x, slope, y, n4, C / 4);
+        hipLaunchKernelGGL(prelu_fwd_kernel<true>, dim3(blocks256(n4)), dim3(256), 0, (hipStream_t)stream, x, slope, y, n4, C / 4);
     else
-        hipLaunchKernelGGL(prelu_fwd_kernel<false>, dim3(ir_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x, slope, y, n4, C / 4);
+        hipLaunchKernelGGL(prelu_fwd_kernel<false>, dim3(blocks256(n4)), dim3(256), 0, (hipStream_t)stream, x, slope, y, n4, C / 4);
     return gim_check_launch("gim_prelu_fwd");
 }
 
@@ -533,15 +442,15 @@ extern "C" int gim_prelu_bwd(const float* dy, const float* x, const float* slope
     GIM_CHECK_ARG(dy && x && dx, "prelu_bwd: null pointer");
     GIM_CHECK_ARG(slope ? (partials && dslope) : (!dslope && !acc_dslope), "prelu_bwd: slope, partials and dslope are given together or not at all");
     if (ir_check_rows("prelu_bwd: bad dims (M > 0 rows, C % 4 == 0)", M, C)) return GIM_E_BADARG;
-    GIM_CHECK_ARG(ir_aligned(dy) && ir_aligned(x) && ir_aligned(slope) && ir_aligned(dx) && ir_aligned(partials),
+    GIM_CHECK_ARG(aligned16(dy) && aligned16(x) && aligned16(slope) && aligned16(dx) && aligned16(partials),
                   "prelu_bwd: pointers must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    int ns;
-    const long long rps = ir_slab_rows(M, &ns);
-    const dim3 grid((C + IR_CB - 1) / IR_CB, ns);
+    const long long rps = slab_rows(M);
+    const int ns = slab_count(M);
+    const dim3 grid((C + RS_CB - 1) / RS_CB, ns);
     if (slope) {
         hipLaunchKernelGGL(prelu_bwd_slab_kernel<true>, grid, dim3(256), 0, st, dy, x, slope, dx, partials, (long long)M, C, rps, ns);
-        ir_finalize(partials, ns, C, 1, dslope, nullptr, nullptr, acc_dslope, nullptr, nullptr, st);
+        rowsum_finalize(partials, ns, C, 1, dslope, nullptr, nullptr, acc_dslope, nullptr, nullptr, st);
     } else {
         hipLaunchKernelGGL(prelu_bwd_slab_kernel<false>, grid, dim3(256), 0, st, dy, x, slope, dx, partials, (long long)M, C, rps, ns);
     }
@@ -553,9 +462,9 @@ extern "C" int gim_se_tail_bwd(const float* dout, const float* res, const float*
     GIM_CHECK_ARG(dout && res && gate && dres && dgate, "se_tail_bwd: null pointer");
     GIM_CHECK_ARG(N > 0 && N <= 65535 && Ho > 0 && Wo > 0 && (long long)Ho * Wo < (1ll << 31) && C > 0 && C % 4 == 0 && C <= (1 << 18),
                   "se_tail_bwd: bad dims (N <= 65535, C % 4 == 0)");
-    GIM_CHECK_ARG(ir_aligned(dout) && ir_aligned(res) && ir_aligned(gate) && ir_aligned(dres) && ir_aligned(dgate),
+    GIM_CHECK_ARG(aligned16(dout) && aligned16(res) && aligned16(gate) && aligned16(dres) && aligned16(dgate),
                   "se_tail_bwd: pointers must be 16-byte aligned");
-    hipLaunchKernelGGL(se_tail_bwd_kernel, dim3((C + IR_CB - 1) / IR_CB, N), dim3(256), 0, (hipStream_t)stream, dout, res, gate, dres, dgate,
+    hipLaunchKernelGGL(se_tail_bwd_kernel, dim3((C + RS_CB - 1) / RS_CB, N), dim3(256), 0, (hipStream_t)stream, dout, res, gate, dres, dgate,
                        Ho * Wo, C);
     return gim_check_launch("gim_se_tail_bwd");
 }
@@ -563,34 +472,34 @@ extern "C" int gim_se_tail_bwd(const float* dout, const float* res, const float*
 extern "C" int gim_subsample2_fwd(const float* x, float* y, int N, int H, int W, int C, void* stream) {
     GIM_CHECK_ARG(x && y && N > 0 && H >= 2 && W >= 2 && !(H & 1) && !(W & 1) && C > 0 && C % 4 == 0,
                   "subsample2_fwd: bad args (H, W even: the INPUT size; C % 4 == 0)");
-    GIM_CHECK_ARG(ir_aligned(x) && ir_aligned(y), "subsample2_fwd: pointers must be 16-byte aligned");
+    GIM_CHECK_ARG(aligned16(x) && aligned16(y), "subsample2_fwd: pointers must be 16-byte aligned");
     const long long n4 = (long long)N * (H / 2) * (W / 2) * (C / 4);
-    hipLaunchKernelGGL(subsample2_fwd_kernel, dim3(ir_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x, y, n4, H / 2, W / 2, C / 4);
+    hipLaunchKernelGGL(subsample2_fwd_kernel, dim3(blocks256(n4)), dim3(256), 0, (hipStream_t)stream, x, y, n4, H / 2, W / 2, C / 4);
     return gim_check_launch("gim_subsample2_fwd");
 }
 
 extern "C" int gim_subsample2_bwd(const float* dy, float* dx, int N, int H, int W, int C, void* stream) {
     GIM_CHECK_ARG(dy && dx && N > 0 && H >= 2 && W >= 2 && !(H & 1) && !(W & 1) && C > 0 && C % 4 == 0,
                   "subsample2_bwd: bad args (H, W even: the size of dx; C % 4 == 0)");
-    GIM_CHECK_ARG(ir_aligned(dy) && ir_aligned(dx), "subsample2_bwd: pointers must be 16-byte aligned");
+    GIM_CHECK_ARG(aligned16(dy) && aligned16(dx), "subsample2_bwd: pointers must be 16-byte aligned");
     const long long n4 = (long long)N * H * W * (C / 4);
-    hipLaunchKernelGGL(subsample2_bwd_kernel, dim3(ir_blocks(n4)), dim3(256), 0, (hipStream_t)stream, dy, dx, n4, H, W, C / 4);
+    hipLaunchKernelGGL(subsample2_bwd_kernel, dim3(blocks256(n4)), dim3(256), 0, (hipStream_t)stream, dy, dx, n4, H, W, C / 4);
     return gim_check_launch("gim_subsample2_bwd");
 }
 
 extern "C" int gim_dropout(const float* x, float* y, int64_t n, float p, uint64_t seed, uint64_t offset, void* stream) {
     GIM_CHECK_ARG(x && y && n > 0 && n % 4 == 0, "dropout: bad args (n % 4 == 0)");
     GIM_CHECK_ARG(p >= 0.f && p < 1.f, "dropout: p must be in [0, 1)");
-    GIM_CHECK_ARG(ir_aligned(x) && ir_aligned(y), "dropout: pointers must be 16-byte aligned");
+    GIM_CHECK_ARG(aligned16(x) && aligned16(y), "dropout: pointers must be 16-byte aligned");
     // p == 0: every hash value is >= 0 and the scale is exactly 1 - the copy is bit-exact
-    hipLaunchKernelGGL(dropout_kernel, dim3(ir_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, x, y, (long long)(n / 4), p,
+    hipLaunchKernelGGL(dropout_kernel, dim3(blocks256(n / 4)), dim3(256), 0, (hipStream_t)stream, x, y, (long long)(n / 4), p,
                        1.0f / (1.0f - p), seed, offset);
     return gim_check_launch("gim_dropout");
 }
 
 extern "C" int gim_l2norm_rows_bwd(const float* dy, const float* x, float* dx, int B, int D, void* stream) {
     GIM_CHECK_ARG(dy && x && dx && B > 0 && D > 0 && D % 4 == 0, "l2norm_rows_bwd: bad args (D % 4 == 0)");
-    GIM_CHECK_ARG(ir_aligned(dy) && ir_aligned(x) && ir_aligned(dx), "l2norm_rows_bwd: pointers must be 16-byte aligned");
+    GIM_CHECK_ARG(aligned16(dy) && aligned16(x) && aligned16(dx), "l2norm_rows_bwd: pointers must be 16-byte aligned");
     hipLaunchKernelGGL(l2norm_rows_bwd_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, dy, x, dx, B, D / 4);
     return gim_check_launch("gim_l2norm_rows_bwd");
 }
@@ -612,7 +521,7 @@ extern "C" int gim_arcface_margin_fwd(const float* cosv, const int64_t* label, f
     GIM_CHECK_ARG(cosv && label && out && B > 0 && N > 0 && s > 0.f, "arcface_margin_fwd: bad args");
     const IrMargin m = {s, cos_m, sin_m, mm, threshold};
     const long long n = (long long)B * N;
-    hipLaunchKernelGGL(arc_margin_fwd_kernel, dim3(ir_blocks(n)), dim3(256), 0, (hipStream_t)stream, cosv, label, out, n, N, m);
+    hipLaunchKernelGGL(arc_margin_fwd_kernel, dim3(blocks256(n)), dim3(256), 0, (hipStream_t)stream, cosv, label, out, n, N, m);
     return gim_check_launch("gim_arcface_margin_fwd");
 }
 
@@ -621,7 +530,7 @@ extern "C" int gim_arcface_margin_bwd(const float* dout, const float* cosv, cons
     GIM_CHECK_ARG(dout && cosv && label && dcos && B > 0 && N > 0 && s > 0.f, "arcface_margin_bwd: bad args");
     const IrMargin m = {s, cos_m, sin_m, mm, threshold};
     const long long n = (long long)B * N;
-    hipLaunchKernelGGL(arc_margin_bwd_kernel, dim3(ir_blocks(n)), dim3(256), 0, (hipStream_t)stream, dout, cosv, label, dcos, n, N, m);
+    hipLaunchKernelGGL(arc_margin_bwd_kernel, dim3(blocks256(n)), dim3(256), 0, (hipStream_t)stream, dout, cosv, label, dcos, n, N, m);
     return gim_check_launch("gim_arcface_margin_bwd");
 }
 
@@ -636,6 +545,6 @@ extern "C" int gim_softmax_ce_bwd(const float* dloss, const float* logits, const
                                   int N, void* stream) {
     GIM_CHECK_ARG(dloss && logits && label && lse && dlogits && B > 0 && N > 0, "softmax_ce_bwd: bad args");
     const long long n = (long long)B * N;
-    hipLaunchKernelGGL(softmax_ce_bwd_kernel, dim3(ir_blocks(n)), dim3(256), 0, (hipStream_t)stream, dloss, logits, label, lse, dlogits, n, N);
+    hipLaunchKernelGGL(softmax_ce_bwd_kernel, dim3(blocks256(n)), dim3(256), 0, (hipStream_t)stream, dloss, logits, label, lse, dlogits, n, N);
     return gim_check_launch("gim_softmax_ce_bwd");
 }

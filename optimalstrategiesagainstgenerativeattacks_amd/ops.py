@@ -2178,16 +2178,14 @@ def channel_affine(x, scale, shift):
     return y
 
 
-def se_tail(res, gate, shortcut, sstride=1, scale=None, shift=None):
-    """out = res * sigmoid(gate[n, c]) + shortcut[n, ::sstride, ::sstride, c]; with scale / shift also out * scale[c] + shift[c].
-    Returns out, or (out, out_bn)."""
+def _se_tail_fwd(what, res, gate, shortcut, sstride, scale=None, shift=None):
+    """Checks and forward launch of ops.se_tail / ops.se_tail_train -> (res, gate, out, out_bn or None)."""
     lib = _lib.load()
-    _no_grad_inputs("se_tail", res, gate, shortcut, scale, shift)
     res, gate, shortcut = _req(res, "res"), _req(gate, "gate"), _req(shortcut, "shortcut")
     N, Ho, Wo, C = res.shape
     if tuple(shortcut.shape) != (N, Ho * sstride, Wo * sstride, C) or tuple(gate.shape) != (N, C):
-        raise RuntimeError("se_tail: shortcut %s / gate %s do not match res %s at sstride %d"
-                           % (tuple(shortcut.shape), tuple(gate.shape), tuple(res.shape), sstride))
+        raise RuntimeError("%s: shortcut %s / gate %s do not match res %s at sstride %s"
+                           % (what, tuple(shortcut.shape), tuple(gate.shape), tuple(res.shape), sstride))
     out = torch.empty_like(res)
     out_bn = None
     if scale is not None:
@@ -2195,6 +2193,14 @@ def se_tail(res, gate, shortcut, sstride=1, scale=None, shift=None):
         out_bn = torch.empty_like(res)
     check(lib.gim_se_tail(_p(res), _p(gate), _p(shortcut), _p(scale), _p(shift), _p(out), _p(out_bn), N, Ho, Wo, C, sstride, _stream()),
           "se_tail")
+    return res, gate, out, out_bn
+
+
+def se_tail(res, gate, shortcut, sstride=1, scale=None, shift=None):
+    """out = res * sigmoid(gate[n, c]) + shortcut[n, ::sstride, ::sstride, c]; with scale / shift also out * scale[c] + shift[c].
+    Returns out, or (out, out_bn)."""
+    _no_grad_inputs("se_tail", res, gate, shortcut, scale, shift)
+    _, _, out, out_bn = _se_tail_fwd("se_tail", res, gate, shortcut, sstride, scale, shift)
     return out if out_bn is None else (out, out_bn)
 
 
@@ -2210,44 +2216,59 @@ def pair_score(a, b):
     return out
 
 
-def absdiff(a, b):
-    """|a - b|, elementwise."""
-    lib = _lib.load()
-    _no_grad_inputs("absdiff", a, b)
+def _absdiff_fwd(what, a, b):
+    """Checks and forward launch of ops.absdiff / ops.absdiff_train -> (a, b, y)."""
     a, b = _req(a, "a"), _req(b, "b")
     if a.shape != b.shape:
-        raise RuntimeError("absdiff: shapes differ")
+        raise RuntimeError("%s: shapes differ" % what)
     y = torch.empty_like(a)
-    check(lib.gim_absdiff(_p(a), _p(b), _p(y), a.numel(), _stream()), "absdiff")
-    return y
+    check(_lib.load().gim_absdiff(_p(a), _p(b), _p(y), a.numel(), _stream()), "absdiff")
+    return a, b, y
+
+
+def absdiff(a, b):
+    """|a - b|, elementwise."""
+    _no_grad_inputs("absdiff", a, b)
+    return _absdiff_fwd("absdiff", a, b)[2]
+
+
+def _l2norm_rows_fwd(x):
+    """Forward launch of ops.l2norm_rows / ops.l2norm_rows_train -> (x, y)."""
+    x = _req(x, "x")
+    y = torch.empty_like(x)
+    check(_lib.load().gim_l2norm_rows(_p(x), _p(y), x.shape[0], x.shape[1], _stream()), "l2norm_rows")
+    return x, y
 
 
 def l2norm_rows(x):
     """x / |x| per row of a [B, D] matrix."""
-    lib = _lib.load()
     _no_grad_inputs("l2norm_rows", x)
-    x = _req(x, "x")
-    y = torch.empty_like(x)
-    check(lib.gim_l2norm_rows(_p(x), _p(y), x.shape[0], x.shape[1], _stream()), "l2norm_rows")
-    return y
+    return _l2norm_rows_fwd(x)[1]
 
 
 # --------------------------------------------------------------------------------------------
 # training the siamese baseline (baseline_training.py): BatchNorm with batch statistics + ReLU + MaxPool2d(2), |a - b|
 # --------------------------------------------------------------------------------------------
-def _bn_partials(rows, C, device):
-    n = _lib.load().gim_bn_partials_floats(rows, C)
-    if n <= 0:
-        check(n, "bn_partials_floats")
-    return torch.empty(n, device=device, dtype=torch.float32)
-
-
 def bn_slabs(rows):
     """Number of row slabs the two-stage sums of the BatchNorm kernels cut a map of `rows` rows into."""
     n = _lib.load().gim_bn_slabs(rows)
     if n <= 0:
         check(n, "bn_slabs")
     return n
+
+
+def _slab_partials(rows, C, sums, device):
+    """Stage-1 buffer of `sums` per-channel sums over `rows` rows (csrc/rowsum.h): one float per sum, slab and channel."""
+    return torch.empty(sums * bn_slabs(rows) * C, device=device, dtype=torch.float32)
+
+
+def _channel_grads(need, params, sums):
+    """The rule for the gradients of per-channel parameters.  need[i]: autograd wants the gradient of params[i] (a [C] tensor or
+    None), whose total the kernel writes to sums[i].  -> (acc, grads): acc[i] is the parameter's .grad where that is the optimizer's
+    bucket - the kernel ADDS the total there and grads[i] is None - and otherwise None, and grads[i] = sums[i] goes back to autograd."""
+    acc = [_grad_target(p) if (p is not None and n) else None for p, n in zip(params, need)]
+    grads = [sums[i] if (p is not None and n and acc[i] is None) else None for i, (p, n) in enumerate(zip(params, need))]
+    return acc, grads
 
 
 def _req_map(z, what):
@@ -2257,13 +2278,23 @@ def _req_map(z, what):
     return z
 
 
+def _req_rows(x, what):
+    """x [..., C] with C % 4 == 0, contiguous -> (x, rows, C)."""
+    x = _req(x, what)
+    C = x.shape[-1]
+    if x.dim() < 2 or C % 4:
+        raise RuntimeError("%s must be [..., C] with C %% 4 == 0, got %s" % (what, tuple(x.shape)))
+    return x, x.numel() // C, C
+
+
 def bn_stats(z, eps=1e-5, running_mean=None, running_var=None, num_batches_tracked=None, momentum=0.1):
-    """(mean [C], invstd [C]) of an NHWC map over its N * H * W rows (biased variance, as nn.BatchNorm2d normalises in training mode);
-    with running_mean / running_var / num_batches_tracked these are updated in place as nn.BatchNorm2d does (unbiased variance)."""
+    """(mean [C], invstd [C]) over the M >= 2 rows of any [..., C] tensor with C % 4 == 0 (an NHWC map of any size, [B, C] of a
+    BatchNorm1d): the biased variance, as nn.BatchNorm normalises in training mode; with running_mean / running_var /
+    num_batches_tracked these are updated in place as nn.BatchNorm does (unbiased variance)."""
     lib = _lib.load()
-    z = _req_map(z, "z")
-    C = z.shape[3]
-    M = z.numel() // C
+    z, M, C = _req_rows(z, "z")
+    if M < 2:
+        raise RuntimeError("batch statistics need at least two rows, got %s" % (tuple(z.shape),))
     if momentum is None:
         raise NotImplementedError("bn_stats: momentum=None (cumulative moving average) is not implemented")
     for name, v in (("running_mean", running_mean), ("running_var", running_var)):
@@ -2272,7 +2303,7 @@ def bn_stats(z, eps=1e-5, running_mean=None, running_var=None, num_batches_track
     if num_batches_tracked is not None and not (num_batches_tracked.is_cuda and num_batches_tracked.dtype == torch.int64):
         raise RuntimeError("bn_stats: num_batches_tracked must be a CUDA int64 tensor")
     stats = torch.empty((2, C), device=z.device, dtype=torch.float32)
-    partials = _bn_partials(M, C, z.device)
+    partials = _slab_partials(M, C, 2, z.device)      # (mean, M2) per slab and channel
     nbt = None if num_batches_tracked is None else num_batches_tracked.data_ptr()
     check(lib.gim_bn_stats(_p(z), _p(partials), _p(stats), _p(stats, C), _p(running_mean), _p(running_var), nbt, M, C,
                            float(momentum), float(eps), _stream()), "bn_stats")
@@ -2309,10 +2340,9 @@ class BnReluMaxPool2Fn(Function):
         dp = _req(dp, "dp")
         st = _stream()
         sums = torch.empty((2, C), device=z.device, dtype=torch.float32)      # dgamma, dbeta
-        partials = _bn_partials(N * (H // 2) * (W // 2), C, z.device)
+        partials = _slab_partials(N * (H // 2) * (W // 2), C, 2, z.device)
         need = ctx.needs_input_grad
-        acc_w = _grad_target(weight) if need[1] else None
-        acc_b = _grad_target(bias) if need[2] else None
+        (acc_w, acc_b), (dw, db) = _channel_grads(need[1:3], (weight, bias), sums)
         check(lib.gim_bn_pool_bwd_reduce(_p(dp), _p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(partials), _p(sums), _p(sums, C),
                                          _p(acc_w), _p(acc_b), N, H, W, C, st), "bn_pool_bwd_reduce")
         dz = None
@@ -2320,8 +2350,6 @@ class BnReluMaxPool2Fn(Function):
             dz = torch.empty_like(z)
             check(lib.gim_bn_pool_bwd_dx(_p(dp), _p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(sums), _p(sums, C), _p(dz),
                                          N, H, W, C, st), "bn_pool_bwd_dx")
-        dw = sums[0] if (need[1] and acc_w is None) else None
-        db = sums[1] if (need[2] and acc_b is None) else None
         return dz, dw, db, None, None, None, None, None
 
 
@@ -2337,25 +2365,17 @@ class AbsDiffFn(Function):
 
     @staticmethod
     def forward(ctx, a, b):
-        lib = _lib.load()
-        halves = b is None
-        if halves:
+        ctx.halves = b is None
+        if ctx.halves:
             e = _req(a, "e")
             if e.dim() != 2 or e.shape[0] % 2:
                 raise RuntimeError("absdiff_halves: a [2B, D] matrix expected, got %s" % (tuple(e.shape),))
             B = e.shape[0] // 2
-            a, b = e[:B], e[B:]
-        else:
-            a, b = _req(a, "a"), _req(b, "b")
-            if a.shape != b.shape:
-                raise RuntimeError("absdiff_train: shapes differ")
-        y = torch.empty_like(a)
-        check(lib.gim_absdiff(_p(a), _p(b), _p(y), a.numel(), _stream()), "absdiff")
-        if halves:
+            y = _absdiff_fwd("absdiff_halves", e[:B], e[B:])[2]
             ctx.save_for_backward(e)
         else:
+            a, b, y = _absdiff_fwd("absdiff_train", a, b)
             ctx.save_for_backward(a, b)
-        ctx.halves = halves
         return y
 
     @staticmethod
@@ -2393,15 +2413,6 @@ def absdiff_halves(e):
 # parameters (gamma, beta, PReLU slope) are ADDED into the parameter's .grad where that is the optimizer's bucket (_grad_target),
 # and None goes back to autograd - as BnReluMaxPool2Fn does.
 # --------------------------------------------------------------------------------------------
-def _req_rows(x, what):
-    """x [..., C] with C % 4 == 0, contiguous -> (x, rows, C)."""
-    x = _req(x, what)
-    C = x.shape[-1]
-    if x.dim() < 2 or C % 4:
-        raise RuntimeError("%s must be [..., C] with C %% 4 == 0, got %s" % (what, tuple(x.shape)))
-    return x, x.numel() // C, C
-
-
 def _req_chan(v, name, C):
     v = _req(v, name)
     if tuple(v.shape) != (C,):
@@ -2409,35 +2420,10 @@ def _req_chan(v, name, C):
     return v
 
 
-def _sum_partials(rows, C, device):
-    return torch.empty(3 * bn_slabs(rows) * C, device=device, dtype=torch.float32)
-
-
 def _req_label(label, B):
     if not (torch.is_tensor(label) and label.is_cuda and label.dtype == torch.int64 and tuple(label.shape) == (B,)):
         raise RuntimeError("label must be a CUDA int64 tensor of shape [%d]" % B)
     return label if label.is_contiguous() else label.contiguous()
-
-
-def bn_stats_rows(z, eps=1e-5, running_mean=None, running_var=None, num_batches_tracked=None, momentum=0.1):
-    """ops.bn_stats for any [..., C] tensor of M >= 2 rows (maps of odd size, BatchNorm1d): (mean [C], invstd [C])."""
-    lib = _lib.load()
-    z, M, C = _req_rows(z, "z")
-    if M < 2:
-        raise RuntimeError("batch statistics need at least two rows, got %s" % (tuple(z.shape),))
-    if momentum is None:
-        raise NotImplementedError("bn_stats_rows: momentum=None (cumulative moving average) is not implemented")
-    for name, v in (("running_mean", running_mean), ("running_var", running_var)):
-        if v is not None and (tuple(_req(v, name).shape) != (C,) or not v.is_contiguous()):
-            raise RuntimeError("bn_stats_rows: %s must be a contiguous [C] tensor" % name)
-    if num_batches_tracked is not None and not (num_batches_tracked.is_cuda and num_batches_tracked.dtype == torch.int64):
-        raise RuntimeError("bn_stats_rows: num_batches_tracked must be a CUDA int64 tensor")
-    stats = torch.empty((2, C), device=z.device, dtype=torch.float32)
-    partials = _bn_partials(M, C, z.device)
-    nbt = None if num_batches_tracked is None else num_batches_tracked.data_ptr()
-    check(lib.gim_bn_stats(_p(z), _p(partials), _p(stats), _p(stats, C), _p(running_mean), _p(running_var), nbt, M, C,
-                           float(momentum), float(eps), _stream()), "bn_stats")
-    return stats[0], stats[1]
 
 
 class BatchNormFn(Function):
@@ -2451,7 +2437,7 @@ class BatchNormFn(Function):
         z, M, C = _req_rows(z, "z")
         weight, bias = _req_chan(weight, "weight", C), _req_chan(bias, "bias", C)
         slope = None if slope is None else _req_chan(slope, "slope", C)
-        mean, invstd = bn_stats_rows(z, eps, running_mean, running_var, num_batches_tracked, momentum)
+        mean, invstd = bn_stats(z, eps, running_mean, running_var, num_batches_tracked, momentum)
         y = torch.empty_like(z)
         check(lib.gim_bn_apply_fwd(_p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(slope), _p(y), M, C, _stream()), "bn_apply_fwd")
         ctx.save_for_backward(z, weight, bias, mean, invstd, slope)
@@ -2467,11 +2453,9 @@ class BatchNormFn(Function):
         dy = _req(dy, "dy")
         st = _stream()
         sums = torch.empty((3, C), device=z.device, dtype=torch.float32)      # dgamma, dbeta, dslope
-        partials = _sum_partials(M, C, z.device)
+        partials = _slab_partials(M, C, 3, z.device)
         need = ctx.needs_input_grad
-        acc_w = _grad_target(weight) if need[1] else None
-        acc_b = _grad_target(bias) if need[2] else None
-        acc_s = _grad_target(slope) if (slope is not None and need[3]) else None
+        (acc_w, acc_b, acc_s), (dw, db, ds) = _channel_grads(need[1:4], (weight, bias, slope), sums)
         check(lib.gim_bn_bwd_reduce(_p(dy), _p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(slope), _p(partials), _p(sums),
                                     _p(sums, C), _p(sums, 2 * C) if slope is not None else None, _p(acc_w), _p(acc_b), _p(acc_s), M, C, st),
               "bn_bwd_reduce")
@@ -2480,9 +2464,6 @@ class BatchNormFn(Function):
             dz = torch.empty_like(z)
             check(lib.gim_bn_bwd_dx(_p(dy), _p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(slope), _p(sums), _p(sums, C), _p(dz),
                                     M, C, st), "bn_bwd_dx")
-        dw = sums[0] if (need[1] and acc_w is None) else None
-        db = sums[1] if (need[2] and acc_b is None) else None
-        ds = sums[2] if (slope is not None and need[3] and acc_s is None) else None
         return dz, dw, db, ds, None, None, None, None, None
 
 
@@ -2514,13 +2495,13 @@ class PReLUFn(Function):
         M = x.numel() // C
         dy = _req(dy, "dy")
         dx = torch.empty_like(x)
-        ds = partials = acc = None
+        sums = partials = None
         if slope is not None:
-            ds = torch.empty(C, device=x.device, dtype=torch.float32)
-            partials = _sum_partials(M, C, x.device)
-            acc = _grad_target(slope) if ctx.needs_input_grad[1] else None
-        check(lib.gim_prelu_bwd(_p(dy), _p(x), _p(slope), _p(dx), _p(partials), _p(ds), _p(acc), M, C, _stream()), "prelu_bwd")
-        return dx, (ds if (slope is not None and ctx.needs_input_grad[1] and acc is None) else None)
+            sums = torch.empty((1, C), device=x.device, dtype=torch.float32)
+            partials = _slab_partials(M, C, 1, x.device)
+        (acc,), (ds,) = _channel_grads(ctx.needs_input_grad[1:2], (slope,), sums)
+        check(lib.gim_prelu_bwd(_p(dy), _p(x), _p(slope), _p(dx), _p(partials), _p(sums), _p(acc), M, C, _stream()), "prelu_bwd")
+        return dx, ds
 
 
 def prelu(x, slope):
@@ -2563,14 +2544,9 @@ class SETailFn(Function):
 
     @staticmethod
     def forward(ctx, res, gate, shortcut, sstride):
-        lib = _lib.load()
-        res, gate, shortcut = _req(res, "res"), _req(gate, "gate"), _req(shortcut, "shortcut")
-        N, Ho, Wo, C = res.shape
-        if sstride not in (1, 2) or tuple(shortcut.shape) != (N, Ho * sstride, Wo * sstride, C) or tuple(gate.shape) != (N, C):
-            raise RuntimeError("se_tail_train: shortcut %s / gate %s do not match res %s at sstride %s"
-                               % (tuple(shortcut.shape), tuple(gate.shape), tuple(res.shape), sstride))
-        out = torch.empty_like(res)
-        check(lib.gim_se_tail(_p(res), _p(gate), _p(shortcut), None, None, _p(out), None, N, Ho, Wo, C, sstride, _stream()), "se_tail")
+        if sstride not in (1, 2):      # the backward scatters the shortcut's gradient with subsample2_bwd
+            raise RuntimeError("se_tail_train: sstride must be 1 or 2, got %s" % (sstride,))
+        res, gate, out, _ = _se_tail_fwd("se_tail_train", res, gate, shortcut, sstride)
         ctx.save_for_backward(res, gate)
         ctx.sstride = sstride
         return out
@@ -2633,11 +2609,9 @@ class L2NormRowsFn(Function):
 
     @staticmethod
     def forward(ctx, x):
-        x = _req(x, "x")
-        if x.dim() != 2 or x.shape[1] % 4:
+        if x.dim() != 2 or x.shape[1] % 4:      # the backward kernel moves 16 bytes per access
             raise RuntimeError("l2norm_rows_train: [B, D] with D %% 4 == 0 expected, got %s" % (tuple(x.shape),))
-        y = torch.empty_like(x)
-        check(_lib.load().gim_l2norm_rows(_p(x), _p(y), x.shape[0], x.shape[1], _stream()), "l2norm_rows")
+        x, y = _l2norm_rows_fwd(x)
         ctx.save_for_backward(x)
         return y
 

@@ -106,6 +106,7 @@ SHAPES = {
     "rect": (3, 4, 8, 64),            # H != W
     "c132": (2, 2, 2, 132),           # a channel count that is no multiple of the workgroup's 64-channel block
     "slabs": (5, 16, 16, 64),         # M = 1280 rows: several slabs, the last groups of the combine empty
+    "slabs65": (65, 16, 16, 4),       # 4160 pooled rows: 65 slabs, lane 0 of the backward sums' stage 2 adds two; 260 for the statistics
 }
 FILL = {"slabs": "#1"}      # fill names whose fp64 reference has the margins above ("bnt/slabs" itself has a window maximum of 4.5e-5)
 
@@ -116,8 +117,32 @@ def test_bn_relu_maxpool2_vs_fp64(name):
     N, H, W, C = SHAPES[name]
     if name == "slabs":
         assert ops.bn_slabs(N * H * W) >= 3 and ops.bn_slabs(N * (H // 2) * (W // 2)) >= 2
+    if name == "slabs65":
+        assert ops.bn_slabs(N * H * W) == 260 and ops.bn_slabs(N * (H // 2) * (W // 2)) == 65
     tag = "bnt/" + name + FILL.get(name, "")
     check_case(tag, grid_map(tag, N, H, W, C), *affine(tag, C))
+
+
+def test_bn_relu_maxpool2_adds_into_existing_grad():
+    """gamma.grad and beta.grad exist (FusedAdam's bucket): the sums are ADDED there by the kernel and autograd gets None."""
+    from optimalstrategiesagainstgenerativeattacks_amd import ops
+    N, H, W, C = SHAPES["rect"]
+    tag = "bnt/rect"
+    z, (gamma, beta) = grid_map(tag, N, H, W, C), affine(tag, C)
+    dp = T(pf.uniform(tag + "/dp", (N, H // 2, W // 2, C)))
+    ref = reference(tag, z, gamma, beta, dp)
+    d = dev()
+    zg = z.float().to(d).requires_grad_()
+    gg, bg = gamma.float().to(d).requires_grad_(), beta.float().to(d).requires_grad_()
+    gg.grad, bg.grad = torch.full_like(gg.detach(), 0.25), torch.full_like(bg.detach(), 0.25)
+    rm, rv = ref["rm0"].float().to(d), ref["rv0"].float().to(d)
+    p = ops.bn_relu_maxpool2(zg, gg, bg, rm, rv, torch.tensor(7, dtype=torch.int64, device=d), MOMENTUM, EPS)
+    dz, dgamma, dbeta = torch.autograd.grad(p, (zg, gg, bg), dp.float().to(d), allow_unused=True)
+    assert dgamma is None and dbeta is None
+    for k, got, tol in (("dgamma", gg.grad - 0.25, TOL), ("dbeta", bg.grad - 0.25, TOL), ("dz", dz, TOL_DZ)):
+        e = relerr(got, ref[k])
+        print("%s bucket %s: %.2e" % (tag, k, e))
+        assert e < tol, (k, e)
 
 
 def test_offset_map_keeps_its_variance():

@@ -63,7 +63,10 @@ def close(got, ref, names=None, tol=TOL):
 
 
 # ---------------------------------------------------------------------------------------------------- BatchNorm
-BN_SHAPES = [(3, 6, 6, 8), (2, 5, 7, 24), (8, 512), (2, 64), (4, 32, 32, 64)]
+BN_SHAPES = [(3, 6, 6, 8), (2, 5, 7, 24), (8, 512), (2, 64), (4, 32, 32, 64), (4161, 8), (65537, 4)]
+# more slabs than the 64 lanes of the sums' stage 2, so that a lane adds a second slab: 66 slabs of 64 rows (lanes 0 and 1 add two,
+# the last slab holds one row), and 1009 slabs of 65 rows at the cap of 1024 (the last one holds 17)
+BN_SLABS = {(4161, 8): 66, (65537, 4): 1009}
 
 
 def bn_inputs(tag, shape, prelu):
@@ -135,6 +138,8 @@ def test_batch_norm(shape, prelu):
     inp = bn_inputs(tag, shape, prelu)
     ref = bn_reference(*inp)
     M = inp[0].numel() // shape[-1]
+    if shape in BN_SLABS:
+        assert ops_mod().bn_slabs(M) == BN_SLABS[shape]
     bounds = {}
     if M == 2:
         # two rows: xhat = +-1 / sqrt(1 + eps / var), and dz = gamma * invstd * (dyhat - mean - xhat * mean(dyhat * xhat)) cancels to
@@ -157,7 +162,7 @@ def test_batch_norm_offset_map_keeps_its_variance():
     z = torch.from_numpy(np.rint(pf.normal("irse/bn/offset", (2, 8, 8, 8)) * 16.0) / 8.0 + 1024.0).float()
     x = z.double().reshape(-1, 8)
     rm, rv = torch.zeros(8, device=dev()), torch.ones(8, device=dev())
-    mean, invstd = ops.bn_stats_rows(z.to(dev()), EPS, rm, rv, None, MOMENTUM)
+    mean, invstd = ops.bn_stats(z.to(dev()), EPS, rm, rv, None, MOMENTUM)
     assert float(x.mean(0).min()) > 1000.0
     assert relerr(mean, x.mean(0)) < TOL and relerr(invstd, 1.0 / torch.sqrt(x.var(0, unbiased=False) + EPS)) < TOL
     assert relerr(rv, 0.9 + 0.1 * x.var(0, unbiased=True)) < TOL

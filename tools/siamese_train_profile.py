@@ -104,11 +104,12 @@ def summarise(path):
     with open(path) as f:
         for r in csv.DictReader(f):
             name = r["Kernel_Name"].split("(")[0].replace("void ", "")
-            if name.startswith("bn_"):
+            if name.startswith(("bn_", "rowsum_")):
                 wg = int(r["Grid_Size_X"]) * int(r["Grid_Size_Y"]) // (int(r["Workgroup_Size_X"]) * int(r["Workgroup_Size_Y"]))
                 rows[name].append((int(r["Start_Timestamp"]), (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-3, wg))
     # bytes each kernel has to move at a map of Z bytes: stats reads z; forward reads z, writes z / 4; the backward sums read z and
-    # dp (z / 4); dz reads z and dp and writes z; the two finalize kernels read 8 bytes per channel and slab
+    # dp (z / 4); dz reads z and dp and writes z; the two stage-2 kernels (bn_finalize_kernel, rowsum_finalize_kernel) read 8 bytes per channel and
+    # slab
     moved = {"bn_stats_slab_kernel": 1.0, "bn_relu_maxpool2_fwd_kernel": 1.25, "bn_pool_bwd_slab_kernel": 1.25, "bn_pool_bwd_dx_kernel": 2.25}
     print("%-32s %8s %10s %9s %9s %8s %s" % ("kernel", "map", "MB moved", "median us", "min us", "TB/s", "of the 6.29 TB/s copy rate"))
     for name in sorted(rows):
