@@ -568,6 +568,37 @@ int gim_softmax_ce_fwd(const float* logits, const int64_t* label, float* loss, f
 int gim_softmax_ce_bwd(const float* dloss, const float* logits, const int64_t* label, const float* lse, float* dlogits, int B, int N,
                        void* stream);
 
+/* ---- Strided convolution for training (baseline_training.py: the stride-2 3x3 convolution and the strided 1x1 shortcut convolution of
+ * a bottleneck_IR_SE unit, arcface/models.py:69-76, forward and autograd).  Plain convolutions over their own KH x KH taps: no pool /
+ * ups / fold, no sigma, no activation.  The shape is gim_conv2d_infer's struct: H, W the INPUT size (powers of two >= 2), KH in
+ * {1, 3}, pad = (KH - 1) / 2, stride in {1, 2}; x / dx [N][H][W][Cin], y / dy [N][H/stride][W/stride][Cout], w / dw [Cout][KH][KH][Cin].
+ * fp32 operands on the fp32 MFMA.  Every launch executes 2 * N * (H/stride) * (W/stride) * Cin * Cout * KH^2 FLOPs, the algorithmic
+ * count: a stride-2 convolution is not computed at full resolution and subsampled.  Batches beyond the 32-bit buffer-offset range
+ * are halved as everywhere.
+ *   gim_conv2d_strided_fwd  : y = conv(x, w, stride) + bias (bias NULL = 0).  This IS the launch of gim_conv2d_infer with a null
+ *       slope (no code of its own): never splits K, bitwise reproducible.
+ *   gim_conv2d_strided_dgrad: dx[n,iy,ix,ci] = sum over the taps (a, b) with (iy + pad - a), (ix + pad - b) even and
+ *       oy = (iy + pad - a) / 2 < H/2, ox likewise, of w[co][a][b][ci] * dy[n][oy][ox][co].  The four input-parity classes of dx have
+ *       1 / 2 / 2 / 4 taps for KH = 3 (1 / 0 / 0 / 0 for KH = 1): one launch per class that has taps, with that class's own K extent -
+ *       9 taps per 2 x 2 block of dx, no zero tap is multiplied.  Every element of dx is defined by the call (the caller hands
+ *       uninitialised memory): one clear of dx precedes the launches when a class has no taps or a launch splits K (float atomics into
+ *       zeros, as gim_conv2d_dgrad does); deterministic != 0: no launch splits K.  stride 1 forwards to gim_conv2d_dgrad.
+ *   gim_conv2d_strided_wgrad: dw[co][a][b][ci] = sum_{n,oy,ox} dy[n,oy,ox,co] * x[n][oy*stride+a-pad][ox*stride+b-pad][ci] and, with
+ *       dbias != NULL, dbias[co] = sum dy.  workspace == NULL: the pixel slices combine by float atomics; accumulate == 0: dw / dbias
+ *       are cleared by the call, != 0: the gradient is ADDED to what they hold (the optimizer's flat gradient bucket).  workspace !=
+ *       NULL (the bytes gim_conv2d_strided_wgrad_workspace reports): the deterministic combine - one slab per pixel slice, added in
+ *       a fixed order (gim_wgrad_finish), into dw / dbias or (accumulate) onto them.  The library never allocates.
+ *   gim_conv2d_strided_plan : introspection (tests), nothing is launched.  kind 0 forward, 1 dgrad (stride 2), 2 wgrad.  out[16] = four
+ *       rows {K extent of the launch = taps * gathered channels (wgrad: columns of dw), tile rows, tile columns, K slices (wgrad: pixel
+ *       slices)}, one row per launch - the dgrad's classes in the order (0,0) (0,1) (1,0) (1,1), a class without taps as zeros - the
+ *       rest -1. */
+int gim_conv2d_strided_fwd(const float* x, const float* w, const float* bias, float* y, const gim_infer_conv* shape, void* stream);
+int gim_conv2d_strided_dgrad(const float* dy, const float* w, float* dx, const gim_infer_conv* shape, int deterministic, void* stream);
+int gim_conv2d_strided_wgrad_workspace(const gim_infer_conv* shape, int64_t* bytes);
+int gim_conv2d_strided_wgrad(const float* dy, const float* x, float* dw, float* dbias, const gim_infer_conv* shape, int accumulate,
+                             float* workspace, void* stream);
+int gim_conv2d_strided_plan(const gim_infer_conv* shape, int kind, int32_t* out);
+
 /* Stream self-check: one wave busy for `usec` microseconds (1 .. 5000, constant 100 MHz wall clock) on `stream`.  The host
  * launches one per engine stream at the same moment and event-times the total: streams that share a HIP hardware queue serialize
  * (nn.DataParallel's one-thread-per-device streams of training/gim_img_training.py:406-411 have no such aliasing to check). */

@@ -156,6 +156,11 @@ SIGNATURES = {
     "gim_arcface_margin_bwd": [P, P, P, P, c_int, c_int, c_float, c_float, c_float, c_float, c_float, P],
     "gim_softmax_ce_fwd": [P, P, P, P, P, c_int, c_int, P],
     "gim_softmax_ce_bwd": [P, P, P, P, P, c_int, c_int, P],
+    "gim_conv2d_strided_fwd": [P, P, P, P, POINTER(GimInferConv), P],
+    "gim_conv2d_strided_dgrad": [P, P, P, POINTER(GimInferConv), c_int, P],
+    "gim_conv2d_strided_wgrad_workspace": [POINTER(GimInferConv), POINTER(c_int64)],
+    "gim_conv2d_strided_wgrad": [P, P, P, P, POINTER(GimInferConv), c_int, P, P],
+    "gim_conv2d_strided_plan": [POINTER(GimInferConv), c_int, P],
     "gim_version": [],
 }
 

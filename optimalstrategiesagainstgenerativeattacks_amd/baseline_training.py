@@ -17,7 +17,7 @@ Both inputs of a pair batch go through the encoder in ONE pass, so the batch sta
 
 The second half of the file trains the ArcFace baseline (``baselines.ArcFace`` on the IR-SE ``Backbone``: ``baselines/arcface/models.py``)
 the same way: ``arcface_forward_train`` is the reference's ``ArcFace.forward(x, label)`` in training mode over the inference classes'
-parameters (csrc/irse_train.hip for everything but the convolutions, which all run at stride 1 through ``ops.conv2d``),
+parameters (csrc/irse_train.hip for everything but the convolutions: ``ops.conv2d``, and ``ops.conv2d_strided`` for the stride-2 ones),
 ``train_arcface`` writes ``ckpts/model_*.pt['arcface']`` and the ``args.json`` that ``get_arcface_authenticator`` reads."""
 import json
 import os
@@ -311,26 +311,39 @@ def _bn_train(x, bn, slope=None):
     return ops.batch_norm(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps, slope)
 
 
+# Host switch (read once at import): GIM_NO_STRIDED_CONV=1 restores the stride-1 + subsample route of the stride-2 convolutions, for
+# same-box A/B runs; the two routes differ by rounding only.
+_STRIDED_CONV = os.environ.get("GIM_NO_STRIDED_CONV") is None
+
+
 def irse_unit_train(unit, x):
-    """One bottleneck_IR_SE (a baselines._Unit) with batch statistics on an NHWC map.  Every convolution runs at stride 1: the
-    stride-2 3x3 convolution (padding 1) is the even-position subsample of the stride-1 one, the strided 1x1 shortcut convolution
-    the 1x1 convolution of the subsampled input.  The SE bottleneck's two 1x1 convolutions run on the [N, 1, 1, C] squeeze with the
-    nn.Conv2d parameters themselves (their gradients land in the optimizer's bucket), the ReLU between them as ops.prelu without a
-    slope."""
+    """One bottleneck_IR_SE (a baselines._Unit) with batch statistics on an NHWC map.  The stride-2 3x3 convolution (padding 1) and the
+    strided 1x1 shortcut convolution run as ops.conv2d_strided: forward, input gradient and weight gradient execute the convolution's
+    own FLOPs.  (GIM_NO_STRIDED_CONV: at stride 1 through ops.conv2d - the stride-2 3x3 convolution as the even-position subsample of
+    the stride-1 one, the shortcut as the 1x1 convolution of the subsampled input.)  The SE bottleneck's two 1x1 convolutions run on
+    the [N, 1, 1, C] squeeze with the nn.Conv2d parameters themselves (their gradients land in the optimizer's bucket), the ReLU
+    between them as ops.prelu without a slope."""
     r = unit.res_layer
+    strided = unit.stride == 2 and _STRIDED_CONV
     h = ops.conv2d(_bn_train(x, r[0]), r[1].weight)
-    h = ops.conv2d(ops.prelu(h, r[2].weight), r[3].weight)
-    if unit.stride == 2:
-        h = ops.subsample2(h)
+    h = ops.prelu(h, r[2].weight)
+    if strided:
+        h = ops.conv2d_strided(h, r[3].weight, stride=2)
+    else:
+        h = ops.conv2d(h, r[3].weight)
+        if unit.stride == 2:
+            h = ops.subsample2(h)
     h = _bn_train(h, r[4])
     N, Ho, Wo, C = h.shape
     z = ops.mean_dim1(h.view(N, Ho * Wo, C)).view(N, 1, 1, C)
     gate = ops.conv2d(ops.prelu(ops.conv2d(z, r[5].fc1.weight), None), r[5].fc2.weight).view(N, C)
     if unit.cin == unit.depth:
         return ops.se_tail_train(h, gate, x, unit.stride)
-    xs = ops.subsample2(x) if unit.stride == 2 else x
-    sc = _bn_train(ops.conv2d(xs, unit.shortcut_layer[0].weight), unit.shortcut_layer[1])
-    return ops.se_tail_train(h, gate, sc, 1)
+    if strided:
+        sc = ops.conv2d_strided(x, unit.shortcut_layer[0].weight, stride=2)
+    else:
+        sc = ops.conv2d(ops.subsample2(x) if unit.stride == 2 else x, unit.shortcut_layer[0].weight)
+    return ops.se_tail_train(h, gate, _bn_train(sc, unit.shortcut_layer[1]), 1)
 
 
 def arcface_forward_train(model, x, label, dropout=None):

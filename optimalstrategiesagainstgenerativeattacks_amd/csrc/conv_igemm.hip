@@ -1949,9 +1949,9 @@ static int run_igemm(const ConvP& p, const IgemmPlan& q, size_t y_elems, hipStre
 // One forward-style call, validated and filled (the first half of an entry point): what plan_igemm and run_igemm need.
 struct ConvCall { ConvP p; size_t y_elems; int bmode, gen; };   // y_elems: floats of the output (a split-K launch clears them first)
 
-// the second half of every forward-style entry point
-static int plan_and_run(ConvCall& c, void* stream, const char* what) {
-    const IgemmPlan q = plan_igemm(c.p, c.bmode, c.gen);
+// the second half of every forward-style entry point: plan_and_run; run_planned launches a plan the caller already made of c
+// (gim_conv2d_strided_dgrad plans its four launches before it enqueues the first)
+static int run_planned(const ConvCall& c, const IgemmPlan& q, void* stream, const char* what) {
     hipStream_t st = (hipStream_t)stream;
     int rc;
     if (c.bmode == 0) rc = c.gen ? run_igemm<0, 1>(c.p, q, c.y_elems, st) : run_igemm<0, 0>(c.p, q, c.y_elems, st);
@@ -1960,6 +1960,10 @@ static int plan_and_run(ConvCall& c, void* stream, const char* what) {
     else if (c.gen == 2) rc = run_igemm<1, 2>(c.p, q, c.y_elems, st);
     else rc = run_igemm<1, 3>(c.p, q, c.y_elems, st);
     return rc ? rc : gim_check_launch(what);
+}
+static int plan_and_run(ConvCall& c, void* stream, const char* what) {
+    const IgemmPlan q = plan_igemm(c.p, c.bmode, c.gen);
+    return run_planned(c, q, stream, what);
 }
 
 // What every forward-style entry point fills the same way: geometry, GEMM sizes, zero page, the buffer range of the gathered tensor
@@ -2599,6 +2603,25 @@ static int wgrad_call(WgP& p, WgPlan& q, const float* dy, const float* x, float*
     return GIM_OK;
 }
 
+// The launch of the MFMA families (conv_wgrad_kernel / conv_wgrad_f16_kernel) for a filled WgP and its plan.
+// What depends on the real pointers is decided here (the plan assumes aligned operands): vector width per operand as the kernel
+// sees it (the sub-pixel form swaps the roles: A = p.dy with p.Cout channels, B = p.x with p.Cin), K step, fast B path.
+static void launch_wgrad_mfma(const WgP& p, const WgPlan& q, int prec, hipStream_t st) {
+    const dim3 g(q.gx, q.gy, q.gz);
+    const bool va = (p.Cout % 4 == 0) && !((uintptr_t)p.dy & 15);
+    const bool vb = (p.Cin % 4 == 0) && !((uintptr_t)p.x & 15);
+    const int bk = (q.bk == 32 && va && vb) ? 32 : BK;
+    const bool fastb = vb && p.g.ups == 0 && ((p.g.H * p.g.W) & (bk - 1)) == 0;   // a K step stays inside one image
+    const bool f16 = q.family == WG_MFMA_F16 && va && vb && bk == 32, sat = prec != 2;   // (prec 2: IEEE conversion, conv_f16.inc)
+    if (f16 && fastb) hipLaunchKernelGGL((sat ? conv_wgrad_f16_kernel<true, true> : conv_wgrad_f16_kernel<true, false>), g, dim3(256), 0, st, p);
+    else if (f16) hipLaunchKernelGGL((sat ? conv_wgrad_f16_kernel<false, true> : conv_wgrad_f16_kernel<false, false>), g, dim3(256), 0, st, p);
+    else if (va && fastb) launch_wgrad<4, 4, true>(p, q.bm, q.bn, bk, g, st);
+    else if (va && vb) launch_wgrad<4, 4, false>(p, q.bm, q.bn, bk, g, st);
+    else if (va) launch_wgrad<4, 1, false>(p, q.bm, q.bn, bk, g, st);
+    else if (vb) launch_wgrad<1, 4, false>(p, q.bm, q.bn, bk, g, st);
+    else launch_wgrad<1, 1, false>(p, q.bm, q.bn, bk, g, st);
+}
+
 static int wgrad_impl(const float* dy, const float* x, float* slabs, float* bias_slabs, int n_slabs, const gim_conv_shape* s,
                       void* stream, bool prezeroed, bool rows = false) {
     WgP p;
@@ -2630,22 +2653,8 @@ static int wgrad_impl(const float* dy, const float* x, float* slabs, float* bias
         else hipLaunchKernelGGL((wgrad_1x1_narrow_kernel<8, false>), g, b, 0, st, wd, nr, slabs, bias_slabs, q.M, Cw, Cn, s->pre_slope, wide_is_dy);
         break;
     }
-    default: {
-        // What depends on the real pointers stays here (the plan assumes aligned operands): vector width per operand as the kernel
-        // sees it (the sub-pixel form swaps the roles: A = p.dy with p.Cout channels, B = p.x with p.Cin), K step, fast B path.
-        const bool va = (p.Cout % 4 == 0) && !((uintptr_t)p.dy & 15);
-        const bool vb = (p.Cin % 4 == 0) && !((uintptr_t)p.x & 15);
-        const int bk = (q.bk == 32 && va && vb) ? 32 : BK;
-        const bool fastb = vb && p.g.ups == 0 && ((p.g.H * p.g.W) & (bk - 1)) == 0;   // a K step stays inside one image
-        const bool f16 = q.family == WG_MFMA_F16 && va && vb && bk == 32, sat = s->prec != 2;   // (prec 2: IEEE conversion, conv_f16.inc)
-        if (f16 && fastb) hipLaunchKernelGGL((sat ? conv_wgrad_f16_kernel<true, true> : conv_wgrad_f16_kernel<true, false>), g, dim3(256), 0, st, p);
-        else if (f16) hipLaunchKernelGGL((sat ? conv_wgrad_f16_kernel<false, true> : conv_wgrad_f16_kernel<false, false>), g, dim3(256), 0, st, p);
-        else if (va && fastb) launch_wgrad<4, 4, true>(p, q.bm, q.bn, bk, g, st);
-        else if (va && vb) launch_wgrad<4, 4, false>(p, q.bm, q.bn, bk, g, st);
-        else if (va) launch_wgrad<4, 1, false>(p, q.bm, q.bn, bk, g, st);
-        else if (vb) launch_wgrad<1, 4, false>(p, q.bm, q.bn, bk, g, st);
-        else launch_wgrad<1, 1, false>(p, q.bm, q.bn, bk, g, st);
-    }
+    default:
+        launch_wgrad_mfma(p, q, s->prec, st);
     }
     return gim_check_launch("gim_conv2d_wgrad");
 }
@@ -2731,4 +2740,234 @@ extern "C" int gim_conv_launch_plan(const gim_conv_shape* s, int kind, int32_t* 
     GIM_CHECK_ARG(s && out && kind >= 0 && kind <= 3, "conv_launch_plan: bad args");
     for (int i = 0; i < 8; ++i) out[i] = -1;
     return launch_plan(s, kind, out);
+}
+
+// -------------------------------------------------------------------------------------------------
+// Strided convolution for training (baseline_training.py: the stride-2 3x3 and 1x1 convolutions of the IR-SE units): forward, input
+// gradient and weight gradient of y[n,oy,ox,co] = sum w[co][a][b][ci] * x[n][oy*s+a-pad][ox*s+b-pad][ci] (+ bias) over the
+// convolution's OWN K x K taps (K in {1, 3}) - no pool / ups / fold, no sigma, no activation.  Nothing here is a new kernel: the three
+// directions are gather geometries of the existing ones.
+//   forward : gim_conv2d_infer's launch (geo_strided on the EPI = 1 forward kernels) with a null slope.
+//   dgrad   : dx pixel (2u + py, 2v + px) collects the taps a with (py + pad - a) even: oy = u + (py + pad - a) / 2.  The four input-
+//             parity classes have 1 / 2 / 2 / 4 taps (K = 3; K = 1: 1 / 0 / 0 / 0), so each is a launch of its own - a plain geometry
+//             with its own Th x Tw, weight taps (a_max - 2 ta, b_max - 2 tb), output stride 2 - 9 taps per 2 x 2 block of dx in total.
+//             (PC mode has ONE Th / Tw / Ktot per launch; a per-class K extent would have to go into the kernels.)
+//   wgrad   : the stride-2-gather weight gradient (what the pool fold runs over its (K+1)^2 folded taps) over K x K taps.
+// -------------------------------------------------------------------------------------------------
+
+// the shape checks of every entry point below, with the entry point's name in front of the message
+#define STRIDED_CHECK(s, WHAT)                                                                                                      \
+    do {                                                                                                                            \
+        GIM_CHECK_ARG((s) != nullptr, WHAT ": null shape");                                                                         \
+        GIM_CHECK_ARG((s)->N > 0 && (s)->Cin > 0 && (s)->Cout > 0, WHAT ": non-positive dims");                                     \
+        GIM_CHECK_ARG((s)->KH == 1 || (s)->KH == 3, WHAT ": KH must be 1 or 3");                                                    \
+        GIM_CHECK_ARG((s)->stride == 1 || (s)->stride == 2, WHAT ": stride must be 1 or 2");                                        \
+        GIM_CHECK_ARG(ilog2_exact((s)->H) >= 1 && ilog2_exact((s)->W) >= 1, WHAT ": H and W must be powers of two >= 2");           \
+        GIM_CHECK_ARG((long long)(s)->N * (s)->H * (s)->W < (1ll << 31), WHAT ": too many pixels");                                 \
+        GIM_CHECK_ARG(strided_image_max(s) * sizeof(float) <= BUF_MAX_BYTES, WHAT ": one image exceeds 2 GiB (32-bit buffer offsets)"); \
+        GIM_CHECK_ARG((long long)(s)->Cout * (s)->KH * (s)->KH * (s)->Cin < (1ll << 31), WHAT ": weight tensor of 2^31 elements or more"); \
+    } while (0)
+
+// elements per image of x / dx and of y / dy
+static void strided_image_elems(const gim_infer_conv* s, size_t& xi, size_t& yi) {
+    xi = (size_t)s->H * s->W * s->Cin;
+    yi = (size_t)(s->H / s->stride) * (s->W / s->stride) * s->Cout;
+}
+static size_t strided_image_max(const gim_infer_conv* s) {
+    size_t xi, yi;
+    strided_image_elems(s, xi, yi);
+    return xi > yi ? xi : yi;
+}
+
+extern "C" int gim_conv2d_strided_fwd(const float* x, const float* w, const float* bias, float* y, const gim_infer_conv* s, void* stream) {
+    STRIDED_CHECK(s, "conv2d_strided_fwd");
+    GIM_CHECK_ARG(x && w && y, "conv2d_strided_fwd: null pointer");
+    return gim_conv2d_infer(x, w, bias, nullptr, y, s, stream);
+}
+
+// The (up to) four launches of one strided input gradient, filled and planned; taps[cls] == 0: the class has no tap (its pixels are zeros).
+struct StridedDgrad {
+    ConvCall c[4];
+    IgemmPlan q[4];
+    int taps[4];
+};
+
+static int strided_dgrad_fill(StridedDgrad& d, const float* dy, const float* w, float* dx, const gim_infer_conv* s, int deterministic) {
+    const int K = s->KH, pd = (K - 1) / 2, Ho = s->H / 2, Wo = s->W / 2;
+    for (int cls = 0; cls < 4; ++cls) {
+        const int par[2] = {cls >> 1, cls & 1};
+        int th[2], off[2], base[2];
+        for (int d2 = 0; d2 < 2; ++d2) {   // taps a = a0, a0 + 2, ... <= K - 1; ta = 0 is the largest (the smallest gathered row)
+            const int a0 = (par[d2] + pd) & 1;
+            th[d2] = a0 <= K - 1 ? (K - 1 - a0) / 2 + 1 : 0;
+            base[d2] = a0 + 2 * (th[d2] - 1);
+            off[d2] = (par[d2] + pd - base[d2]) / 2;
+        }
+        d.taps[cls] = th[0] * th[1];
+        if (!d.taps[cls]) continue;
+        Geo g{};
+        geo_grid(g, s->N, Ho, Wo);
+        g.Hin = Ho; g.Win = Wo; g.ups = 0;
+        g.s_in = g.s_in_x = 1; g.off_y = off[0]; g.off_x = off[1]; g.Th = th[0]; g.Tw = th[1]; g.KF = g.KFw = K;
+        g.wa_base = base[0]; g.wb_base = base[1]; g.wa_step = g.wb_step = -2;
+        g.os = 2; g.py = par[0]; g.px = par[1];
+        ConvCall& c = d.c[cls];
+        c = ConvCall{};
+        ConvP& p = c.p;
+        // (tune_kind 6: no table rows - the rows of kind 1 were measured on plain and pool-folded geometries)
+        const int rc = convp_begin(p, g, s->Cout, s->Cin, s->Cout, 6, nullptr, "conv2d_strided_dgrad: one image exceeds 2 GiB (32-bit buffer offsets)");
+        if (rc) return rc;
+        p.x = dy; p.w = w; p.y = dx;
+        p.Cin_w = s->Cin;
+        p.pre_slope = 1.f; p.mask_slope = 1.f; p.out_scale = 1.f; p.post_slope = 1.f;
+        p.tune_ks = deterministic ? 1 : 0;   // one K slice: no float atomics
+        c.y_elems = (size_t)s->N * s->H * s->W * s->Cin;
+        const bool gen = (s->Cout % BK) != 0 || ((uintptr_t)dy & 15);
+        const bool bscalar = (s->Cin % 4) != 0 || ((uintptr_t)w & 15);
+        c.bmode = 1; c.gen = (gen ? 1 : 0) | (bscalar ? 2 : 0);
+        d.q[cls] = plan_igemm(p, c.bmode, c.gen);
+    }
+    return GIM_OK;
+}
+
+extern "C" int gim_conv2d_strided_dgrad(const float* dy, const float* w, float* dx, const gim_infer_conv* s, int deterministic, void* stream) {
+    STRIDED_CHECK(s, "conv2d_strided_dgrad");
+    int rc;
+    GIM_CHECK_ARG(dy && w && dx, "conv2d_strided_dgrad: null pointer");
+    if (s->stride == 1) {   // the plain entry
+        gim_conv_shape v{};
+        v.N = s->N; v.H = s->H; v.W = s->W; v.Cin = s->Cin; v.Cout = s->Cout; v.KH = s->KH; v.pre_slope = 1.f;
+        v.tune_ksplit = deterministic ? 1 : 0;
+        return gim_conv2d_dgrad(dy, w, nullptr, nullptr, dx, &v, stream);
+    }
+    size_t xi, yi;
+    strided_image_elems(s, xi, yi);
+    gim_infer_conv a, b;
+    if (split_batch(*s, xi > yi ? xi : yi, a, b)) {
+        rc = gim_conv2d_strided_dgrad(dy, w, dx, &a, deterministic, stream);
+        if (rc) return rc;
+        return gim_conv2d_strided_dgrad(dy + a.N * yi, w, dx + a.N * xi, &b, deterministic, stream);
+    }
+    StridedDgrad d;
+    rc = strided_dgrad_fill(d, dy, w, dx, s, deterministic);
+    if (rc) return rc;
+    // The classes write disjoint pixels of ONE tensor: a class that splits K adds into zeros, a class without taps IS zeros - one
+    // clear of dx in front of the first launch serves both (a launch's own clear would wipe the classes before it).
+    bool clear = false;
+    for (int cls = 0; cls < 4; ++cls) clear = clear || !d.taps[cls] || d.q[cls].ksplit > 1;
+    if (clear) (void)hipMemsetAsync(dx, 0, xi * s->N * sizeof(float), (hipStream_t)stream);
+    for (int cls = 0; cls < 4; ++cls) {
+        if (!d.taps[cls]) continue;
+        d.c[cls].p.y_zeroed = 1;
+        rc = run_planned(d.c[cls], d.q[cls], stream, "gim_conv2d_strided_dgrad");
+        if (rc) return rc;
+    }
+    return GIM_OK;
+}
+
+// wgrad_plan of the strided geometry: the plain slicing on the grid of dy (heuristics only - the table's wgrad rows are keyed by
+// plain / folded shapes - and the MFMA family: the direct and outer-product kernels read x without a gather stride)
+static WgPlan strided_wgrad_plan(const gim_infer_conv* s, int combine) {
+    gim_conv_shape v{};
+    v.N = s->N; v.H = s->H / s->stride; v.W = s->W / s->stride; v.Cin = s->Cin; v.Cout = s->Cout; v.KH = s->KH; v.pre_slope = 1.f;
+    v.tune_tile = -1;
+    return wgrad_plan(&v, false, combine, true);
+}
+
+extern "C" int gim_conv2d_strided_wgrad_workspace(const gim_infer_conv* s, int64_t* bytes) {
+    STRIDED_CHECK(s, "conv2d_strided_wgrad_workspace");
+    int rc;
+    GIM_CHECK_ARG(bytes != nullptr, "conv2d_strided_wgrad_workspace: null pointer");
+    size_t xi, yi;
+    strided_image_elems(s, xi, yi);
+    gim_infer_conv a, b;
+    if (split_batch(*s, xi > yi ? xi : yi, a, b)) {   // the halves run one after the other on the same workspace
+        int64_t ba = 0, bb = 0;
+        rc = gim_conv2d_strided_wgrad_workspace(&a, &ba);
+        if (!rc) rc = gim_conv2d_strided_wgrad_workspace(&b, &bb);
+        *bytes = ba > bb ? ba : bb;
+        return rc;
+    }
+    const WgPlan q = strided_wgrad_plan(s, WG_SLABS);
+    *bytes = (int64_t)q.ns * ((int64_t)q.rows * q.cols + q.rows) * (int64_t)sizeof(float);
+    return GIM_OK;
+}
+
+extern "C" int gim_conv2d_strided_wgrad(const float* dy, const float* x, float* dw, float* dbias, const gim_infer_conv* s, int accumulate,
+                                        float* workspace, void* stream) {
+    STRIDED_CHECK(s, "conv2d_strided_wgrad");
+    int rc;
+    GIM_CHECK_ARG(dy && x && dw, "conv2d_strided_wgrad: null pointer");
+    size_t xi, yi;
+    strided_image_elems(s, xi, yi);
+    gim_infer_conv a, b;
+    if (split_batch(*s, xi > yi ? xi : yi, a, b)) {   // the second half ADDS to the first
+        rc = gim_conv2d_strided_wgrad(dy, x, dw, dbias, &a, accumulate, workspace, stream);
+        if (rc) return rc;
+        return gim_conv2d_strided_wgrad(dy + a.N * yi, x + a.N * xi, dw, dbias, &b, 1, workspace, stream);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const WgPlan q = strided_wgrad_plan(s, workspace ? WG_SLABS : (accumulate ? WG_ACC : WG_ONE_SLAB));
+    const size_t n = (size_t)q.rows * q.cols;
+    WgP p{};
+    p.zero = zero_page();
+    p.pos_inf = __builtin_inff();
+    p.g = geo_strided(s);
+    p.dy = dy; p.x = x; p.Cin = s->Cin; p.Cout = s->Cout; p.pre_slope = 1.f; p.a_slope = 1.f; p.pix = s->Cin;
+    p.M = q.M; p.Kcols = q.cols; p.mper = q.mper; p.ns = q.slices; p.xcd = q.xcd; p.atomic = q.atomic;
+    p.x_bytes = (unsigned)(xi * s->N * sizeof(float));
+    if (workspace) {   // one slab per pixel slice, added in a fixed order
+        p.slabs = workspace;
+        p.bias_slabs = dbias ? workspace + (size_t)q.ns * n : nullptr;
+        launch_wgrad_mfma(p, q, 0, st);
+        rc = gim_check_launch("gim_conv2d_strided_wgrad");
+        if (rc) return rc;
+        return gim_wgrad_finish(p.slabs, p.bias_slabs, q.ns, nullptr, nullptr, nullptr, nullptr, dw, accumulate ? nullptr : dbias, nullptr,
+                                s->Cout, s->Cin, s->KH, 0, accumulate ? dw : nullptr, accumulate ? dbias : nullptr, stream);
+    }
+    if (!accumulate && q.atomic) {
+        (void)hipMemsetAsync(dw, 0, n * sizeof(float), st);
+        if (dbias) (void)hipMemsetAsync(dbias, 0, (size_t)q.rows * sizeof(float), st);
+    }
+    p.slabs = dw; p.bias_slabs = dbias;
+    launch_wgrad_mfma(p, q, 0, st);
+    return gim_check_launch("gim_conv2d_strided_wgrad");
+}
+
+// The launches the three entry points above would make for `s`, nothing is launched (tests): kind 0 forward, 1 dgrad, 2 wgrad (atomic
+// combine).  out[16] = four rows {K extent of the launch (taps * gathered channels; wgrad: columns of dW), tile rows, tile columns,
+// K slices (wgrad: pixel slices)}: one row per launch - the dgrad's four parity classes in order (0,0) (0,1) (1,0) (1,1), a class
+// without taps as {0, 0, 0, 0} - the rest -1.  A batch beyond the buffer range reports its last half; a stride-1 dgrad is
+// gim_conv2d_dgrad's launch (gim_conv_launch_plan).
+extern "C" int gim_conv2d_strided_plan(const gim_infer_conv* s, int kind, int32_t* out) {
+    STRIDED_CHECK(s, "conv2d_strided_plan");
+    int rc;
+    GIM_CHECK_ARG(out && kind >= 0 && kind <= 2 && !(kind == 1 && s->stride == 1), "conv2d_strided_plan: bad args");
+    for (int i = 0; i < 16; ++i) out[i] = -1;
+    float* const fake = reinterpret_cast<float*>(uintptr_t(4096));
+    size_t xi, yi;
+    strided_image_elems(s, xi, yi);
+    gim_infer_conv a, b;
+    if (split_batch(*s, xi > yi ? xi : yi, a, b)) return gim_conv2d_strided_plan(&b, kind, out);
+    if (kind == 0) {
+        ConvCall c{};
+        rc = convp_begin(c.p, geo_strided(s), s->Cin, s->Cout, s->Cin, 0, nullptr, "conv2d_strided_plan: one image exceeds 2 GiB");
+        if (rc) return rc;
+        c.p.x = fake; c.p.w = fake; c.p.epi = 1; c.p.no_split = 1;
+        const IgemmPlan q = plan_igemm(c.p, 0, (s->Cin % BK) != 0 ? 1 : 0);
+        out[0] = c.p.Ktot; out[1] = q.BM; out[2] = q.BN; out[3] = q.ksplit;
+    } else if (kind == 1) {
+        StridedDgrad d;
+        rc = strided_dgrad_fill(d, fake, fake, fake, s, 0);
+        if (rc) return rc;
+        for (int cls = 0; cls < 4; ++cls) {
+            int32_t* o = out + 4 * cls;
+            if (!d.taps[cls]) { o[0] = o[1] = o[2] = o[3] = 0; continue; }
+            o[0] = d.c[cls].p.Ktot; o[1] = d.q[cls].BM; o[2] = d.q[cls].BN; o[3] = d.q[cls].ksplit;
+        }
+    } else {
+        const WgPlan q = strided_wgrad_plan(s, WG_ACC);
+        out[0] = q.cols; out[1] = q.bm; out[2] = q.bn; out[3] = q.slices;
+    }
+    return GIM_OK;
 }

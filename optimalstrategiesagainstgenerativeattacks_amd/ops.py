@@ -2509,6 +2509,122 @@ def prelu(x, slope):
     return PReLUFn.apply(x, slope)
 
 
+def _strided_weight(w, Cin):
+    """(storage view [Cout, KH, KH, Cin], logical) of a conv2d_strided weight.  logical: w is a convolution parameter as ops.conv2d
+    takes it, [Cout, Cin, KH, KH] kept channels-last (weight_phys gives the view); else w is [Cout, KH, KH, Cin] itself, as
+    conv2d_infer takes it.  Where both shapes fit (Cin == KH) the memory order decides: a channels-last parameter is not contiguous."""
+    if w.dim() != 4:
+        raise RuntimeError("conv2d_strided: weight %s is neither [Cout, KH, KH, Cin] nor a [Cout, Cin, KH, KH] parameter" % (tuple(w.shape),))
+    Cout, a, b, c = w.shape
+    as_storage, as_logical = (a == b and c == Cin), (b == c and a == Cin)
+    if as_storage and as_logical:
+        as_logical = not w.is_contiguous() and w.permute(0, 2, 3, 1).is_contiguous()
+        as_storage = not as_logical
+    if as_logical:
+        return weight_phys(w), True
+    if as_storage:
+        return (w if w.is_contiguous() else w.contiguous()), False
+    raise RuntimeError("conv2d_strided: weight %s does not match [Cout, KH, KH, Cin = %d] (or a [Cout, Cin = %d, KH, KH] parameter)"
+                       % (tuple(w.shape), Cin, Cin))
+
+
+def _note_strided(kind, cfg):
+    N, Ho, Wo, Cin, Cout, KH, _ = cfg
+    _FLOPS.setdefault((kind, cfg), [0, 2.0 * N * Ho * Wo * Cin * Cout * KH * KH])[0] += 1
+
+
+class ConvStridedFn(Function):
+    """y = conv(x, w, stride, padding = (KH - 1) / 2) + bias on an NHWC map, KH in {1, 3}: the library's strided training entries
+    (gim_conv2d_strided_fwd / _dgrad / _wgrad).  A stride-2 convolution executes its own FLOPs in all three directions - it is not
+    computed at full resolution and subsampled.  The weight and bias gradients go where ConvFn's go: ADDED into the parameter's
+    existing .grad (FusedAdam's flat bucket; autograd then gets None and runs no AccumulateGrad kernel), returned otherwise; under
+    ops.set_deterministic the forward and the dgrad never split K and the weight gradient's pixel slices are slabs added in a fixed
+    order.  count_flops: ("strided_fwd" / "strided_dgrad" / "strided_wgrad", (N, Ho, Wo, Cin, Cout, KH, stride))."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, stride):
+        lib = _lib.load()
+        x = _req(x, "x")
+        _req_w(w)
+        if _PREC[0]:
+            raise RuntimeError("conv2d_strided runs on the fp32 matrix path only (ops.set_matrix_path('fp32')): the strided launches "
+                               "have no fp16 variant")
+        if x.dim() != 4:
+            raise RuntimeError("conv2d_strided: an NHWC map [N, H, W, Cin] expected, got %s" % (tuple(x.shape),))
+        N, H, W, Cin = x.shape
+        wp, logical = _strided_weight(w, Cin)
+        Cout, KH = wp.shape[0], wp.shape[1]
+        if bias is not None and tuple(_req(bias, "bias").shape) != (Cout,):
+            raise RuntimeError("conv2d_strided: bias must be [Cout]")
+        sh = _lib.GimInferConv(N, H, W, Cin, Cout, KH, stride)
+        y = torch.empty((N, H // max(stride, 1), W // max(stride, 1), Cout), device=x.device, dtype=torch.float32)
+        check(lib.gim_conv2d_strided_fwd(_p(x), _p(wp), _p(bias), _p(y), ctypes.byref(sh), _stream()), "conv2d_strided_fwd")
+        ctx.save_for_backward(x, w, bias)
+        ctx.cfg = (N, H, W, Cin, Cout, KH, stride, logical)
+        if _FLOPS is not None:
+            _note_strided("strided_fwd", (N, H // stride, W // stride, Cin, Cout, KH, stride))
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, w, bias = ctx.saved_tensors
+        N, H, W, Cin, Cout, KH, stride, logical = ctx.cfg
+        dy = _req(dy, "dy")
+        st, dev = _stream(), dy.device
+        sh = _lib.GimInferConv(N, H, W, Cin, Cout, KH, stride)
+        cfg = (N, H // stride, W // stride, Cin, Cout, KH, stride)
+        det = 1 if _DETERMINISTIC[0] else 0
+        need = ctx.needs_input_grad
+        dx = dw = db = None
+        if need[0]:
+            wp = _strided_weight(w, Cin)[0]
+            dx = torch.empty((N, H, W, Cin), device=dev, dtype=torch.float32)
+            check(lib.gim_conv2d_strided_dgrad(_p(dy), _p(wp), _p(dx), ctypes.byref(sh), det, st), "conv2d_strided_dgrad")
+            if _FLOPS is not None:
+                _note_strided("strided_dgrad", cfg)
+        want_b = bias is not None and need[2]
+        if need[1]:
+            # the parameter's .grad in the weight's own memory order (a [Cout, KH, KH, Cin] weight: the gradient tensor as it stands)
+            if logical:
+                acc_w = _grad_target(w)
+            else:
+                gw = w.grad
+                acc_w = gw if (gw is not None and gw.is_cuda and gw.dtype == torch.float32 and gw.shape == w.shape and gw.is_contiguous()) else None
+            acc_b = _grad_target(bias) if (want_b and acc_w is not None) else None
+            if want_b and acc_b is None:
+                acc_w = None      # one launch, one combine: both gradients are returned
+            ws = None
+            if det or _WGRAD_SLABS:
+                nbytes = ctypes.c_int64(0)
+                check(lib.gim_conv2d_strided_wgrad_workspace(ctypes.byref(sh), ctypes.byref(nbytes)), "conv2d_strided_wgrad_workspace")
+                ws = torch.empty(max(nbytes.value // 4, 1), device=dev, dtype=torch.float32)
+            if acc_w is not None:
+                check(lib.gim_conv2d_strided_wgrad(_p(dy), _p(x), _p(acc_w), _p(acc_b), ctypes.byref(sh), 1, _p(ws), st), "conv2d_strided_wgrad")
+            else:
+                dwp = torch.empty((Cout, KH, KH, Cin), device=dev, dtype=torch.float32)
+                if want_b:
+                    db = torch.empty(Cout, device=dev, dtype=torch.float32)
+                check(lib.gim_conv2d_strided_wgrad(_p(dy), _p(x), _p(dwp), _p(db), ctypes.byref(sh), 0, _p(ws), st), "conv2d_strided_wgrad")
+                dw = dwp.permute(0, 3, 1, 2) if logical else dwp
+            if _FLOPS is not None:
+                _note_strided("strided_wgrad", cfg)
+        elif want_b:
+            db = torch.empty(Cout, device=dev, dtype=torch.float32)
+            scratch = torch.empty(256 * Cout, device=dev, dtype=torch.float32)
+            check(lib.gim_colsum(_p(dy), _p(db), _p(scratch), N * (H // stride) * (W // stride), Cout, st), "colsum")
+        return dx, dw, db, None
+
+
+def conv2d_strided(x, w, bias=None, stride=2):
+    """y = conv(x, w, stride, padding = (KH - 1) / 2) + bias, differentiable in x, w and bias (ConvStridedFn).  x NHWC [N, H, W, Cin]
+    (H, W powers of two >= 2); w [Cout, KH, KH, Cin] (the library's storage order) or a convolution parameter as ops.conv2d takes it
+    ([Cout, Cin, KH, KH] kept channels-last - the form whose .grad lives in FusedAdam's bucket); KH in {1, 3}; stride in {1, 2}.
+    Returns [N, H / stride, W / stride, Cout]."""
+    return ConvStridedFn.apply(x, w, bias, stride)
+
+
 class Subsample2Fn(Function):
     """y[n, i, j] = x[n, 2 i, 2 j] of an NHWC map with even H and W (MaxPool2d(1, 2); what a stride-2 convolution keeps of the
     stride-1 one).  The backward scatters into zeros in one pass."""
