@@ -1968,28 +1968,54 @@ static int plan_and_run(ConvCall& c, void* stream, const char* what) {
 
 // What every forward-style entry point fills the same way: geometry, GEMM sizes, zero page, the buffer range of the gathered tensor
 // (Ca channels per tap, pix floats between its pixels) and the launch-table kind; with `tune`, the caller's launch overrides.
-static int convp_begin(ConvP& p, const Geo& g, int Ca, int Cb, int pix, int tune_kind, const gim_conv_shape* tune, const char* too_big) {
+// Everything else starts neutral - null pointers, bmode 0, no slope / scale / residual - so an entry writes only what differs.
+static int convp_begin(ConvCall& c, const Geo& g, int Ca, int Cb, int pix, int tune_kind, const gim_conv_shape* tune, const char* too_big) {
+    c = ConvCall{};
+    ConvP& p = c.p;
     p.zero = zero_page();
     p.pos_inf = __builtin_inff();
     p.g = g;
     p.Ca = Ca; p.Cb = Cb; p.pix = pix;
     p.M = g.N * g.H * g.W; p.Ktot = g.Th * g.Tw * Ca;
+    p.pre_slope = p.mask_slope = p.out_scale = p.post_slope = 1.f;
     const unsigned long long xb = (unsigned long long)g.N * g.Hin * g.Win * pix * 4ull;
-    GIM_CHECK_ARG(xb <= 0x7FFFFFF0ull, too_big);
+    GIM_CHECK_ARG(xb <= BUF_MAX_BYTES, too_big);
     p.x_bytes = (unsigned)xb;
     p.tune_kind = tune_kind;
     if (tune) { p.tune_tile = tune->tune_tile; p.tune_ks = tune->tune_ksplit; p.y_zeroed = tune->out_zeroed; }
     return GIM_OK;
 }
 
-// Operands beyond the 32-bit buffer-offset range: the batch is halved (images are independent; per_image = floats of the larger
-// operand per image).  True: the caller runs `a`, then `b` on pointers advanced by a.N images.
-template <class Shape>
-static bool split_batch(const Shape& s, size_t per_image, Shape& a, Shape& b) {
-    if (s.N <= 1 || per_image * s.N * sizeof(float) <= BUF_MAX_BYTES) return false;
-    a = s; b = s;
+// forward-style launches: generic K (channels of the gathered tensor not a multiple of 16, or an unaligned operand)
+static int gen_fwd(int Ca, const float* x, const float* w) { return ((Ca % BK) != 0 || ((uintptr_t)x & 15) || ((uintptr_t)w & 15)) ? 1 : 0; }
+// k-major weights (BMODE 1): bit 0 generic K over dy, bit 1 scalar loads of the weight tile
+static int gen_dgrad(int Cout, int Cin, const float* dy, const float* w) {
+    return (((Cout % BK) != 0 || ((uintptr_t)dy & 15)) ? 1 : 0) | (((Cin % 4) != 0 || ((uintptr_t)w & 15)) ? 2 : 0);
+}
+// the output of one launch lies within the buffer range too
+static int set_y_elems(ConvCall& c, size_t elems, const char* too_big) {
+    GIM_CHECK_ARG(elems * sizeof(float) <= BUF_MAX_BYTES, too_big);
+    c.y_elems = elems;
+    return GIM_OK;
+}
+static int set_post_slope(ConvP& p, float post_slope) {
+    GIM_CHECK_ARG(post_slope >= 0.f && post_slope <= 1.f, "conv fwd: post_slope must be in [0, 1] (0 or 1 = none)");
+    p.post_slope = (post_slope > 0.f) ? post_slope : 1.f;
+    return GIM_OK;
+}
+
+// Operands beyond the 32-bit buffer-offset range: the batch is halved until a part fits (images are independent; xi / yi = floats
+// per image of the input-side and of the output-side operand).  run(part, n0, later) is called on every part in image order: n0 = its
+// first image, from which the entry advances its own pointers; later = images came before it.  What a halved call does differently
+// rides on these two: a weight gradient ADDS its later parts to the first, a workspace query keeps the maximum over the parts, a plan
+// query lets every part overwrite the row, so the last one is reported.
+template <class Shape, class Run>
+static int over_batch_halves(const Shape& s, size_t xi, size_t yi, Run&& run, size_t n0 = 0) {
+    if (s.N <= 1 || (xi > yi ? xi : yi) * s.N * sizeof(float) <= BUF_MAX_BYTES) return run(s, n0, n0 != 0);
+    Shape a = s, b = s;
     a.N = s.N / 2; b.N = s.N - a.N;
-    return true;
+    const int rc = over_batch_halves(a, xi, yi, run, n0);
+    return rc ? rc : over_batch_halves(b, xi, yi, run, n0 + a.N);
 }
 
 // 3 -> 3 / 1 -> 1 image layers: direct convolution (conv_tiny.hip) unless the caller chose a launch (tune_* / deterministic mode)
@@ -2005,28 +2031,25 @@ static void image_elems(const gim_conv_shape* s, bool dx_side, size_t& xi, size_
 
 static int fwd_call(ConvCall& c, const float* x, const float* w, const float* bias, const float* sigma, const float* residual, float* y,
                     const gim_conv_shape* s) {
-    c = ConvCall{};
-    ConvP& p = c.p;
     const bool up_fold = s->ups && s->wfold;
-    int rc = convp_begin(p, s->pool ? geo_s2(s, false) : (up_fold ? geo_pc(s, 0) : geo_plain(s, false)), s->Cin, s->Cout, s->Cin, 0, s,
+    int rc = convp_begin(c, s->pool ? geo_s2(s, false) : (up_fold ? geo_pc(s, 0) : geo_plain(s, false)), s->Cin, s->Cout, s->Cin, 0, s,
                          "conv: one image of the gathered tensor exceeds 2 GiB (32-bit buffer offsets)");
     if (rc) return rc;
-    p.x = x; p.w = w; p.bias = bias; p.sigma = sigma; p.res = residual; p.mask_x = nullptr; p.y = y;
+    ConvP& p = c.p;
+    p.x = x; p.w = w; p.bias = bias; p.sigma = sigma; p.res = residual; p.y = y;
     p.Cin_w = s->Cin;
-    p.pre_slope = s->pre_slope; p.mask_slope = 1.f; p.out_scale = s->pool ? 0.25f : 1.f; p.res_ups = s->res_ups;
-    GIM_CHECK_ARG(s->post_slope >= 0.f && s->post_slope <= 1.f, "conv fwd: post_slope must be in [0, 1] (0 or 1 = none)");
-    p.post_slope = (s->post_slope > 0.f) ? s->post_slope : 1.f;
+    p.pre_slope = s->pre_slope; p.out_scale = s->pool ? 0.25f : 1.f; p.res_ups = s->res_ups;
+    rc = set_post_slope(p, s->post_slope);
+    if (rc) return rc;
     p.f16 = s->prec;
-    c.y_elems = (size_t)s->N * (s->H >> s->pool) * (s->W >> s->pool) * s->Cout;
-    GIM_CHECK_ARG(c.y_elems * sizeof(float) <= 0x7FFFFFF0ull, "conv: one image of the output exceeds 2 GiB (32-bit buffer offsets)");
-    c.bmode = 0;
-    c.gen = ((s->Cin % BK) != 0 || ((uintptr_t)x & 15) || ((uintptr_t)w & 15)) ? 1 : 0;
-    return GIM_OK;
+    c.gen = gen_fwd(s->Cin, x, w);
+    return set_y_elems(c, (size_t)s->N * (s->H >> s->pool) * (s->W >> s->pool) * s->Cout,
+                       "conv: one image of the output exceeds 2 GiB (32-bit buffer offsets)");
 }
 
 extern "C" int gim_conv2d_fwd(const float* x, const float* w, const float* bias, const float* sigma, const float* residual,
                               float* y, const gim_conv_shape* s, void* stream) {
-    int rc = check_shape(s);
+    const int rc = check_shape(s);
     if (rc) return rc;
     GIM_CHECK_ARG(x && w && y, "conv fwd: null pointer");
     if (tiny_route(s)) {
@@ -2035,16 +2058,12 @@ extern "C" int gim_conv2d_fwd(const float* x, const float* w, const float* bias,
     }
     size_t xi, yi;
     image_elems(s, false, xi, yi);
-    gim_conv_shape a, b;
-    if (split_batch(*s, xi > yi ? xi : yi, a, b)) {
-        const size_t ri = s->res_ups ? yi / 4 : yi;
-        rc = gim_conv2d_fwd(x, w, bias, sigma, residual, y, &a, stream);
-        if (rc) return rc;
-        return gim_conv2d_fwd(x + a.N * xi, w, bias, sigma, residual ? residual + a.N * ri : nullptr, y + a.N * yi, &b, stream);
-    }
-    ConvCall c;
-    rc = fwd_call(c, x, w, bias, sigma, residual, y, s);
-    return rc ? rc : plan_and_run(c, stream, "gim_conv2d_fwd");
+    const size_t ri = s->res_ups ? yi / 4 : yi;
+    return over_batch_halves(*s, xi, yi, [&](const gim_conv_shape& h, size_t n0, bool) {
+        ConvCall c;
+        const int rc = fwd_call(c, x + n0 * xi, w, bias, sigma, residual ? residual + n0 * ri : nullptr, y + n0 * yi, &h);
+        return rc ? rc : plan_and_run(c, stream, "gim_conv2d_fwd");
+    });
 }
 
 // Forward-only strided convolution with a per-channel epilogue (inference of the baseline authenticators, baselines.py): the plain
@@ -2062,73 +2081,94 @@ static Geo geo_strided(const gim_infer_conv* s) {
     return g;
 }
 
-extern "C" int gim_conv2d_infer(const float* x, const float* w, const float* bias, const float* slope, float* y,
-                                const gim_infer_conv* s, void* stream) {
-    GIM_CHECK_ARG(s != nullptr, "conv infer: null shape");
-    GIM_CHECK_ARG(x && w && y, "conv infer: null pointer");
-    GIM_CHECK_ARG(s->N > 0 && s->Cin > 0 && s->Cout > 0, "conv infer: non-positive dims");
-    GIM_CHECK_ARG(s->KH == 1 || s->KH == 3, "conv infer: KH must be 1 or 3");
-    GIM_CHECK_ARG(s->stride == 1 || s->stride == 2, "conv infer: stride must be 1 or 2");
-    GIM_CHECK_ARG(ilog2_exact(s->H) >= 0 && ilog2_exact(s->W) >= 0, "conv infer: H and W must be powers of two");
-    GIM_CHECK_ARG(s->H >= s->stride && s->W >= s->stride, "conv infer: stride 2 needs H, W >= 2");
-    GIM_CHECK_ARG((long long)s->N * s->H * s->W < (1ll << 31), "conv infer: too many pixels");
-    const int Ho = s->H / s->stride, Wo = s->W / s->stride;
-    const size_t xi = (size_t)s->H * s->W * s->Cin, yi = (size_t)Ho * Wo * s->Cout;   // elements per image
-    GIM_CHECK_ARG((xi > yi ? xi : yi) * sizeof(float) <= BUF_MAX_BYTES, "conv infer: one image exceeds 2 GiB (32-bit buffer offsets)");
-    gim_infer_conv a, b;
-    if (split_batch(*s, xi > yi ? xi : yi, a, b)) {
-        const int rc = gim_conv2d_infer(x, w, bias, slope, y, &a, stream);
-        if (rc) return rc;
-        return gim_conv2d_infer(x + a.N * xi, w, bias, slope, y + a.N * yi, &b, stream);
-    }
-    ConvCall c{};
-    ConvP& p = c.p;
-    const int rc = convp_begin(p, geo_strided(s), s->Cin, s->Cout, s->Cin, 0, nullptr, "conv infer: one image exceeds 2 GiB (32-bit buffer offsets)");
+// elements per image of x / dx and of y / dy
+static void strided_image_elems(const gim_infer_conv* s, size_t& xi, size_t& yi) {
+    xi = (size_t)s->H * s->W * s->Cin;
+    yi = (size_t)(s->H / s->stride) * (s->W / s->stride) * s->Cout;
+}
+
+// The shape checks of every entry point that takes a gim_infer_conv, with the entry point's name in front of the message.  training
+// (the gim_conv2d_strided_* entries): maps of at least 2 x 2 whatever the stride, and a weight tensor below 2^31 elements.
+static int check_infer_conv(const gim_infer_conv* s, const char* what, bool training) {
+    size_t xi = 0, yi = 0;
+    if (s && (s->stride == 1 || s->stride == 2)) strided_image_elems(s, xi, yi);
+    const char* msg = nullptr;
+    if (!s) msg = "null shape";
+    else if (!(s->N > 0 && s->Cin > 0 && s->Cout > 0)) msg = "non-positive dims";
+    else if (!(s->KH == 1 || s->KH == 3)) msg = "KH must be 1 or 3";
+    else if (!(s->stride == 1 || s->stride == 2)) msg = "stride must be 1 or 2";
+    else if (training && !(ilog2_exact(s->H) >= 1 && ilog2_exact(s->W) >= 1)) msg = "H and W must be powers of two >= 2";
+    else if (!training && !(ilog2_exact(s->H) >= 0 && ilog2_exact(s->W) >= 0)) msg = "H and W must be powers of two";
+    else if (!training && !(s->H >= s->stride && s->W >= s->stride)) msg = "stride 2 needs H, W >= 2";
+    else if (!((long long)s->N * s->H * s->W < (1ll << 31))) msg = "too many pixels";
+    else if (!((xi > yi ? xi : yi) * sizeof(float) <= BUF_MAX_BYTES)) msg = "one image exceeds 2 GiB (32-bit buffer offsets)";
+    else if (training && !((long long)s->Cout * s->KH * s->KH * s->Cin < (1ll << 31))) msg = "weight tensor of 2^31 elements or more";
+    if (!msg) return GIM_OK;
+    char buf[160];
+    snprintf(buf, sizeof(buf), "%s: %s", what, msg);
+    gim_set_error(buf);
+    return GIM_E_BADARG;
+}
+
+// gim_conv2d_infer's fill (its plan query: gim_conv2d_strided_plan kind 0, on stand-in pointers)
+static int infer_call(ConvCall& c, const float* x, const float* w, const float* bias, const float* slope, float* y, const gim_infer_conv* s) {
+    const int rc = convp_begin(c, geo_strided(s), s->Cin, s->Cout, s->Cin, 0, nullptr, "conv infer: one image exceeds 2 GiB (32-bit buffer offsets)");
     if (rc) return rc;
+    ConvP& p = c.p;
     p.x = x; p.w = w; p.bias = bias; p.slope = slope; p.y = y;
     p.Cin_w = s->Cin;
-    p.pre_slope = 1.f; p.mask_slope = 1.f; p.out_scale = 1.f; p.post_slope = 1.f;
     p.epi = 1; p.no_split = 1;
-    c.y_elems = yi * s->N;
-    c.gen = ((s->Cin % BK) != 0 || ((uintptr_t)x & 15) || ((uintptr_t)w & 15)) ? 1 : 0;
-    return plan_and_run(c, stream, "gim_conv2d_infer");
+    c.y_elems = (size_t)s->N * (s->H / s->stride) * (s->W / s->stride) * s->Cout;
+    c.gen = gen_fwd(s->Cin, x, w);
+    return GIM_OK;
+}
+
+extern "C" int gim_conv2d_infer(const float* x, const float* w, const float* bias, const float* slope, float* y,
+                                const gim_infer_conv* s, void* stream) {
+    if (s) GIM_CHECK_ARG(x && w && y, "conv infer: null pointer");   // (reported before a bad shape, after a null one)
+    const int rc = check_infer_conv(s, "conv infer", false);
+    if (rc) return rc;
+    size_t xi, yi;
+    strided_image_elems(s, xi, yi);
+    return over_batch_halves(*s, xi, yi, [&](const gim_infer_conv& h, size_t n0, bool) {
+        ConvCall c;
+        const int rc = infer_call(c, x + n0 * xi, w, bias, slope, y + n0 * yi, &h);
+        return rc ? rc : plan_and_run(c, stream, "gim_conv2d_infer");
+    });
 }
 
 // dx from dy.  pool: dx [N,H,W,Cin] from dy [N,H/2,W/2,Cout] by input-parity classes; sub-pixel (ups+wfold): dx [N,H/2,W/2,Cin]
 // directly from dy [N,H,W,Cout] by a stride-2 gather; plain: dx at the conv's resolution
 static int dgrad_call(ConvCall& c, const float* dy, const float* w, const float* sigma, const float* mask_x, float* dx,
                       const gim_conv_shape* s, bool transposed, const float* res_half, float res_scale) {
-    c = ConvCall{};
-    ConvP& p = c.p;
     const bool up_fold = s->ups && s->wfold;
     GIM_CHECK_ARG(!(mask_x && s->ups && !up_fold), "conv dgrad: mask_x with ups == 1 needs folded weights");
-    int rc = convp_begin(p, s->pool ? geo_pc(s, 1) : (up_fold ? geo_s2(s, true) : geo_plain(s, true)), s->Cout, s->Cin, s->Cout, 1, s,
+    int rc = convp_begin(c, s->pool ? geo_pc(s, 1) : (up_fold ? geo_s2(s, true) : geo_plain(s, true)), s->Cout, s->Cin, s->Cout, 1, s,
                          "conv: one image of the gathered tensor exceeds 2 GiB (32-bit buffer offsets)");
     if (rc) return rc;
-    p.x = dy; p.w = w; p.bias = nullptr; p.sigma = sigma; p.res = res_half; p.res_scale = res_scale; p.mask_x = mask_x; p.y = dx;
+    ConvP& p = c.p;
+    p.x = dy; p.w = w; p.sigma = sigma; p.res = res_half; p.res_scale = res_scale; p.mask_x = mask_x; p.y = dx;
     p.Cin_w = s->Cin;
-    p.pre_slope = 1.f; p.mask_slope = s->pre_slope; p.out_scale = s->pool ? 0.25f : 1.f; p.res_ups = 0;
-    p.post_slope = 1.f;
-    c.y_elems = (size_t)s->N * (s->H >> (up_fold ? 1 : 0)) * (s->W >> (up_fold ? 1 : 0)) * s->Cin;
-    GIM_CHECK_ARG(c.y_elems * sizeof(float) <= 0x7FFFFFF0ull, "conv: one image of the output exceeds 2 GiB (32-bit buffer offsets)");
-    const bool gen = (s->Cout % BK) != 0 || ((uintptr_t)dy & 15);
-    const bool bscalar = (s->Cin % 4) != 0 || ((uintptr_t)w & 15);
-    p.f16 = transposed ? s->prec : 0;   // fp16 operands: the k-contiguous (transposed-weights) form only - ops.py routes fp16 dgrads there
+    p.mask_slope = s->pre_slope; p.out_scale = s->pool ? 0.25f : 1.f;
+    rc = set_y_elems(c, (size_t)s->N * (s->H >> (up_fold ? 1 : 0)) * (s->W >> (up_fold ? 1 : 0)) * s->Cin,
+                     "conv: one image of the output exceeds 2 GiB (32-bit buffer offsets)");
+    if (rc) return rc;
+    const int gen = gen_dgrad(s->Cout, s->Cin, dy, w);
     if (transposed) {
         // WT[ci][a][b][co]: the weight rows are k-contiguous (k = (tap, co)), i.e. the forward kernel's operand layout
-        GIM_CHECK_ARG(!gen && !((uintptr_t)w & 15), "conv dgrad (transposed weights): Cout % 16 == 0 and 16-byte aligned operands required");
+        GIM_CHECK_ARG(!(gen & 1) && !((uintptr_t)w & 15), "conv dgrad (transposed weights): Cout % 16 == 0 and 16-byte aligned operands required");
         p.Cin_w = s->Cout;
         p.tune_kind = 4;
-        c.bmode = 0; c.gen = 0;
+        p.f16 = s->prec;   // fp16 operands: the k-contiguous (transposed-weights) form only - ops.py routes fp16 dgrads there
     } else {
-        c.bmode = 1; c.gen = (gen ? 1 : 0) | (bscalar ? 2 : 0);
+        c.bmode = 1; c.gen = gen;
     }
     return GIM_OK;
 }
 
 static int dgrad_impl(const float* dy, const float* w, const float* sigma, const float* mask_x, float* dx,
                       const gim_conv_shape* s, void* stream, bool transposed, const float* res_half = nullptr, float res_scale = 0.f) {
-    int rc = check_shape(s);
+    const int rc = check_shape(s);
     if (rc) return rc;
     GIM_CHECK_ARG(dy && w && dx, "conv dgrad: null pointer");
     if (!transposed && !res_half && tiny_route(s)) {
@@ -2137,16 +2177,12 @@ static int dgrad_impl(const float* dy, const float* w, const float* sigma, const
     }
     size_t xi, yi;
     image_elems(s, true, xi, yi);
-    gim_conv_shape a, b;
-    if (split_batch(*s, xi > yi ? xi : yi, a, b)) {
-        rc = dgrad_impl(dy, w, sigma, mask_x, dx, &a, stream, transposed, res_half, res_scale);
-        if (rc) return rc;
-        return dgrad_impl(dy + a.N * yi, w, sigma, mask_x ? mask_x + a.N * xi : nullptr, dx + a.N * xi, &b, stream, transposed,
-                          res_half ? res_half + a.N * (xi / 4) : nullptr, res_scale);
-    }
-    ConvCall c;
-    rc = dgrad_call(c, dy, w, sigma, mask_x, dx, s, transposed, res_half, res_scale);
-    return rc ? rc : plan_and_run(c, stream, transposed ? "gim_conv2d_dgrad_t" : "gim_conv2d_dgrad");
+    return over_batch_halves(*s, xi, yi, [&](const gim_conv_shape& h, size_t n0, bool) {
+        ConvCall c;
+        const int rc = dgrad_call(c, dy + n0 * yi, w, sigma, mask_x ? mask_x + n0 * xi : nullptr, dx + n0 * xi, &h, transposed,
+                                  res_half ? res_half + n0 * (xi / 4) : nullptr, res_scale);
+        return rc ? rc : plan_and_run(c, stream, transposed ? "gim_conv2d_dgrad_t" : "gim_conv2d_dgrad");
+    });
 }
 
 extern "C" int gim_conv2d_dgrad(const float* dy, const float* w, const float* sigma, const float* mask_x, float* dx,
@@ -2187,29 +2223,25 @@ static Geo geo_xfold(const gim_conv_shape* s, int J) {
 // operand path over dy with stride (1, J), K x (K + J - 1) taps and J * Cin output columns.
 extern "C" int gim_conv2d_dgrad_xfold(const float* dy, const float* wx, const float* sigma, const float* mask_x, float* dx,
                                       const gim_conv_shape* s, int J, void* stream) {
-    int rc = check_shape(s);
+    const int rc = check_shape(s);
     if (rc) return rc;
     GIM_CHECK_ARG(dy && wx && dx, "conv dgrad (x-folded): null pointer");
     GIM_CHECK_ARG(!s->ups && !s->pool && !s->wfold, "conv dgrad (x-folded): plain convolutions only");
     GIM_CHECK_ARG(J >= 2 && (J & (J - 1)) == 0 && s->W % J == 0 && J * s->Cin <= 32, "conv dgrad (x-folded): J must be a power of two dividing W with J * Cin <= 32");
     GIM_CHECK_ARG(s->Cout % BK == 0 && !((uintptr_t)dy & 15) && !((uintptr_t)wx & 15), "conv dgrad (x-folded): Cout % 16 == 0 and 16-byte aligned operands required");
     const size_t yi = (size_t)s->H * s->W * s->Cout, xi = (size_t)s->H * s->W * s->Cin;
-    gim_conv_shape a, b;
-    if (split_batch(*s, xi > yi ? xi : yi, a, b)) {
-        rc = gim_conv2d_dgrad_xfold(dy, wx, sigma, mask_x, dx, &a, J, stream);
+    return over_batch_halves(*s, xi, yi, [&](const gim_conv_shape& h, size_t n0, bool) {
+        ConvCall c;
+        // (tune_kind 5: no table rows - heuristics, or the caller's tune_* fields)
+        const int rc = convp_begin(c, geo_xfold(&h, J), h.Cout, J * h.Cin, h.Cout, 5, &h, "conv: one image of the gathered tensor exceeds 2 GiB (32-bit buffer offsets)");
         if (rc) return rc;
-        return gim_conv2d_dgrad_xfold(dy + a.N * yi, wx, sigma, mask_x ? mask_x + a.N * xi : nullptr, dx + a.N * xi, &b, J, stream);
-    }
-    ConvCall c{};
-    ConvP& p = c.p;
-    // (tune_kind 5: no table rows - heuristics, or the caller's tune_* fields)
-    rc = convp_begin(p, geo_xfold(s, J), s->Cout, J * s->Cin, s->Cout, 5, s, "conv: one image of the gathered tensor exceeds 2 GiB (32-bit buffer offsets)");
-    if (rc) return rc;
-    p.x = dy; p.w = wx; p.bias = nullptr; p.sigma = sigma; p.res = nullptr; p.mask_x = mask_x; p.y = dx;
-    p.Cin_w = s->Cout;
-    p.pre_slope = 1.f; p.mask_slope = s->pre_slope; p.out_scale = 1.f; p.res_ups = 0; p.post_slope = 1.f;
-    c.y_elems = (size_t)s->N * s->H * s->W * s->Cin;
-    return plan_and_run(c, stream, "gim_conv2d_dgrad_xfold");
+        ConvP& p = c.p;
+        p.x = dy + n0 * yi; p.w = wx; p.sigma = sigma; p.mask_x = mask_x ? mask_x + n0 * xi : nullptr; p.y = dx + n0 * xi;
+        p.Cin_w = h.Cout;
+        p.mask_slope = h.pre_slope;
+        c.y_elems = h.N * xi;
+        return plan_and_run(c, stream, "gim_conv2d_dgrad_xfold");
+    });
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -2319,20 +2351,17 @@ extern "C" int gim_conv2d_fwd_rows(const float* xp, const float* wp, const float
     int rc = rows_shape_ok(s);
     if (rc) return rc;
     GIM_CHECK_ARG(xp && wp && y && !((uintptr_t)xp & 15) && !((uintptr_t)wp & 15), "conv fwd (rows form): null or unaligned pointer");
-    ConvCall c{};
-    ConvP& p = c.p;
+    ConvCall c;
     const int CaP = (s->KH * s->Cin + 15) & ~15;
     // (tune_kind 6: no table rows - heuristics, or the caller's tune_* fields)
-    rc = convp_begin(p, geo_rows(s), CaP, s->Cout, s->Cin, 6, s, "conv fwd (rows form): the padded image batch exceeds 2 GiB (32-bit buffer offsets): split the batch");
+    rc = convp_begin(c, geo_rows(s), CaP, s->Cout, s->Cin, 6, s, "conv fwd (rows form): the padded image batch exceeds 2 GiB (32-bit buffer offsets): split the batch");
     if (rc) return rc;
-    p.x = xp; p.w = wp; p.bias = bias; p.sigma = sigma; p.res = residual; p.mask_x = nullptr; p.y = y;
+    ConvP& p = c.p;
+    p.x = xp; p.w = wp; p.bias = bias; p.sigma = sigma; p.res = residual; p.y = y;
     p.Cin_w = CaP;
-    p.pre_slope = 1.f; p.mask_slope = 1.f; p.out_scale = 1.f; p.res_ups = 0;
-    GIM_CHECK_ARG(s->post_slope >= 0.f && s->post_slope <= 1.f, "conv fwd: post_slope must be in [0, 1] (0 or 1 = none)");
-    p.post_slope = (s->post_slope > 0.f) ? s->post_slope : 1.f;
-    c.y_elems = (size_t)s->N * s->H * s->W * s->Cout;
-    GIM_CHECK_ARG(c.y_elems * sizeof(float) <= 0x7FFFFFF0ull, "conv: the output exceeds 2 GiB (32-bit buffer offsets): split the batch");
-    return plan_and_run(c, stream, "gim_conv2d_fwd_rows");
+    rc = set_post_slope(p, s->post_slope);
+    if (!rc) rc = set_y_elems(c, (size_t)s->N * s->H * s->W * s->Cout, "conv: the output exceeds 2 GiB (32-bit buffer offsets): split the batch");
+    return rc ? rc : plan_and_run(c, stream, "gim_conv2d_fwd_rows");
 }
 template <int VA, int VB, bool FASTB>
 static void launch_wgrad(const WgP& p, int bm, int bn, int bk, dim3 g, hipStream_t st) {
@@ -2571,6 +2600,31 @@ extern "C" int gim_conv2d_wgrad_slabs(const gim_conv_shape* s) {
     return wgrad_plan(s, false, WG_SLABS, true).ns;
 }
 
+// The kernel parameters of one planned weight gradient, but for where the result goes (slabs / bias_slabs: the caller's).  a: the
+// operand whose rows are streamed (the kernel's dy), b: the one gathered through g (its x), pix floats between b's pixels.
+struct WgOperand { const float* ptr; int C; float slope; };
+static int wgp_fill(WgP& p, const WgPlan& q, const Geo& g, WgOperand a, WgOperand b, int pix) {
+    p = WgP{};
+    p.zero = zero_page();
+    p.pos_inf = __builtin_inff();
+    p.g = g;
+    p.dy = a.ptr; p.Cout = a.C; p.a_slope = a.slope;
+    p.x = b.ptr; p.Cin = b.C; p.pre_slope = b.slope; p.pix = pix;
+    p.M = q.M; p.Kcols = q.cols; p.mper = q.mper; p.ns = q.slices; p.xcd = q.xcd; p.atomic = q.atomic;
+    const unsigned long long xb = (unsigned long long)g.N * g.Hin * g.Win * pix * 4ull;
+    GIM_CHECK_ARG(xb <= BUF_MAX_BYTES, "conv wgrad: gathered tensor larger than 2 GiB (32-bit buffer offsets): split the batch");
+    p.x_bytes = (unsigned)xb;
+    return GIM_OK;
+}
+
+// Slices that combine by float atomics (and the direct kernel, which always adds into its slot) need zeros to add to: unless the
+// caller vouches for them (prezeroed: zeros, or a partial sum to add to), dW and dbias are cleared in front of the launch.
+static void wgrad_clear(const WgPlan& q, bool prezeroed, float* dw, float* dbias, hipStream_t st) {
+    if (prezeroed || !(q.atomic || q.family == WG_TINY)) return;
+    (void)hipMemsetAsync(dw, 0, (size_t)q.rows * q.cols * sizeof(float), st);
+    if (dbias) (void)hipMemsetAsync(dbias, 0, (size_t)q.rows * sizeof(float), st);
+}
+
 // Validate, plan and fill the kernel parameters of one weight gradient (the first half of wgrad_impl, and of the plan query).
 // prezeroed: the caller guarantees slabs / bias_slabs hold zeros (or a partial sum to add to): pixel slices are combined
 // with float atomics and nothing is cleared (gim_conv2d_wgrad_acc).
@@ -2583,24 +2637,14 @@ static int wgrad_call(WgP& p, WgPlan& q, const float* dy, const float* x, float*
     if (!prezeroed) GIM_CHECK_ARG(n_slabs == 1 || n_slabs == q.ns, "conv wgrad: n_slabs must be 1 (atomic combine) or gim_conv2d_wgrad_slabs(shape)");
     const bool up_fold = s->ups && s->wfold;
     GIM_CHECK_ARG(!(up_fold && bias_slabs), "conv wgrad: the sub-pixel form does not produce the bias gradient (use gim_colsum)");
-    p = WgP{};
-    p.zero = zero_page();
-    p.pos_inf = __builtin_inff();
-    if (rows) p.g = geo_rows(s);
-    else if (s->pool || up_fold) p.g = geo_s2(s, false);
-    else p.g = geo_plain(s, false);
-    if (up_fold) {
-        p.dy = x; p.x = dy; p.Cin = s->Cout; p.Cout = s->Cin; p.pre_slope = 1.f; p.a_slope = s->pre_slope; p.pix = s->Cout;
-    } else {
-        p.dy = dy; p.x = x; p.Cin = s->Cin; p.Cout = s->Cout; p.pre_slope = s->pre_slope; p.a_slope = 1.f; p.pix = s->Cin;
-    }
+    if (rows)   // CaP columns per tap row, Cin floats between pixels; the padded copy is already activated
+        rc = wgp_fill(p, q, geo_rows(s), {dy, s->Cout, 1.f}, {x, (s->KH * s->Cin + 15) & ~15, 1.f}, s->Cin);
+    else if (up_fold)   // the roles swap: x is streamed, dy gathered with stride 2
+        rc = wgp_fill(p, q, geo_s2(s, false), {x, s->Cin, s->pre_slope}, {dy, s->Cout, 1.f}, s->Cout);
+    else
+        rc = wgp_fill(p, q, s->pool ? geo_s2(s, false) : geo_plain(s, false), {dy, s->Cout, 1.f}, {x, s->Cin, s->pre_slope}, s->Cin);
     p.slabs = slabs; p.bias_slabs = bias_slabs;
-    p.M = q.M; p.Kcols = q.cols; p.mper = q.mper; p.ns = q.slices; p.xcd = q.xcd; p.atomic = q.atomic;
-    if (rows) { p.Cin = (s->KH * s->Cin + 15) & ~15; p.pix = s->Cin; p.pre_slope = 1.f; }   // columns per tap row; the padded copy is already activated
-    const unsigned long long xb = (unsigned long long)p.g.N * p.g.Hin * p.g.Win * p.pix * 4ull;
-    GIM_CHECK_ARG(xb <= 0x7FFFFFF0ull, "conv wgrad: gathered tensor larger than 2 GiB (32-bit buffer offsets): split the batch");
-    p.x_bytes = (unsigned)xb;
-    return GIM_OK;
+    return rc;
 }
 
 // The launch of the MFMA families (conv_wgrad_kernel / conv_wgrad_f16_kernel) for a filled WgP and its plan.
@@ -2629,10 +2673,7 @@ static int wgrad_impl(const float* dy, const float* x, float* slabs, float* bias
     const int rc = wgrad_call(p, q, dy, x, slabs, bias_slabs, n_slabs, s, prezeroed, rows);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (!prezeroed && (q.atomic || q.family == WG_TINY)) {   // (the direct kernel always adds into its slot)
-        (void)hipMemsetAsync(slabs, 0, (size_t)q.rows * q.cols * sizeof(float), st);
-        if (bias_slabs) (void)hipMemsetAsync(bias_slabs, 0, (size_t)q.rows * sizeof(float), st);
-    }
+    wgrad_clear(q, prezeroed, slabs, bias_slabs, st);
     const dim3 g(q.gx, q.gy, q.gz);
     switch (q.family) {
     case WG_TINY:
@@ -2665,17 +2706,13 @@ extern "C" int gim_conv2d_wgrad(const float* dy, const float* x, float* slabs, f
 }
 
 extern "C" int gim_conv2d_wgrad_acc(const float* dy, const float* x, float* acc, float* bias_acc, const gim_conv_shape* s, void* stream) {
-    int rc = check_shape(s);
+    const int rc = check_shape(s);
     if (rc) return rc;
     size_t xi, yi;
     image_elems(s, false, xi, yi);
-    gim_conv_shape a, b;
-    if (split_batch(*s, xi > yi ? xi : yi, a, b)) {   // both halves ADD into acc
-        rc = gim_conv2d_wgrad_acc(dy, x, acc, bias_acc, &a, stream);
-        if (rc) return rc;
-        return gim_conv2d_wgrad_acc(dy + a.N * yi, x + a.N * xi, acc, bias_acc, &b, stream);
-    }
-    return wgrad_impl(dy, x, acc, bias_acc, 1, s, stream, true);
+    return over_batch_halves(*s, xi, yi, [&](const gim_conv_shape& h, size_t n0, bool) {   // every part ADDS into acc
+        return wgrad_impl(dy + n0 * yi, x + n0 * xi, acc, bias_acc, 1, &h, stream, true);
+    });
 }
 
 // dW slot [Cout][K][CaP] (+)= dy^T * rows(xp), bias slot += column sums of dy: the weight gradient of the row-contiguous form
@@ -2711,29 +2748,26 @@ static int launch_plan(const gim_conv_shape* s, int kind, int32_t* out) {
     }
     size_t xi, yi;
     image_elems(s, kind == 1 || kind == 2, xi, yi);
-    gim_conv_shape a, b;
-    if (split_batch(*s, xi > yi ? xi : yi, a, b)) {
-        rc = launch_plan(&a, kind, out);
-        return rc ? rc : launch_plan(&b, kind, out);
-    }
-    if (kind == 3) {
-        const int form[] = {0, 2, 3, 1, 0};   // by WgFamily
-        WgP p;
-        WgPlan q;
-        rc = wgrad_call(p, q, fake, fake, fake, nullptr, 1, s, true, false);
-        if (!rc) plan_row(out, q.table_hit, q.bm, q.bn, q.slices, q.gx, q.gy, q.gz, form[q.family]);
-        return rc;
-    }
-    const int form[] = {0, 1, 2, 2};          // by IgemmFamily
-    ConvCall c;
-    rc = kind == 0 ? fwd_call(c, fake, fake, nullptr, nullptr, nullptr, fake, s)
-                   : dgrad_call(c, fake, fake, nullptr, nullptr, fake, s, kind == 2, nullptr, 0.f);
-    if (rc) return rc;
-    const IgemmPlan q = plan_igemm(c.p, c.bmode, c.gen);
-    // bits 8.. of out[7]: the share of the launch's K steps that is SKIPPED, in 1/1000 (position-major rows skip padding taps; else 0)
-    const int skipped = 1000 - pm_valid_permille(c.p.g, c.p.M, q.BM);
-    plan_row(out, q.table_hit, q.BM, q.BN, q.ksplit, q.gx, q.gy, q.gz, form[q.family] | (skipped << 8));
-    return GIM_OK;
+    return over_batch_halves(*s, xi, yi, [&](const gim_conv_shape& h, size_t, bool) {   // every part writes the row: the last one stays
+        if (kind == 3) {
+            const int form[] = {0, 2, 3, 1, 0};   // by WgFamily
+            WgP p;
+            WgPlan q;
+            const int rc = wgrad_call(p, q, fake, fake, fake, nullptr, 1, &h, true, false);
+            if (!rc) plan_row(out, q.table_hit, q.bm, q.bn, q.slices, q.gx, q.gy, q.gz, form[q.family]);
+            return rc;
+        }
+        const int form[] = {0, 1, 2, 2};          // by IgemmFamily
+        ConvCall c;
+        const int rc = kind == 0 ? fwd_call(c, fake, fake, nullptr, nullptr, nullptr, fake, &h)
+                                 : dgrad_call(c, fake, fake, nullptr, nullptr, fake, &h, kind == 2, nullptr, 0.f);
+        if (rc) return rc;
+        const IgemmPlan q = plan_igemm(c.p, c.bmode, c.gen);
+        // bits 8.. of out[7]: the share of the launch's K steps that is SKIPPED, in 1/1000 (position-major rows skip padding taps; else 0)
+        const int skipped = 1000 - pm_valid_permille(c.p.g, c.p.M, q.BM);
+        plan_row(out, q.table_hit, q.BM, q.BN, q.ksplit, q.gx, q.gy, q.gz, form[q.family] | (skipped << 8));
+        return (int)GIM_OK;
+    });
 }
 
 extern "C" int gim_conv_launch_plan(const gim_conv_shape* s, int kind, int32_t* out) {
@@ -2755,32 +2789,9 @@ extern "C" int gim_conv_launch_plan(const gim_conv_shape* s, int kind, int32_t* 
 //   wgrad   : the stride-2-gather weight gradient (what the pool fold runs over its (K+1)^2 folded taps) over K x K taps.
 // -------------------------------------------------------------------------------------------------
 
-// the shape checks of every entry point below, with the entry point's name in front of the message
-#define STRIDED_CHECK(s, WHAT)                                                                                                      \
-    do {                                                                                                                            \
-        GIM_CHECK_ARG((s) != nullptr, WHAT ": null shape");                                                                         \
-        GIM_CHECK_ARG((s)->N > 0 && (s)->Cin > 0 && (s)->Cout > 0, WHAT ": non-positive dims");                                     \
-        GIM_CHECK_ARG((s)->KH == 1 || (s)->KH == 3, WHAT ": KH must be 1 or 3");                                                    \
-        GIM_CHECK_ARG((s)->stride == 1 || (s)->stride == 2, WHAT ": stride must be 1 or 2");                                        \
-        GIM_CHECK_ARG(ilog2_exact((s)->H) >= 1 && ilog2_exact((s)->W) >= 1, WHAT ": H and W must be powers of two >= 2");           \
-        GIM_CHECK_ARG((long long)(s)->N * (s)->H * (s)->W < (1ll << 31), WHAT ": too many pixels");                                 \
-        GIM_CHECK_ARG(strided_image_max(s) * sizeof(float) <= BUF_MAX_BYTES, WHAT ": one image exceeds 2 GiB (32-bit buffer offsets)"); \
-        GIM_CHECK_ARG((long long)(s)->Cout * (s)->KH * (s)->KH * (s)->Cin < (1ll << 31), WHAT ": weight tensor of 2^31 elements or more"); \
-    } while (0)
-
-// elements per image of x / dx and of y / dy
-static void strided_image_elems(const gim_infer_conv* s, size_t& xi, size_t& yi) {
-    xi = (size_t)s->H * s->W * s->Cin;
-    yi = (size_t)(s->H / s->stride) * (s->W / s->stride) * s->Cout;
-}
-static size_t strided_image_max(const gim_infer_conv* s) {
-    size_t xi, yi;
-    strided_image_elems(s, xi, yi);
-    return xi > yi ? xi : yi;
-}
-
 extern "C" int gim_conv2d_strided_fwd(const float* x, const float* w, const float* bias, float* y, const gim_infer_conv* s, void* stream) {
-    STRIDED_CHECK(s, "conv2d_strided_fwd");
+    const int rc = check_infer_conv(s, "conv2d_strided_fwd", true);
+    if (rc) return rc;
     GIM_CHECK_ARG(x && w && y, "conv2d_strided_fwd: null pointer");
     return gim_conv2d_infer(x, w, bias, nullptr, y, s, stream);
 }
@@ -2812,126 +2823,107 @@ static int strided_dgrad_fill(StridedDgrad& d, const float* dy, const float* w, 
         g.wa_base = base[0]; g.wb_base = base[1]; g.wa_step = g.wb_step = -2;
         g.os = 2; g.py = par[0]; g.px = par[1];
         ConvCall& c = d.c[cls];
-        c = ConvCall{};
-        ConvP& p = c.p;
         // (tune_kind 6: no table rows - the rows of kind 1 were measured on plain and pool-folded geometries)
-        const int rc = convp_begin(p, g, s->Cout, s->Cin, s->Cout, 6, nullptr, "conv2d_strided_dgrad: one image exceeds 2 GiB (32-bit buffer offsets)");
+        const int rc = convp_begin(c, g, s->Cout, s->Cin, s->Cout, 6, nullptr, "conv2d_strided_dgrad: one image exceeds 2 GiB (32-bit buffer offsets)");
         if (rc) return rc;
+        ConvP& p = c.p;
         p.x = dy; p.w = w; p.y = dx;
         p.Cin_w = s->Cin;
-        p.pre_slope = 1.f; p.mask_slope = 1.f; p.out_scale = 1.f; p.post_slope = 1.f;
         p.tune_ks = deterministic ? 1 : 0;   // one K slice: no float atomics
         c.y_elems = (size_t)s->N * s->H * s->W * s->Cin;
-        const bool gen = (s->Cout % BK) != 0 || ((uintptr_t)dy & 15);
-        const bool bscalar = (s->Cin % 4) != 0 || ((uintptr_t)w & 15);
-        c.bmode = 1; c.gen = (gen ? 1 : 0) | (bscalar ? 2 : 0);
+        c.bmode = 1; c.gen = gen_dgrad(s->Cout, s->Cin, dy, w);
         d.q[cls] = plan_igemm(p, c.bmode, c.gen);
     }
     return GIM_OK;
 }
 
+// the stride-1 convolution of `s`, or the convolution on the grid of its output, as the plain entries describe it
+static gim_conv_shape plain_shape_of(const gim_infer_conv* s) {
+    gim_conv_shape v{};
+    v.N = s->N; v.H = s->H / s->stride; v.W = s->W / s->stride; v.Cin = s->Cin; v.Cout = s->Cout; v.KH = s->KH; v.pre_slope = 1.f;
+    return v;
+}
+
 extern "C" int gim_conv2d_strided_dgrad(const float* dy, const float* w, float* dx, const gim_infer_conv* s, int deterministic, void* stream) {
-    STRIDED_CHECK(s, "conv2d_strided_dgrad");
-    int rc;
+    const int rc = check_infer_conv(s, "conv2d_strided_dgrad", true);
+    if (rc) return rc;
     GIM_CHECK_ARG(dy && w && dx, "conv2d_strided_dgrad: null pointer");
     if (s->stride == 1) {   // the plain entry
-        gim_conv_shape v{};
-        v.N = s->N; v.H = s->H; v.W = s->W; v.Cin = s->Cin; v.Cout = s->Cout; v.KH = s->KH; v.pre_slope = 1.f;
+        gim_conv_shape v = plain_shape_of(s);
         v.tune_ksplit = deterministic ? 1 : 0;
         return gim_conv2d_dgrad(dy, w, nullptr, nullptr, dx, &v, stream);
     }
     size_t xi, yi;
     strided_image_elems(s, xi, yi);
-    gim_infer_conv a, b;
-    if (split_batch(*s, xi > yi ? xi : yi, a, b)) {
-        rc = gim_conv2d_strided_dgrad(dy, w, dx, &a, deterministic, stream);
+    return over_batch_halves(*s, xi, yi, [&](const gim_infer_conv& h, size_t n0, bool) {
+        float* const dxh = dx + n0 * xi;
+        StridedDgrad d;
+        int rc = strided_dgrad_fill(d, dy + n0 * yi, w, dxh, &h, deterministic);
         if (rc) return rc;
-        return gim_conv2d_strided_dgrad(dy + a.N * yi, w, dx + a.N * xi, &b, deterministic, stream);
-    }
-    StridedDgrad d;
-    rc = strided_dgrad_fill(d, dy, w, dx, s, deterministic);
-    if (rc) return rc;
-    // The classes write disjoint pixels of ONE tensor: a class that splits K adds into zeros, a class without taps IS zeros - one
-    // clear of dx in front of the first launch serves both (a launch's own clear would wipe the classes before it).
-    bool clear = false;
-    for (int cls = 0; cls < 4; ++cls) clear = clear || !d.taps[cls] || d.q[cls].ksplit > 1;
-    if (clear) (void)hipMemsetAsync(dx, 0, xi * s->N * sizeof(float), (hipStream_t)stream);
-    for (int cls = 0; cls < 4; ++cls) {
-        if (!d.taps[cls]) continue;
-        d.c[cls].p.y_zeroed = 1;
-        rc = run_planned(d.c[cls], d.q[cls], stream, "gim_conv2d_strided_dgrad");
-        if (rc) return rc;
-    }
-    return GIM_OK;
+        // The classes write disjoint pixels of ONE tensor: a class that splits K adds into zeros, a class without taps IS zeros - one
+        // clear of dx in front of the first launch serves both (a launch's own clear would wipe the classes before it).
+        bool clear = false;
+        for (int cls = 0; cls < 4; ++cls) clear = clear || !d.taps[cls] || d.q[cls].ksplit > 1;
+        if (clear) (void)hipMemsetAsync(dxh, 0, xi * h.N * sizeof(float), (hipStream_t)stream);
+        for (int cls = 0; cls < 4 && !rc; ++cls) {
+            if (!d.taps[cls]) continue;
+            d.c[cls].p.y_zeroed = 1;
+            rc = run_planned(d.c[cls], d.q[cls], stream, "gim_conv2d_strided_dgrad");
+        }
+        return rc;
+    });
 }
 
 // wgrad_plan of the strided geometry: the plain slicing on the grid of dy (heuristics only - the table's wgrad rows are keyed by
 // plain / folded shapes - and the MFMA family: the direct and outer-product kernels read x without a gather stride)
 static WgPlan strided_wgrad_plan(const gim_infer_conv* s, int combine) {
-    gim_conv_shape v{};
-    v.N = s->N; v.H = s->H / s->stride; v.W = s->W / s->stride; v.Cin = s->Cin; v.Cout = s->Cout; v.KH = s->KH; v.pre_slope = 1.f;
+    gim_conv_shape v = plain_shape_of(s);
     v.tune_tile = -1;
     return wgrad_plan(&v, false, combine, true);
 }
 
 extern "C" int gim_conv2d_strided_wgrad_workspace(const gim_infer_conv* s, int64_t* bytes) {
-    STRIDED_CHECK(s, "conv2d_strided_wgrad_workspace");
-    int rc;
+    const int rc = check_infer_conv(s, "conv2d_strided_wgrad_workspace", true);
+    if (rc) return rc;
     GIM_CHECK_ARG(bytes != nullptr, "conv2d_strided_wgrad_workspace: null pointer");
     size_t xi, yi;
     strided_image_elems(s, xi, yi);
-    gim_infer_conv a, b;
-    if (split_batch(*s, xi > yi ? xi : yi, a, b)) {   // the halves run one after the other on the same workspace
-        int64_t ba = 0, bb = 0;
-        rc = gim_conv2d_strided_wgrad_workspace(&a, &ba);
-        if (!rc) rc = gim_conv2d_strided_wgrad_workspace(&b, &bb);
-        *bytes = ba > bb ? ba : bb;
-        return rc;
-    }
-    const WgPlan q = strided_wgrad_plan(s, WG_SLABS);
-    *bytes = (int64_t)q.ns * ((int64_t)q.rows * q.cols + q.rows) * (int64_t)sizeof(float);
-    return GIM_OK;
+    *bytes = 0;
+    return over_batch_halves(*s, xi, yi, [&](const gim_infer_conv& h, size_t, bool) {   // the parts run one after the other on the same workspace
+        const WgPlan q = strided_wgrad_plan(&h, WG_SLABS);
+        const int64_t b = (int64_t)q.ns * ((int64_t)q.rows * q.cols + q.rows) * (int64_t)sizeof(float);
+        if (b > *bytes) *bytes = b;
+        return (int)GIM_OK;
+    });
 }
 
 extern "C" int gim_conv2d_strided_wgrad(const float* dy, const float* x, float* dw, float* dbias, const gim_infer_conv* s, int accumulate,
                                         float* workspace, void* stream) {
-    STRIDED_CHECK(s, "conv2d_strided_wgrad");
-    int rc;
+    const int rc = check_infer_conv(s, "conv2d_strided_wgrad", true);
+    if (rc) return rc;
     GIM_CHECK_ARG(dy && x && dw, "conv2d_strided_wgrad: null pointer");
     size_t xi, yi;
     strided_image_elems(s, xi, yi);
-    gim_infer_conv a, b;
-    if (split_batch(*s, xi > yi ? xi : yi, a, b)) {   // the second half ADDS to the first
-        rc = gim_conv2d_strided_wgrad(dy, x, dw, dbias, &a, accumulate, workspace, stream);
+    return over_batch_halves(*s, xi, yi, [&](const gim_infer_conv& h, size_t n0, bool later) {
+        const bool acc = accumulate || later;   // a later part ADDS to the first
+        hipStream_t st = (hipStream_t)stream;
+        const WgPlan q = strided_wgrad_plan(&h, workspace ? WG_SLABS : (acc ? WG_ACC : WG_ONE_SLAB));
+        WgP p;
+        int rc = wgp_fill(p, q, geo_strided(&h), {dy + n0 * yi, h.Cout, 1.f}, {x + n0 * xi, h.Cin, 1.f}, h.Cin);
         if (rc) return rc;
-        return gim_conv2d_strided_wgrad(dy + a.N * yi, x + a.N * xi, dw, dbias, &b, 1, workspace, stream);
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const WgPlan q = strided_wgrad_plan(s, workspace ? WG_SLABS : (accumulate ? WG_ACC : WG_ONE_SLAB));
-    const size_t n = (size_t)q.rows * q.cols;
-    WgP p{};
-    p.zero = zero_page();
-    p.pos_inf = __builtin_inff();
-    p.g = geo_strided(s);
-    p.dy = dy; p.x = x; p.Cin = s->Cin; p.Cout = s->Cout; p.pre_slope = 1.f; p.a_slope = 1.f; p.pix = s->Cin;
-    p.M = q.M; p.Kcols = q.cols; p.mper = q.mper; p.ns = q.slices; p.xcd = q.xcd; p.atomic = q.atomic;
-    p.x_bytes = (unsigned)(xi * s->N * sizeof(float));
-    if (workspace) {   // one slab per pixel slice, added in a fixed order
-        p.slabs = workspace;
-        p.bias_slabs = dbias ? workspace + (size_t)q.ns * n : nullptr;
+        if (workspace) {   // one slab per pixel slice, added in a fixed order
+            p.slabs = workspace;
+            p.bias_slabs = dbias ? workspace + (size_t)q.ns * q.rows * q.cols : nullptr;
+        } else {
+            wgrad_clear(q, acc, dw, dbias, st);
+            p.slabs = dw; p.bias_slabs = dbias;
+        }
         launch_wgrad_mfma(p, q, 0, st);
         rc = gim_check_launch("gim_conv2d_strided_wgrad");
-        if (rc) return rc;
-        return gim_wgrad_finish(p.slabs, p.bias_slabs, q.ns, nullptr, nullptr, nullptr, nullptr, dw, accumulate ? nullptr : dbias, nullptr,
-                                s->Cout, s->Cin, s->KH, 0, accumulate ? dw : nullptr, accumulate ? dbias : nullptr, stream);
-    }
-    if (!accumulate && q.atomic) {
-        (void)hipMemsetAsync(dw, 0, n * sizeof(float), st);
-        if (dbias) (void)hipMemsetAsync(dbias, 0, (size_t)q.rows * sizeof(float), st);
-    }
-    p.slabs = dw; p.bias_slabs = dbias;
-    launch_wgrad_mfma(p, q, 0, st);
-    return gim_check_launch("gim_conv2d_strided_wgrad");
+        if (rc || !workspace) return rc;
+        return gim_wgrad_finish(p.slabs, p.bias_slabs, q.ns, nullptr, nullptr, nullptr, nullptr, dw, acc ? nullptr : dbias, nullptr,
+                                h.Cout, h.Cin, h.KH, 0, acc ? dw : nullptr, acc ? dbias : nullptr, stream);
+    });
 }
 
 // The launches the three entry points above would make for `s`, nothing is launched (tests): kind 0 forward, 1 dgrad, 2 wgrad (atomic
@@ -2940,34 +2932,33 @@ extern "C" int gim_conv2d_strided_wgrad(const float* dy, const float* x, float* 
 // without taps as {0, 0, 0, 0} - the rest -1.  A batch beyond the buffer range reports its last half; a stride-1 dgrad is
 // gim_conv2d_dgrad's launch (gim_conv_launch_plan).
 extern "C" int gim_conv2d_strided_plan(const gim_infer_conv* s, int kind, int32_t* out) {
-    STRIDED_CHECK(s, "conv2d_strided_plan");
-    int rc;
+    const int rc = check_infer_conv(s, "conv2d_strided_plan", true);
+    if (rc) return rc;
     GIM_CHECK_ARG(out && kind >= 0 && kind <= 2 && !(kind == 1 && s->stride == 1), "conv2d_strided_plan: bad args");
     for (int i = 0; i < 16; ++i) out[i] = -1;
     float* const fake = reinterpret_cast<float*>(uintptr_t(4096));
     size_t xi, yi;
     strided_image_elems(s, xi, yi);
-    gim_infer_conv a, b;
-    if (split_batch(*s, xi > yi ? xi : yi, a, b)) return gim_conv2d_strided_plan(&b, kind, out);
-    if (kind == 0) {
-        ConvCall c{};
-        rc = convp_begin(c.p, geo_strided(s), s->Cin, s->Cout, s->Cin, 0, nullptr, "conv2d_strided_plan: one image exceeds 2 GiB");
-        if (rc) return rc;
-        c.p.x = fake; c.p.w = fake; c.p.epi = 1; c.p.no_split = 1;
-        const IgemmPlan q = plan_igemm(c.p, 0, (s->Cin % BK) != 0 ? 1 : 0);
-        out[0] = c.p.Ktot; out[1] = q.BM; out[2] = q.BN; out[3] = q.ksplit;
-    } else if (kind == 1) {
-        StridedDgrad d;
-        rc = strided_dgrad_fill(d, fake, fake, fake, s, 0);
-        if (rc) return rc;
-        for (int cls = 0; cls < 4; ++cls) {
-            int32_t* o = out + 4 * cls;
-            if (!d.taps[cls]) { o[0] = o[1] = o[2] = o[3] = 0; continue; }
-            o[0] = d.c[cls].p.Ktot; o[1] = d.q[cls].BM; o[2] = d.q[cls].BN; o[3] = d.q[cls].ksplit;
+    return over_batch_halves(*s, xi, yi, [&](const gim_infer_conv& h, size_t, bool) {   // every part writes the rows: the last one stays
+        if (kind == 0) {
+            ConvCall c;
+            const int rc = infer_call(c, fake, fake, nullptr, nullptr, fake, &h);
+            if (rc) return rc;
+            const IgemmPlan q = plan_igemm(c.p, c.bmode, c.gen);
+            out[0] = c.p.Ktot; out[1] = q.BM; out[2] = q.BN; out[3] = q.ksplit;
+        } else if (kind == 1) {
+            StridedDgrad d;
+            const int rc = strided_dgrad_fill(d, fake, fake, fake, &h, 0);
+            if (rc) return rc;
+            for (int cls = 0; cls < 4; ++cls) {
+                int32_t* o = out + 4 * cls;
+                if (!d.taps[cls]) { o[0] = o[1] = o[2] = o[3] = 0; continue; }
+                o[0] = d.c[cls].p.Ktot; o[1] = d.q[cls].BM; o[2] = d.q[cls].BN; o[3] = d.q[cls].ksplit;
+            }
+        } else {
+            const WgPlan q = strided_wgrad_plan(&h, WG_ACC);
+            out[0] = q.cols; out[1] = q.bm; out[2] = q.bn; out[3] = q.slices;
         }
-    } else {
-        const WgPlan q = strided_wgrad_plan(s, WG_ACC);
-        out[0] = q.cols; out[1] = q.bm; out[2] = q.bn; out[3] = q.slices;
-    }
-    return GIM_OK;
+        return (int)GIM_OK;
+    });
 }

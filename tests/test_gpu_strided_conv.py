@@ -180,6 +180,71 @@ def test_wgrad_entry_accumulates_and_clears():
             assert ew < TOL_WGRAD and eb < TOL, (use_ws, acc, ew, eb)
 
 
+def test_strided_operands_beyond_2gib_are_split_over_the_batch():
+    """test_gpu_ops.py::test_conv_operands_beyond_2gib_are_split_over_the_batch for the strided entries: x and dx of 2.5 GB are beyond
+    one launch's 32-bit buffer offsets, so every entry halves the batch; K = 3 puts all four dgrad classes across the seam, and the
+    second half of the weight gradient must ADD to the first - with the float atomics and with the workspace the query reports.
+    (The forward entry has no deterministic mode: it never splits K.)  y and dx on both halves and the seam against fp64 F.conv2d
+    and its autograd; dw and dbias against an fp64 sum over chunks of 50 images, within the 1e-4 of the plain test's atomic combine."""
+    from optimalstrategiesagainstgenerativeattacks_amd import _lib
+    lib = _lib.load()
+    N, S, C, K = 600, 256, 16, 3
+    So = S // 2
+    g = torch.Generator(device="cuda").manual_seed(7)
+    x = torch.randn(N, S, S, C, device=dev(), generator=g)
+    dy = torch.randn(N, So, So, C, device=dev(), generator=g)
+    w = torch.randn(C, K, K, C, device=dev(), generator=g) * (K * K * C) ** -0.5
+    b = torch.randn(C, device=dev(), generator=g)
+    assert x.numel() * 4 > 2 ** 31
+    st = torch.cuda.current_stream().cuda_stream
+    sh = _lib.GimInferConv(N, S, S, C, C, K, 2)
+    slices = (slice(0, 2), slice(299, 301), slice(598, 600))      # both halves and the seam
+    wr = w.double().cpu().permute(0, 3, 1, 2)
+
+    y = torch.full((N, So, So, C), float("nan"), device=dev())
+    _lib.check(lib.gim_conv2d_strided_fwd(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), ctypes.byref(sh), st), "conv2d_strided_fwd")
+    dx_ref = {}
+    for sl in slices:
+        xr = x[sl].double().cpu().permute(0, 3, 1, 2).requires_grad_()
+        yr = F.conv2d(xr, wr, b.double().cpu(), stride=2, padding=1)
+        e = relerr(y[sl], yr.detach().permute(0, 2, 3, 1))
+        print("strided > 2 GiB: y[%d:%d] %.2e" % (sl.start, sl.stop, e))
+        assert e < TOL, (sl, e)
+        dx_ref[sl.start] = torch.autograd.grad(yr, xr, dy[sl].double().cpu().permute(0, 3, 1, 2))[0].permute(0, 2, 3, 1)
+    del y
+    for det in (0, 1):
+        dx = torch.full((N, S, S, C), float("nan"), device=dev())
+        _lib.check(lib.gim_conv2d_strided_dgrad(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), ctypes.byref(sh), det, st), "conv2d_strided_dgrad")
+        for sl in slices:
+            e = relerr(dx[sl], dx_ref[sl.start])
+            print("strided > 2 GiB: det=%d dx[%d:%d] %.2e" % (det, sl.start, sl.stop, e))
+            assert e < TOL, (det, sl, e)
+        del dx
+
+    # dw[o][a][b][c] = sum dy[n][oy][ox][o] * xpad[n][2 oy + a][2 ox + b][c]
+    dw_ref = torch.zeros(C, K, K, C, device=dev(), dtype=torch.float64)
+    db_ref = torch.zeros(C, device=dev(), dtype=torch.float64)
+    for n0 in range(0, N, 50):
+        xp = F.pad(x[n0:n0 + 50].double(), (0, 0, 1, 1, 1, 1))
+        dyc = dy[n0:n0 + 50].double()
+        for a in range(K):
+            for bb in range(K):
+                dw_ref[:, a, bb, :] += torch.einsum("nhwo,nhwc->oc", dyc, xp[:, a:a + S:2, bb:bb + S:2])
+        db_ref += dyc.sum((0, 1, 2))
+    del xp, dyc
+    nbytes = ctypes.c_int64(0)
+    _lib.check(lib.gim_conv2d_strided_wgrad_workspace(ctypes.byref(sh), ctypes.byref(nbytes)), "conv2d_strided_wgrad_workspace")
+    for use_ws in (False, True):
+        ws = torch.full((nbytes.value // 4,), float("nan"), device=dev()) if use_ws else None
+        dw = torch.full((C, K, K, C), float("nan"), device=dev())
+        db = torch.full((C,), float("nan"), device=dev())
+        _lib.check(lib.gim_conv2d_strided_wgrad(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), db.data_ptr(), ctypes.byref(sh), 0,
+                                                ws.data_ptr() if use_ws else None, st), "conv2d_strided_wgrad")
+        ew, eb = relerr(dw, dw_ref), relerr(db, db_ref)
+        print("strided > 2 GiB: ws=%d dw %.2e db %.2e" % (use_ws, ew, eb))
+        assert ew < 1e-4 and eb < 1e-4, (use_ws, ew, eb)
+
+
 @pytest.mark.parametrize("name", ["fast", "many_images_8x8", "many_images_4x4", "bias"])
 def test_deterministic_mode_is_bit_reproducible(name):
     ops = ops_mod()
