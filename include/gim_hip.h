@@ -599,6 +599,35 @@ int gim_conv2d_strided_wgrad(const float* dy, const float* x, float* dw, float* 
                              float* workspace, void* stream);
 int gim_conv2d_strided_plan(const gim_infer_conv* shape, int kind, int32_t* out);
 
+/* ---- ROC statistics of two score sets as exact integer counts (authentication_eval.roc_statistics / calibrate_threshold: the
+ * decision threshold of a baseline authenticator).  csrc/roc.hip.  pos [n_pos] are the scores on real sets, neg [n_neg] the scores on
+ * fake sets, cand [n_cand] candidate thresholds: fp32, any float-aligned pointers, any positive sizes with n_cand < 2^31 and
+ * n_pos + n_neg < 2^31 (GIM_E_BADARG otherwise).  Comparisons are IEEE on unflushed fp32: -0 == 0, the infinities are ordered,
+ * subnormals differ from 0 and from each other, and a NaN (score or candidate) compares false everywhere, so it counts nowhere.  No
+ * sort, no float atomics, nothing rounded: every result is an integer, bit-identical between runs.
+ *   gim_roc_slices   : pure host function, nothing is launched: the number of slices (grid.y) into which a counts launch with n_cand
+ *       candidates cuts n_scores = n_pos + n_neg scores.  One thread per candidate and 256 per workgroup; with few candidates the
+ *       scores' tiles of 1024 are dealt to up to 4096 / workgroups slices, never more slices than n_scores has tiles.
+ *   gim_roc_counts   : counts[3][n_cand] (uint32), for every candidate c: plane 0 #{i : pos[i] >= c}, plane 1 #{j : neg[j] < c},
+ *       plane 2 #{j : neg[j] == c}.  The call zeroes the 3 * n_cand words it uses on `stream` (one fill per call), then the slices add
+ *       their counts by integer atomics: the result does not depend on the slicing.
+ *   gim_roc_calibrate: the counts with cand = [pos; neg] (never materialised) into the caller's `counts` workspace of
+ *       3 * (n_pos + n_neg) words, then one finish launch that reduces them to record[GIM_ROC_WORDS] (int64):
+ *         [0] sum over the positives c of plane 1 (negatives below each positive), [1] the same of plane 2 (ties) - the AUC is
+ *             ([0] + [1] / 2) / (n_pos n_neg);
+ *         [2] the best key, max_c plane0[c] * n_neg + plane1[c] * n_pos = 2 n_pos n_neg times the best balanced accuracy of a rule
+ *             "accept when score >= c";
+ *         [3] the chosen candidate's index in [pos; neg]: among the candidates with the best key the largest score value (reject when
+ *             in doubt; -0 and 0 are one value), among equal values the smallest index;
+ *         [4] its plane 0 (true accepts), [5] its plane 1 (true rejects);
+ *         [6] the number of NaN scores in pos and neg together;
+ *         [7] the chosen score's fp32 bit pattern in the low 32 bits. */
+int gim_roc_slices(int64_t n_cand, int64_t n_scores);
+int gim_roc_counts(const float* cand, int n_cand, const float* pos, int n_pos, const float* neg, int n_neg, uint32_t* counts,
+                   void* stream);
+#define GIM_ROC_WORDS 8
+int gim_roc_calibrate(const float* pos, int n_pos, const float* neg, int n_neg, uint32_t* counts, int64_t* record, void* stream);
+
 /* Stream self-check: one wave busy for `usec` microseconds (1 .. 5000, constant 100 MHz wall clock) on `stream`.  The host
  * launches one per engine stream at the same moment and event-times the total: streams that share a HIP hardware queue serialize
  * (nn.DataParallel's one-thread-per-device streams of training/gim_img_training.py:406-411 have no such aliasing to check). */

@@ -47,6 +47,7 @@ from .gim_img_training import (au_eval_step, au_train_step, eval_step, gim_step,
 from .baselines import ArcFace, Backbone, ProtonetEmbeddingNet, SiameseNet
 from .baseline_training import (ArcFaceTrainer, IdentitySampler, PairSampler, SiameseTrainer, arcface_forward_train, margin_softmax_loss,
                                 siamese_forward_train, top1_accuracy, train_arcface, train_siamese)
+from .authentication_eval import calibrate_baseline, calibrate_threshold, roc_statistics
 from .training_logger import Logger
 from .optim import FusedAdam
 from .training_utils import CheckpointIO, DataParallelMock, EpisodeParallel, GlobalStep, adjust_batch_size, pin_rank_to_cores
@@ -59,4 +60,5 @@ __all__ = [
     "ImagePack", "pack_directory", "pack_omniglot", "resample_table", "resize_images",
     "PairSampler", "SiameseTrainer", "siamese_forward_train", "train_siamese",
     "IdentitySampler", "ArcFaceTrainer", "arcface_forward_train", "margin_softmax_loss", "top1_accuracy", "train_arcface",
+    "calibrate_baseline", "calibrate_threshold", "roc_statistics",
 ]

@@ -161,6 +161,9 @@ SIGNATURES = {
     "gim_conv2d_strided_wgrad_workspace": [POINTER(GimInferConv), POINTER(c_int64)],
     "gim_conv2d_strided_wgrad": [P, P, P, P, POINTER(GimInferConv), c_int, P, P],
     "gim_conv2d_strided_plan": [POINTER(GimInferConv), c_int, P],
+    "gim_roc_slices": [c_int64, c_int64],
+    "gim_roc_counts": [P, c_int, P, c_int, P, c_int, P, P],
+    "gim_roc_calibrate": [P, c_int, P, c_int, P, P, P],
     "gim_version": [],
 }
 

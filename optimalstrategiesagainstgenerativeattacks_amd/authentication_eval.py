@@ -9,6 +9,7 @@ authenticators (``baselines.py``), the random-source impersonator, the dispatche
 which writes the reference's CSV columns with the ``csv`` module."""
 import csv
 import itertools
+import json
 import os
 import random
 
@@ -99,8 +100,73 @@ def roc_auc(y_true, y_score):
     return float((ranks[y_true].sum() - n_pos * (n_pos + 1) / 2.0) / (n_pos * n_neg))
 
 
-def eval_authenticator_and_impersonator(device, ds, batch_size, num_workers, authenticator, impersonator, dbg=False):
-    """authentication_score.py:45-97: accuracy (total, on fake, on real) and ROC-AUC of `authenticator` against `impersonator`."""
+def _roc_record_host(pos, neg):
+    """The eight words of gim_roc_calibrate (include/gim_hip.h) for the NaN-free candidates [pos; neg], sort-based in fp64 on the
+    host; the last word is the chosen score itself, not its bit pattern."""
+    n_pos, n_neg = len(pos), len(neg)
+    cand = np.concatenate([pos, neg])
+    sp, sn = np.sort(pos), np.sort(neg)
+    p0 = n_pos - np.searchsorted(sp, cand, side="left")          # positives >= c
+    p1 = np.searchsorted(sn, cand, side="left")                  # negatives < c
+    p2 = np.searchsorted(sn, cand, side="right") - p1            # negatives == c
+    key = p0.astype(np.int64) * n_neg + p1.astype(np.int64) * n_pos
+    best = np.flatnonzero(key == key.max())
+    idx = int(best[cand[best] == cand[best].max()][0])           # the largest value with the best key, its first occurrence
+    return [int(p1[:n_pos].sum()), int(p2[:n_pos].sum()), int(key[idx]), idx, int(p0[idx]), int(p1[idx]), 0, float(cand[idx])]
+
+
+def _roc_stats(record, th, n_pos, n_neg):
+    """The dict of roc_statistics from the record's integers (fp64 on the host) and the chosen score."""
+    if record[6]:
+        raise ValueError("roc_statistics: %d of the scores are NaN" % record[6])
+    return {"auc": (record[0] + 0.5 * record[1]) / (n_pos * n_neg), "th": float(th),
+            "balanced_acc": record[2] / (2 * n_pos * n_neg), "acc_on_real": record[4] / n_pos, "acc_on_fake": record[5] / n_neg,
+            "n_real": n_pos, "n_fake": n_neg}
+
+
+def _score_sets(out_on_real, out_on_fake):
+    sets = []
+    for name, v in (("out_on_real", out_on_real), ("out_on_fake", out_on_fake)):
+        v = v.detach().reshape(-1) if torch.is_tensor(v) else np.asarray(v, dtype=np.float64).reshape(-1)
+        if len(v) == 0:
+            raise ValueError("roc_statistics: %s is empty" % name)
+        sets.append(v)
+    return sets
+
+
+def roc_statistics_host(out_on_real, out_on_fake):
+    """roc_statistics in numpy / fp64 on the host: the CPU path, and the reference the kernels are tested against."""
+    pos, neg = (np.asarray(v.cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float64)
+                for v in _score_sets(out_on_real, out_on_fake))
+    n_nan = int(np.isnan(pos).sum() + np.isnan(neg).sum())
+    if n_nan:
+        raise ValueError("roc_statistics: %d of the scores are NaN" % n_nan)
+    record = _roc_record_host(pos, neg)
+    return _roc_stats(record, record[7], len(pos), len(neg))
+
+
+def roc_statistics(out_on_real, out_on_fake):
+    """ROC statistics of the scores on real sets (positives) against the scores on fake sets (negatives), and the operating point
+    a threshold calibration takes from them.  For every score c as a candidate threshold of the rule "accept when score >= c":
+    tp(c) = #{real >= c}, tn(c) = #{fake < c}.  Returns a dict of Python floats / ints:
+      auc          (#{(r, f) : f < r} + #{(r, f) : f == r} / 2) / (n_real n_fake) - equal to roc_auc bit for bit;
+      th           the candidate with the largest balanced accuracy; among several the largest score (reject when in doubt);
+      balanced_acc (tp / n_real + tn / n_fake) / 2 at th (>= 0.5), acc_on_real = tp / n_real (> 0), acc_on_fake = tn / n_fake;
+      n_real, n_fake.
+    th is one of the scores themselves, so `score >= th` reproduces acc_on_real / acc_on_fake exactly.  CUDA tensors are counted
+    on the device (ops.roc_record: exact integer counts, one host read of eight words), anything else by roc_statistics_host; the
+    two give the same dict.  An empty score set or a NaN score raises ValueError."""
+    pos, neg = _score_sets(out_on_real, out_on_fake)
+    if not (torch.is_tensor(pos) and torch.is_tensor(neg) and pos.is_cuda and neg.is_cuda):
+        return roc_statistics_host(pos, neg)
+    record, _ = ops.roc_record(pos, neg)
+    th = np.array([record[7]], dtype=np.uint32).view(np.float32)[0]
+    return _roc_stats(record, th, pos.numel(), neg.numel())
+
+
+def collect_scores(device, ds, batch_size, num_workers, authenticator, impersonator, dbg=False):
+    """The batch loop of authentication_score.py:45-97: the authenticator's outputs and decisions on every real set of `ds` and on
+    the impersonator's answer to its leaked set.  -> (out_on_real, out_on_fake, pred_on_real, pred_on_fake), 1-D, on the device."""
     outs = {"or": [], "of": [], "pr": [], "pf": []}
     batches, n_batches = _batches(ds, batch_size, True, num_workers, device)
     num_iters = min(1000, n_batches) if dbg else n_batches
@@ -113,8 +179,14 @@ def eval_authenticator_and_impersonator(device, ds, batch_size, num_workers, aut
         out_on_fake, pred_on_fake = authenticator.act(test_sample=fake_sample, si_sample=si_sample)
         for k_, v in (("or", out_on_real), ("of", out_on_fake), ("pr", pred_on_real), ("pf", pred_on_fake)):
             outs[k_].append(v.view(-1).detach())
-    out_on_real, out_on_fake = torch.cat(outs["or"]), torch.cat(outs["of"])
-    acc, acc_on_fake, acc_on_real = comp_acc(pred_on_real=torch.cat(outs["pr"]), pred_on_fake=torch.cat(outs["pf"]))
+    return tuple(torch.cat(outs[k_]) for k_ in ("or", "of", "pr", "pf"))
+
+
+def eval_authenticator_and_impersonator(device, ds, batch_size, num_workers, authenticator, impersonator, dbg=False):
+    """authentication_score.py:45-97: accuracy (total, on fake, on real) and ROC-AUC of `authenticator` against `impersonator`."""
+    out_on_real, out_on_fake, pred_on_real, pred_on_fake = collect_scores(device, ds, batch_size, num_workers, authenticator,
+                                                                          impersonator, dbg=dbg)
+    acc, acc_on_fake, acc_on_real = comp_acc(pred_on_real=pred_on_real, pred_on_fake=pred_on_fake)
     y_true = torch.cat([torch.ones_like(out_on_real), torch.zeros_like(out_on_fake)]).cpu().numpy()
     y_score = torch.cat([out_on_real, out_on_fake]).cpu().numpy()
     return acc, acc_on_fake, acc_on_real, roc_auc(y_true, y_score)
@@ -171,7 +243,7 @@ def get_siamese_authenticator(device, ckpt_path, args_dict):
     net = ProtonetEmbeddingNet(inp_n_channels=1, inp_img_size=32)      # the reference evaluates the siamese baseline on Omniglot only
     siamese = SiameseNet(net, net.embedding_dim)
     siamese.load_state_dict(torch.load(ckpt_path, map_location='cpu')['model'], strict=True)
-    return Authenticator(get_siamese_au_function(siamese.to(device)))
+    return Authenticator(get_siamese_au_function(siamese.to(device)), th=args_dict.get('th', 0.))
 
 
 def get_arcface_authenticator(device, ckpt_path, args_dict):
@@ -262,3 +334,40 @@ def eval_authentication_task(device, ds, m, n, k, batch_size, num_workers, gim_e
         wr.writeheader()
         wr.writerows(rows)
     return rows
+
+
+# ------------------------------------------------------------------------------------------------------
+# calibrating a baseline's decision threshold
+# ------------------------------------------------------------------------------------------------------
+def calibrate_threshold(authenticator, device, ds, batch_size, num_workers, impersonator=None):
+    """Sets authenticator.th to the threshold of the largest balanced accuracy (roc_statistics) on the real sets of `ds` against
+    `impersonator` - by default the random-source impersonator over `ds`, the table's rnd_src row: other identities are what a
+    verification threshold separates.  Returns the statistics."""
+    if impersonator is None:
+        impersonator = get_impersonator(device=device, im_type='rnd_src', ckpt_path=None, ds=ds, args_dict=None)
+    out_on_real, out_on_fake, _, _ = collect_scores(device, ds, batch_size, num_workers, authenticator, impersonator)
+    stats = roc_statistics(out_on_real, out_on_fake)
+    authenticator.th = stats['th']
+    return stats
+
+
+def calibrate_baseline(device, baseline_type, baseline_exp_dir, ds, batch_size, num_workers=0, specific_model=None, ckpt_dir='ckpts'):
+    """Calibrates the threshold of a trained baseline (siamese | arcface) on `ds` - held-out data, not the training set - and
+    stores it in the experiment's args.json, from where eval_authentication_task loads it: `th` becomes the calibrated value and
+    `th_calibration` records {auc, balanced_acc, acc_on_real, acc_on_fake, n_real, n_fake, ds_root, ckpt}; every other key is
+    kept.  The file is replaced atomically.  Returns the statistics of calibrate_threshold."""
+    if baseline_type not in ('siamese', 'arcface'):
+        raise ValueError("unsupported baseline type %r (siamese | arcface)" % (baseline_type,))
+    ckpt_path, args_dict = get_exp_args_from_dir(baseline_exp_dir, ckpt_dir, specific_model=specific_model)
+    au_agent = get_authenticator(device=device, au_type=baseline_type, ckpt_path=ckpt_path, args_dict=args_dict)
+    stats = calibrate_threshold(au_agent, device, ds, batch_size, num_workers)
+    args = load_args(baseline_exp_dir)                     # the file as written, without the keys get_exp_args_from_dir derives
+    args['th'] = stats['th']
+    args['th_calibration'] = dict({k_: stats[k_] for k_ in ('auc', 'balanced_acc', 'acc_on_real', 'acc_on_fake', 'n_real', 'n_fake')},
+                                  ds_root=getattr(ds, "root", ""), ckpt=os.path.basename(ckpt_path))
+    path = os.path.join(baseline_exp_dir, "args.json")
+    tmp = path + ".tmp.%d" % os.getpid()
+    with open(tmp, "w") as f:
+        json.dump(args, f)
+    os.replace(tmp, path)
+    return stats

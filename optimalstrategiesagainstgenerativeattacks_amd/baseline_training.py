@@ -477,7 +477,8 @@ def train_arcface(device, bank, out_dir, n_iters, num_layers=50, batch_size=128,
     save_every iterations and at the end; logs ('arcface', 'loss' / 'acc') every log_every iterations.  Returns the trainer.
 
     th is stored as given: the decision threshold of ArcFace.predict on the score -|e1 - e2|^2 <= 0.  The reference's default of 1.5
-    can never be reached by such a score; calibrating it (on held-out pairs) is not part of the training."""
+    can never be reached by such a score; calibrating it is a step of its own on held-out data,
+    authentication_eval.calibrate_baseline(device, 'arcface', out_dir, ds, batch_size), which rewrites th in args.json."""
     device = torch.device(device)
     if num_layers not in (50, 100, 152):
         raise ValueError("train_arcface: num_layers should be 50, 100 or 152")

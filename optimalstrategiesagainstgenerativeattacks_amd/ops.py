@@ -2842,3 +2842,49 @@ class SoftmaxCEFn(Function):
 def softmax_ce(logits, label):
     """-> (loss [B], correct [B])."""
     return SoftmaxCEFn.apply(logits, label)
+
+
+# --------------------------------------------------------------------------------------------
+# ROC statistics of two score sets as exact integer counts (authentication_eval.roc_statistics; csrc/roc.hip)
+# --------------------------------------------------------------------------------------------
+ROC_WORDS = 8       # GIM_ROC_WORDS of include/gim_hip.h
+
+
+def roc_slices(n_cand, n_scores):
+    """Number of slices a counts launch with `n_cand` candidates cuts `n_scores` = n_pos + n_neg scores into."""
+    n = _lib.load().gim_roc_slices(n_cand, n_scores)
+    if n <= 0:
+        check(n, "roc_slices")
+    return n
+
+
+def _req_scores(t, name):
+    t = _req(t, name)
+    if t.dim() != 1 or t.numel() == 0:
+        raise RuntimeError("%s must be a non-empty 1-D tensor, got %s" % (name, tuple(t.shape)))
+    return t
+
+
+def roc_counts(cand, pos, neg):
+    """int64 [3, n_cand]: per candidate c the number of pos >= c, of neg < c and of neg == c (IEEE comparisons of fp32)."""
+    cand, pos, neg = _req_scores(cand, "cand"), _req_scores(pos, "pos"), _req_scores(neg, "neg")
+    counts = torch.empty((3, cand.numel()), device=cand.device, dtype=torch.int32)       # uint32 words; every count is below 2^31
+    check(_lib.load().gim_roc_counts(_p(cand), cand.numel(), _p(pos), pos.numel(), _p(neg), neg.numel(), counts.data_ptr(), _stream()),
+          "roc_counts")
+    return counts.to(torch.int64)
+
+
+def roc_record(pos, neg, counts=None):
+    """(record, counts) of the candidates [pos; neg]: record = the ROC_WORDS int64 words of gim_roc_calibrate as a list of Python
+    ints - the call's ONE host read - and counts the int32 [3, n_pos + n_neg] view of the workspace it filled.  `counts`: a CUDA
+    int32 workspace of at least 3 * (n_pos + n_neg) words to use instead of a fresh one; the call zeroes what it uses."""
+    pos, neg = _req_scores(pos, "pos"), _req_scores(neg, "neg")
+    n = pos.numel() + neg.numel()
+    if counts is None:
+        counts = torch.empty(3 * n, device=pos.device, dtype=torch.int32)
+    elif not (counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= 3 * n):
+        raise RuntimeError("roc_record: counts must be a contiguous CUDA int32 workspace of at least %d words" % (3 * n))
+    record = torch.empty(ROC_WORDS, device=pos.device, dtype=torch.int64)
+    check(_lib.load().gim_roc_calibrate(_p(pos), pos.numel(), _p(neg), neg.numel(), counts.data_ptr(), record.data_ptr(), _stream()),
+          "roc_calibrate")
+    return record.tolist(), counts.view(-1)[:3 * n].view(3, n)
