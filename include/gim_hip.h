@@ -134,7 +134,9 @@ int gim_conv2d_wgrad(const float* dy, const float* x, float* slabs, float* bias_
  *                   weight = weight_orig / (u^T W v) with u, v constants).
  * u [Cout]; v [Cin*KH*KW] in the REFERENCE's flattening order (ci, kh, kw).  scratch: >= 512 floats, plus
  * Cout*(KH+1)^2*Cin floats when fold != 0.  acc_dw / acc_db (may be NULL): ADD the results into these buffers
- * (the optimizer's flat gradient bucket) instead of returning them in dw / db (dw then is scratch). */
+ * (the optimizer's flat gradient bucket) instead of returning them in dw / db (dw then is scratch).
+ * Cout*(KH+1)^2*Cin < 2^31 (GIM_E_BADARG otherwise): the un-fold and the chain rule index with 32 bits, as the batched form
+ * below does. */
 int gim_wgrad_finish(const float* slabs, const float* bias_slabs, int n_slabs, const float* w, const float* sigma,
                      const float* u, const float* v, float* dw, float* db, float* scratch, int Cout, int Cin, int KH,
                      int fold, float* acc_dw, float* acc_db, void* stream);

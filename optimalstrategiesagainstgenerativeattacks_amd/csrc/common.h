@@ -43,14 +43,20 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-// Sum over a 256-thread block; result valid in every thread. `red` = 4 floats of LDS.
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
+// Sum over a block of NT threads (a multiple of 64); result valid in every thread. `red` = NT / 64 floats of LDS.  The wave
+// partials are added in index order.
+template <int NT>
+__device__ __forceinline__ float block_sum(float v, float* red) {
     v = wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
+    float tot = red[0];
+#pragma unroll
+    for (int i = 1; i < NT / 64; ++i) tot += red[i];
+    return tot;
 }
+__device__ __forceinline__ float block_sum_256(float v, float* red) { return block_sum<256>(v, red); }
 
 __device__ __forceinline__ float lrelu_f(float v, float slope) { return v > 0.f ? v : v * slope; }
 

@@ -1468,28 +1468,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_row_kernel(const WgP p) {
 // -------------------------------------------------------------------------------------------------
 // folded weights: F[co][a][b][ci] = sum_{dh,dw in {0,1}} W[co][a-dh][b-dw][ci],  a, b in [0, K]
 // -------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void fold_weights_kernel(const float* __restrict__ w, float* __restrict__ f, int Cout, int Cin, int K) {
-    const int KF = K + 1;
-    const long long n = (long long)Cout * KF * KF * Cin;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const int ci = (int)(i % Cin);
-        long long rr = i / Cin;
-        const int b = (int)(rr % KF); rr /= KF;
-        const int a = (int)(rr % KF);
-        const int co = (int)(rr / KF);
-        float s = 0.f;
-#pragma unroll
-        for (int dh = 0; dh < 2; ++dh)
-#pragma unroll
-            for (int dw = 0; dw < 2; ++dw) {
-                const int kh = a - dh, kw = b - dw;
-                if (kh >= 0 && kh < K && kw >= 0 && kw < K) s += w[(((long long)co * K + kh) * K + kw) * Cin + ci];
-            }
-        f[i] = s;
-    }
-}
-
-// all folds of a model in one launch: block b works on chunk tab[2b+1] (of 65536 elements) of job tab[2b].
+// A fold is a gim_fold_job walked in chunks of folded elements.  All folds of a model in one launch: block b works on chunk
+// tab[2b+1] (of 65536 elements) of job tab[2b].
 // (Round 4: 32-bit indices, the tap count a compile-time constant - its divisions become multiplies - and 16-byte loads / stores
 // along the channels when Cin % 4 == 0: the first version's three 64-bit divisions per ELEMENT made the two launches of a step
 // 0.53 ms at the head of the forward passes, ~4x the time of the bytes they move: profiles/r04_c_fold_weights_kernel.txt.)
@@ -1534,16 +1514,25 @@ __device__ __forceinline__ void fold_chunk(const gim_fold_job& jb, unsigned lo, 
     }
 }
 
-__global__ __launch_bounds__(256) void fold_weights_batched_kernel(const gim_fold_job* __restrict__ jobs, const int* __restrict__ tab) {
-    const gim_fold_job jb = jobs[tab[2 * blockIdx.x]];
+#define FOLD_CHUNK 65536u       // folded elements per block of the batched launch (the callers' tables are built on it)
+#define FOLD_CHUNK_CALL 4096u   // ... and of the per-call launch, where one weight has to fill the chip by itself
+__device__ __forceinline__ void fold_job_range(const gim_fold_job& jb, unsigned lo, unsigned len) {
     const unsigned KF = (unsigned)jb.KH + 1u;
     const unsigned n = (unsigned)jb.Cout * KF * KF * (unsigned)jb.Cin;     // < 2^31: checked on the host
-    const unsigned lo = (unsigned)tab[2 * blockIdx.x + 1] * 65536u, hi = lo + 65536u < n ? lo + 65536u : n;
+    const unsigned hi = lo + len < n ? lo + len : n;
     if (KF == 4) fold_chunk<4>(jb, lo, hi);            // 3 x 3 convolutions
     else if (KF == 10) fold_chunk<10>(jb, lo, hi);     // 9 x 9
     else if (KF == 2) fold_chunk<2>(jb, lo, hi);       // 1 x 1
     else fold_chunk<0>(jb, lo, hi);
 }
+
+__global__ __launch_bounds__(256) void fold_weights_batched_kernel(const gim_fold_job* __restrict__ jobs, const int* __restrict__ tab) {
+    const gim_fold_job jb = jobs[tab[2 * blockIdx.x]];
+    fold_job_range(jb, (unsigned)tab[2 * blockIdx.x + 1] * FOLD_CHUNK, FOLD_CHUNK);
+}
+
+// one fold per call: the job by value
+__global__ __launch_bounds__(256) void fold_weights_kernel(const gim_fold_job jb) { fold_job_range(jb, blockIdx.x * FOLD_CHUNK_CALL, FOLD_CHUNK_CALL); }
 
 extern "C" int gim_conv2d_fold_weights_batched(const gim_fold_job* jobs, const int32_t* tab, int n_blocks, void* stream) {
     GIM_CHECK_ARG(jobs && tab && n_blocks > 0, "fold_weights_batched: bad args");
@@ -1554,9 +1543,9 @@ extern "C" int gim_conv2d_fold_weights_batched(const gim_fold_job* jobs, const i
 extern "C" int gim_conv2d_fold_weights(const float* w, float* f, int Cout, int Cin, int KH, void* stream) {
     GIM_CHECK_ARG(w && f && Cout > 0 && Cin > 0 && KH > 0 && (KH & 1), "fold_weights: bad args");
     const long long n = (long long)Cout * (KH + 1) * (KH + 1) * Cin;
-    long long blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(fold_weights_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, w, f, Cout, Cin, KH);
+    GIM_CHECK_ARG(n < (1LL << 31), "fold_weights: Cout*(KH+1)^2*Cin must be below 2^31");
+    const gim_fold_job jb = {w, f, Cout, Cin, KH, 0};
+    hipLaunchKernelGGL(fold_weights_kernel, dim3((unsigned)((n + FOLD_CHUNK_CALL - 1) / FOLD_CHUNK_CALL)), dim3(256), 0, (hipStream_t)stream, jb);
     return gim_check_launch("gim_conv2d_fold_weights");
 }
 

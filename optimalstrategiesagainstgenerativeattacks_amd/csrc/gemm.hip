@@ -18,13 +18,13 @@ struct BgP {
     long long sAb, sAi, sAk, sBb, sBk, sBj;
 };
 
-__global__ __launch_bounds__(256) void bgemm_kernel(const BgP p) {
+// One 64 x 64 tile of A * B in the MFMA accumulators of the block's four waves (wave wv: rows 32 (wv >> 1), columns 32 (wv & 1)).
+// P: M, N, K and the element strides sAi, sAk, sBk, sBj (BgP or gim_gemm_job); A, B: the operands of this block's product.
+template <class P>
+__device__ __forceinline__ f32x16 bgemm_tile(const P& p, const float* A, const float* B, int i0, int j0) {
     __shared__ float As[2][GK * GLD];
     __shared__ float Bs[2][GK * GLD];
     const int t = threadIdx.x;
-    const int i0 = blockIdx.y * GB, j0 = blockIdx.x * GB;
-    const float* A = p.A + (long long)blockIdx.z * p.sAb;
-    const float* B = p.B + (long long)blockIdx.z * p.sBb;
     const bool a_kfast = (p.sAk == 1);
     const bool b_jfast = (p.sBj == 1);
 
@@ -78,15 +78,27 @@ __global__ __launch_bounds__(256) void bgemm_kernel(const BgP p) {
         if (ks + 1 < nk) store_tiles(buf ^ 1);
         __syncthreads();
     }
-    float* C = p.C + (long long)blockIdx.z * p.M * p.N;
+    return acc;
+}
+
+// the accumulator tile into row-major C [M][N]: lane (r, h) of wave wv holds column wn0 + r, rows wm0 + (e & 3) + 8 (e >> 2) + 4 h
+__device__ __forceinline__ void store_tile(float* C, int M, int N, int i0, int j0, const f32x16& acc) {
+    const int t = threadIdx.x, lane = t & 63, r = lane & 31, h = lane >> 5, wv = t >> 6;
+    const int wm0 = (wv >> 1) * 32, wn0 = (wv & 1) * 32;
     const int j = j0 + wn0 + r;
-    if (j < p.N) {
+    if (j < N) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int i = i0 + wm0 + (e & 3) + 8 * (e >> 2) + 4 * h;
-            if (i < p.M) C[(long long)i * p.N + j] = acc[e];
+            if (i < M) C[(long long)i * N + j] = acc[e];
         }
     }
+}
+
+__global__ __launch_bounds__(256) void bgemm_kernel(const BgP p) {
+    const int i0 = blockIdx.y * GB, j0 = blockIdx.x * GB;
+    const f32x16 acc = bgemm_tile(p, p.A + (long long)blockIdx.z * p.sAb, p.B + (long long)blockIdx.z * p.sBb, i0, j0);
+    store_tile(p.C + (long long)blockIdx.z * p.M * p.N, p.M, p.N, i0, j0, acc);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -99,63 +111,11 @@ __global__ __launch_bounds__(256) void bgemm_kernel(const BgP p) {
 // w.r.t. the shared input, pre-zeroed by the caller).  bias: added per output column (forward).
 // -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void bgemm_grouped_kernel(const gim_gemm_job* __restrict__ jobs, const int* __restrict__ tiles) {
-    __shared__ float As[2][GK * GLD];
-    __shared__ float Bs[2][GK * GLD];
-    const int t = threadIdx.x;
     const int job = tiles[3 * blockIdx.x], i0 = tiles[3 * blockIdx.x + 1] * GB, j0 = tiles[3 * blockIdx.x + 2] * GB;
     const gim_gemm_job p = jobs[job];
-    const float* A = p.A;
-    const float* B = p.B;
-    const bool a_kfast = (p.sAk == 1);
-    const bool b_jfast = (p.sBj == 1);
-    float ra[4], rb[4];
-    auto load_tiles = [&](int k0) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int idx = t + 256 * e;
-            int i, k;
-            if (a_kfast) { k = idx & 15; i = idx >> 4; } else { i = idx & 63; k = idx >> 6; }
-            const bool v = (i0 + i) < p.M && (k0 + k) < p.K;
-            ra[e] = v ? A[(long long)(i0 + i) * p.sAi + (long long)(k0 + k) * p.sAk] : 0.f;
-            int j, kb;
-            if (b_jfast) { j = idx & 63; kb = idx >> 6; } else { kb = idx & 15; j = idx >> 4; }
-            const bool vb = (j0 + j) < p.N && (k0 + kb) < p.K;
-            rb[e] = vb ? B[(long long)(k0 + kb) * p.sBk + (long long)(j0 + j) * p.sBj] : 0.f;
-        }
-    };
-    auto store_tiles = [&](int buf) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int idx = t + 256 * e;
-            int i, k;
-            if (a_kfast) { k = idx & 15; i = idx >> 4; } else { i = idx & 63; k = idx >> 6; }
-            As[buf][k * GLD + i] = ra[e];
-            int j, kb;
-            if (b_jfast) { j = idx & 63; kb = idx >> 6; } else { kb = idx & 15; j = idx >> 4; }
-            Bs[buf][kb * GLD + j] = rb[e];
-        }
-    };
-    const int lane = t & 63, r = lane & 31, h = lane >> 5, wv = t >> 6;
+    const f32x16 acc = bgemm_tile(p, p.A, p.B, i0, j0);
+    const int t = threadIdx.x, lane = t & 63, r = lane & 31, h = lane >> 5, wv = t >> 6;
     const int wm0 = (wv >> 1) * 32, wn0 = (wv & 1) * 32;
-    f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-    const int nk = (p.K + GK - 1) / GK;
-    load_tiles(0);
-    store_tiles(0);
-    __syncthreads();
-    for (int ks = 0; ks < nk; ++ks) {
-        const int buf = ks & 1;
-        if (ks + 1 < nk) load_tiles((ks + 1) * GK);
-#pragma unroll
-        for (int kp = 0; kp < GK / 2; ++kp) {
-            const float a = As[buf][(2 * kp + h) * GLD + wm0 + r];
-            const float b = Bs[buf][(2 * kp + h) * GLD + wn0 + r];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-        }
-        if (ks + 1 < nk) store_tiles(buf ^ 1);
-        __syncthreads();
-    }
     const int j = j0 + wn0 + r;
     if (j < p.N) {
         const float bv = p.bias ? p.bias[j] : 0.f;
@@ -280,15 +240,7 @@ __global__ __launch_bounds__(256) void bgemm_vec_kernel(const BgP p) {
         if (ks + 1 < nk) store_tiles(buf ^ 1);
         __syncthreads();
     }
-    float* C = p.C + (long long)blockIdx.z * p.M * p.N;
-    const int j = j0 + wn0 + r;
-    if (j < p.N) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int i = i0 + wm0 + (e & 3) + 8 * (e >> 2) + 4 * h;
-            if (i < p.M) C[(long long)i * p.N + j] = acc[e];
-        }
-    }
+    store_tile(p.C + (long long)blockIdx.z * p.M * p.N, p.M, p.N, i0, j0, acc);
 }
 
 // -------------------------------------------------------------------------------------------------

@@ -533,21 +533,30 @@ __device__ __forceinline__ float colsum_rows_64x4(const float* __restrict__ x, i
     __syncthreads();
     return s;
 }
-__global__ __launch_bounds__(256) void colsum_final_kernel(const float* __restrict__ part, float* __restrict__ out, int P, int C) {
+__global__ __launch_bounds__(256) void colsum_final_kernel(const float* __restrict__ part, float* __restrict__ out, int P, int C, int accumulate) {
     __shared__ float red[4][64];
     const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6, c = blockIdx.x * 64 + cl;
     const float s = colsum_rows_64x4(part, P, C, c, rg, red, cl);
-    if (rg == 0 && c < C) out[c] = s;
+    if (rg == 0 && c < C) out[c] = accumulate ? out[c] + s : s;
 }
-extern "C" int gim_colsum(const float* x, float* out, float* scratch, int64_t rows, int C, void* stream) {
-    GIM_CHECK_ARG(x && out && scratch && rows > 0 && C > 0, "colsum: bad args");
+// out[c] (+)= sum_r x[r][c] in two stages: up to 256 row parts into scratch, then their sum
+static int colsum_launch(const float* x, float* out, float* scratch, int64_t rows, int C, int accumulate, void* stream, const char* what) {
     long long P = (rows + 63) / 64;
     if (P > 256) P = 256;
     const long long rows_per = (rows + P - 1) / P;
     P = (rows + rows_per - 1) / rows_per;
     hipLaunchKernelGGL(colsum_part_kernel, dim3((C + 63) / 64, (int)P), dim3(256), 0, (hipStream_t)stream, x, scratch, (long long)rows, C, rows_per);
-    hipLaunchKernelGGL(colsum_final_kernel, dim3((C + 63) / 64), dim3(256), 0, (hipStream_t)stream, scratch, out, (int)P, C);
-    return gim_check_launch("gim_colsum");
+    hipLaunchKernelGGL(colsum_final_kernel, dim3((C + 63) / 64), dim3(256), 0, (hipStream_t)stream, scratch, out, (int)P, C, accumulate);
+    return gim_check_launch(what);
+}
+extern "C" int gim_colsum(const float* x, float* out, float* scratch, int64_t rows, int C, void* stream) {
+    GIM_CHECK_ARG(x && out && scratch && rows > 0 && C > 0, "colsum: bad args");
+    return colsum_launch(x, out, scratch, rows, C, 0, stream, "gim_colsum");
+}
+// gim_colsum that ADDS: bias gradients straight into the optimizer's gradient bucket
+extern "C" int gim_colsum_acc(const float* x, float* out, float* scratch, int64_t rows, int C, void* stream) {
+    GIM_CHECK_ARG(x && out && scratch && rows > 0 && C > 0, "colsum_acc: bad args");
+    return colsum_launch(x, out, scratch, rows, C, 1, stream, "gim_colsum_acc");
 }
 
 // ---------------------------------------------------------------- sums / repeats over the sample dim
@@ -883,24 +892,6 @@ extern "C" int gim_colsum2(const float* a, const float* b, float* out_a, float* 
     GIM_CHECK_ARG(a && b && out_a && out_b && rows > 0 && C > 0, "colsum2: bad args");
     hipLaunchKernelGGL(colsum2_kernel, dim3((C + 63) / 64), dim3(256), 0, (hipStream_t)stream, a, b, out_a, out_b, rows, C, accumulate);
     return gim_check_launch("gim_colsum2");
-}
-
-__global__ __launch_bounds__(256) void colsum_final_acc_kernel(const float* __restrict__ part, float* __restrict__ out, int P, int C) {
-    __shared__ float red[4][64];
-    const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6, c = blockIdx.x * 64 + cl;
-    const float s = colsum_rows_64x4(part, P, C, c, rg, red, cl);
-    if (rg == 0 && c < C) out[c] += s;
-}
-// out[c] += sum_r x[r][c]  (gim_colsum that ADDS: bias gradients straight into the optimizer's gradient bucket)
-extern "C" int gim_colsum_acc(const float* x, float* out, float* scratch, int64_t rows, int C, void* stream) {
-    GIM_CHECK_ARG(x && out && scratch && rows > 0 && C > 0, "colsum_acc: bad args");
-    long long P = (rows + 63) / 64;
-    if (P > 256) P = 256;
-    const long long rows_per = (rows + P - 1) / P;
-    P = (rows + rows_per - 1) / rows_per;
-    hipLaunchKernelGGL(colsum_part_kernel, dim3((C + 63) / 64, (int)P), dim3(256), 0, (hipStream_t)stream, x, scratch, (long long)rows, C, rows_per);
-    hipLaunchKernelGGL(colsum_final_acc_kernel, dim3((C + 63) / 64), dim3(256), 0, (hipStream_t)stream, scratch, out, (int)P, C);
-    return gim_check_launch("gim_colsum_acc");
 }
 
 // ---------------------------------------------------------------- depth to space

@@ -7,90 +7,127 @@
 
 #define SN_R 8  // row chunks of the W^T u partial sums
 
+// -------------------------------------------------------------------------------------------------
+// power iteration: four stages over a view of ONE weight.  The per-call kernels (sn_*) get the view by value; the batched ones
+// (snb_*) build it from their job, so one round of every conv of a model is 4 launches: the iterations are data independent
+// and a model runs all its rounds up front instead of 4 tiny launches per conv call.
+// -------------------------------------------------------------------------------------------------
+struct SnView {
+    const float* w;
+    float *u, *v;                  // state, updated in place when training
+    float *sigma, *u_out, *v_out;  // results: copies of the vectors used
+    float *part, *v_phys, *tvec;   // scratch: [SN_R][K], [K] (v in physical order), [Cout]
+    int Cout, Cin, T, K;
+};
+
+__host__ __device__ __forceinline__ SnView sn_view(const float* w, float* u, float* v, float* sigma, float* u_out, float* v_out,
+                                                   float* scratch, int Cout, int Cin, int KH) {
+    SnView s;
+    s.w = w; s.u = u; s.v = v; s.sigma = sigma; s.u_out = u_out; s.v_out = v_out;
+    s.Cout = Cout; s.Cin = Cin; s.T = KH * KH; s.K = Cin * s.T;
+    s.part = scratch;
+    s.v_phys = scratch + (long long)SN_R * s.K;
+    s.tvec = s.v_phys + s.K;
+    return s;
+}
+__device__ __forceinline__ SnView sn_view(const gim_sn_job& jb, float* out_base) {
+    return sn_view(jb.w, jb.u, jb.v, out_base + jb.off_sigma, out_base + jb.off_u, out_base + jb.off_v, out_base + jb.off_scratch,
+                   jb.Cout, jb.Cin, jb.KH);
+}
+__host__ __device__ __forceinline__ int sn_row_chunks(int Cout) { return min(SN_R, (Cout + 63) / 64); }
+
 // part[r][p] = sum over the r-th chunk of rows co of W[co][p] * u[co]
-__global__ __launch_bounds__(256) void sn_colpart_kernel(const float* __restrict__ w, const float* __restrict__ u,
-                                                         float* __restrict__ part, int Cout, int K, int rows_per) {
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    const int r = blockIdx.y;
-    const int c0 = r * rows_per, c1 = min(Cout, c0 + rows_per);
-    if (p >= K) return;
+__device__ __forceinline__ void sn_colpart(const SnView& s, int p, int r, int rows_per) {
+    if (p >= s.K) return;
+    const int c0 = r * rows_per, c1 = min(s.Cout, c0 + rows_per);
     float acc = 0.f;
-    for (int co = c0; co < c1; ++co) acc += w[(long long)co * K + p] * u[co];
-    part[(long long)r * K + p] = acc;
+    for (int co = c0; co < c1; ++co) acc += s.w[(long long)co * s.K + p] * s.u[co];
+    s.part[(long long)r * s.K + p] = acc;
 }
 
-// single block.  training: a = sum_r part[r]; v = a / max(|a|, eps) ; else v given.
+// single block of NT threads.  training: a = sum_r part[r]; v = a / max(|a|, eps) ; else v given.
 // writes v_phys (physical order, scratch), v (torch order, in place when training) and v_out (copy).
-__global__ __launch_bounds__(256) void sn_vnorm_kernel(const float* __restrict__ part, int R, float* __restrict__ v,
-                                                       float* __restrict__ v_phys, float* __restrict__ v_out, int K, int Cin,
-                                                       int T, int training) {
-    __shared__ float red[4];
+template <int NT>
+__device__ __forceinline__ void sn_vnorm(const SnView& s, int training, float* red) {
     if (training) {
+        const int R = sn_row_chunks(s.Cout);
         float ss = 0.f;
-        for (int p = threadIdx.x; p < K; p += 256) {
+        for (int p = threadIdx.x; p < s.K; p += NT) {
             float a = 0.f;
-            for (int r = 0; r < R; ++r) a += part[(long long)r * K + p];
-            v_phys[p] = a;
+            for (int r = 0; r < R; ++r) a += s.part[(long long)r * s.K + p];
+            s.v_phys[p] = a;
             ss += a * a;
         }
-        const float nrm = sqrtf(block_sum_256(ss, red));
-        const float inv = 1.0f / fmaxf(nrm, 1e-12f);
-        for (int p = threadIdx.x; p < K; p += 256) {
-            const float val = v_phys[p] * inv;
-            const int tap = p / Cin, ci = p - tap * Cin;
-            const int q = ci * T + tap;
-            v_phys[p] = val;
-            v[q] = val;
-            v_out[q] = val;
+        const float inv = 1.0f / fmaxf(sqrtf(block_sum<NT>(ss, red)), 1e-12f);
+        for (int p = threadIdx.x; p < s.K; p += NT) {   // each thread re-reads only what it wrote itself
+            const float val = s.v_phys[p] * inv;
+            const int tap = p / s.Cin, ci = p - tap * s.Cin;
+            const int q = ci * s.T + tap;
+            s.v_phys[p] = val;
+            s.v[q] = val;
+            s.v_out[q] = val;
         }
     } else {
-        for (int q = threadIdx.x; q < K; q += 256) {
-            const int ci = q / T, tap = q - ci * T;
-            const float val = v[q];
-            v_phys[tap * Cin + ci] = val;
-            v_out[q] = val;
+        for (int q = threadIdx.x; q < s.K; q += NT) {
+            const int ci = q / s.T, tap = q - ci * s.T;
+            const float val = s.v[q];
+            s.v_phys[tap * s.Cin + ci] = val;
+            s.v_out[q] = val;
         }
     }
 }
 
 // t[co] = sum_p W[co][p] * v_phys[p]; one wave per row
-__global__ __launch_bounds__(256) void sn_rowdot_kernel(const float* __restrict__ w, const float* __restrict__ v_phys,
-                                                        float* __restrict__ tvec, int Cout, int K) {
-    const int co = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (co >= Cout) return;
+__device__ __forceinline__ void sn_rowdot(const SnView& s, int co, int lane) {
+    if (co >= s.Cout) return;
+    const float* row = s.w + (long long)co * s.K;
     float acc = 0.f;
-    const float* row = w + (long long)co * K;
-    for (int p = lane; p < K; p += 64) acc += row[p] * v_phys[p];
+    for (int p = lane; p < s.K; p += 64) acc += row[p] * s.v_phys[p];
     acc = wave_sum(acc);
-    if (lane == 0) tvec[co] = acc;
+    if (lane == 0) s.tvec[co] = acc;
 }
 
-// single block. training: u = t / max(|t|, eps); sigma = u . t ; else sigma = u . t with the stored u.
-__global__ __launch_bounds__(256) void sn_final_kernel(const float* __restrict__ tvec, float* __restrict__ u,
-                                                       float* __restrict__ u_out, float* __restrict__ sigma, int Cout,
-                                                       int training) {
-    __shared__ float red[4];
+// single block of 256. training: u = t / max(|t|, eps); sigma = u . t ; else sigma = u . t with the stored u.
+__device__ __forceinline__ void sn_final(const SnView& s, int training, float* red) {
     float inv = 0.f;
     if (training) {
         float ss = 0.f;
-        for (int c = threadIdx.x; c < Cout; c += 256) ss += tvec[c] * tvec[c];
+        for (int c = threadIdx.x; c < s.Cout; c += 256) ss += s.tvec[c] * s.tvec[c];
         inv = 1.0f / fmaxf(sqrtf(block_sum_256(ss, red)), 1e-12f);
     }
     float dot = 0.f;
-    for (int c = threadIdx.x; c < Cout; c += 256) {
+    for (int c = threadIdx.x; c < s.Cout; c += 256) {
         float uv;
         if (training) {
-            uv = tvec[c] * inv;
-            u[c] = uv;
+            uv = s.tvec[c] * inv;
+            s.u[c] = uv;
         } else {
-            uv = u[c];
+            uv = s.u[c];
         }
-        u_out[c] = uv;
-        dot += uv * tvec[c];
+        s.u_out[c] = uv;
+        dot += uv * s.tvec[c];
     }
     dot = block_sum_256(dot, red);
-    if (threadIdx.x == 0) sigma[0] = dot;
+    if (threadIdx.x == 0) s.sigma[0] = dot;
+}
+
+__global__ __launch_bounds__(256) void sn_colpart_kernel(const SnView s, int rows_per) {
+    sn_colpart(s, blockIdx.x * 256 + threadIdx.x, blockIdx.y, rows_per);
+}
+__global__ __launch_bounds__(256) void sn_rowdot_kernel(const SnView s) {
+    sn_rowdot(s, blockIdx.x * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
+}
+// (the four vectors once more as arguments of their own: __restrict__ holds on kernel arguments only, and with it the compiler
+//  keeps the unrolled store loop this kernel always had; without, + 5 % on the entry at 512 x 512 x 3 x 3)
+__global__ __launch_bounds__(256) void sn_vnorm_kernel(SnView s, float* __restrict__ part, float* __restrict__ v_phys,
+                                                       float* __restrict__ v, float* __restrict__ v_out, int training) {
+    __shared__ float red[4];
+    s.part = part; s.v_phys = v_phys; s.v = v; s.v_out = v_out;
+    sn_vnorm<256>(s, training, red);
+}
+__global__ __launch_bounds__(256) void sn_final_kernel(const SnView s, int training) {
+    __shared__ float red[4];
+    sn_final(s, training, red);
 }
 
 extern "C" int gim_spectral_sigma(const float* w, float* u, float* v, float* sigma, float* u_out, float* v_out, float* scratch,
@@ -98,20 +135,53 @@ extern "C" int gim_spectral_sigma(const float* w, float* u, float* v, float* sig
     GIM_CHECK_ARG(w && u && v && sigma && u_out && v_out && scratch, "spectral_sigma: null pointer");
     GIM_CHECK_ARG(Cout > 0 && Cin > 0 && KH > 0, "spectral_sigma: bad dims");
     hipStream_t st = (hipStream_t)stream;
-    const int T = KH * KH, K = Cin * T;
-    float* part = scratch;                 // [SN_R][K]
-    float* v_phys = scratch + SN_R * K;    // [K]
-    float* tvec = v_phys + K;              // [Cout]
-    int R = 1;
+    const SnView s = sn_view(w, u, v, sigma, u_out, v_out, scratch, Cout, Cin, KH);
     if (training) {
-        R = min(SN_R, (Cout + 63) / 64);
-        const int rows_per = (Cout + R - 1) / R;
-        hipLaunchKernelGGL(sn_colpart_kernel, dim3((K + 255) / 256, R), dim3(256), 0, st, w, u, part, Cout, K, rows_per);
+        const int R = sn_row_chunks(Cout);
+        hipLaunchKernelGGL(sn_colpart_kernel, dim3((s.K + 255) / 256, R), dim3(256), 0, st, s, (Cout + R - 1) / R);
     }
-    hipLaunchKernelGGL(sn_vnorm_kernel, dim3(1), dim3(256), 0, st, part, R, v, v_phys, v_out, K, Cin, T, training);
-    hipLaunchKernelGGL(sn_rowdot_kernel, dim3((Cout + 3) / 4), dim3(256), 0, st, w, v_phys, tvec, Cout, K);
-    hipLaunchKernelGGL(sn_final_kernel, dim3(1), dim3(256), 0, st, tvec, u, u_out, sigma, Cout, training);
+    hipLaunchKernelGGL(sn_vnorm_kernel, dim3(1), dim3(256), 0, st, s, s.part, s.v_phys, s.v, s.v_out, training);
+    hipLaunchKernelGGL(sn_rowdot_kernel, dim3((Cout + 3) / 4), dim3(256), 0, st, s);
+    hipLaunchKernelGGL(sn_final_kernel, dim3(1), dim3(256), 0, st, s, training);
     return gim_check_launch("gim_spectral_sigma");
+}
+
+// Batched form.  Job table and block->job maps are static per model; per-round outputs live at static offsets from `out_base`.
+__global__ __launch_bounds__(256) void snb_colpart_kernel(const gim_sn_job* __restrict__ jobs, const int4* __restrict__ tab,
+                                                          float* __restrict__ out_base) {
+    const int4 e = tab[blockIdx.x];  // {job, column block, row chunk, rows per chunk}
+    sn_colpart(sn_view(jobs[e.x], out_base), e.y * 256 + threadIdx.x, e.z, e.w);
+}
+
+// One block of 1024 threads per job (the jobs are few - one per conv - and a 256-thread block walking the 4608-5120 columns of
+// the largest ones was a 46 us chain of dependent-latency loads at the head of every forward pass).
+__global__ __launch_bounds__(1024) void snb_vnorm_kernel(const gim_sn_job* __restrict__ jobs, float* __restrict__ out_base, int training) {
+    __shared__ float red[16];
+    sn_vnorm<1024>(sn_view(jobs[blockIdx.x], out_base), training, red);
+}
+
+__global__ __launch_bounds__(256) void snb_rowdot_kernel(const gim_sn_job* __restrict__ jobs, const int2* __restrict__ tab,
+                                                         float* __restrict__ out_base) {
+    const int2 e = tab[blockIdx.x];  // {job, row block}
+    sn_rowdot(sn_view(jobs[e.x], out_base), e.y * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
+}
+
+__global__ __launch_bounds__(256) void snb_final_kernel(const gim_sn_job* __restrict__ jobs, float* __restrict__ out_base, int training) {
+    __shared__ float red[4];
+    sn_final(sn_view(jobs[blockIdx.x], out_base), training, red);
+}
+
+extern "C" int gim_spectral_sigma_batched(const gim_sn_job* jobs, int n_jobs, const int32_t* tab_cols, int n_col_blocks,
+                                          const int32_t* tab_rows, int n_row_blocks, float* out_base, int training, void* stream) {
+    GIM_CHECK_ARG(jobs && n_jobs > 0 && tab_cols && tab_rows && out_base && n_col_blocks > 0 && n_row_blocks > 0,
+                  "spectral_sigma_batched: bad args");
+    hipStream_t st = (hipStream_t)stream;
+    if (training)
+        hipLaunchKernelGGL(snb_colpart_kernel, dim3(n_col_blocks), dim3(256), 0, st, jobs, reinterpret_cast<const int4*>(tab_cols), out_base);
+    hipLaunchKernelGGL(snb_vnorm_kernel, dim3(n_jobs), dim3(1024), 0, st, jobs, out_base, training);
+    hipLaunchKernelGGL(snb_rowdot_kernel, dim3(n_row_blocks), dim3(256), 0, st, jobs, reinterpret_cast<const int2*>(tab_rows), out_base);
+    hipLaunchKernelGGL(snb_final_kernel, dim3(n_jobs), dim3(256), 0, st, jobs, out_base, training);
+    return gim_check_launch("gim_spectral_sigma_batched");
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -165,31 +235,64 @@ __global__ __launch_bounds__(256) void wgrad_sum_kernel(const float* __restrict_
     }
 }
 
-// fold 1: src = dF [Cout][KF][KF][Cin]:  dW[co][kh][kw][ci] = 0.25 * sum_{dh,dw} dF[co][kh+dh][kw+dw][ci]
-// fold 2: src = G  [Cin][KF][KF][Cout] with dF[co][a][b][ci] = G[ci][K-a][K-b][co]:  dW = sum_{dh,dw} dF[..][kh+dh][kw+dw][..]
+// The two bodies below are shared by the per-call finish (gim_wgrad_finish, slab mode) and the batched one (wgq_*, the training
+// step).  All their index arithmetic is 32-bit - Cout*(K+1)^2*Cin < 2^31 per weight, checked by gim_wgrad_finish and by
+// ops.WgradQueue for the job tables: the first version's 64-bit divisions per element made these HBM-bound passes 3x slower
+// than the bytes they move.
+
+// Where tap (a, b) of dF[co][a][b][ci], the gradient of the folded weights [Cout][K+1][K+1][Cin], lies in the source:
+//   fold 1: src = dF itself;   fold 2: src = G [Cin][K+1][K+1][Cout] with dF[co][a][b][ci] = G[ci][K-a][K-b][co]
+__device__ __forceinline__ unsigned fold_index(unsigned co, unsigned a, unsigned b, unsigned ci, unsigned Cout, unsigned Cin,
+                                               unsigned K, int fold) {
+    const unsigned KF = K + 1;
+    return fold == 1 ? ((co * KF + a) * KF + b) * Cin + ci : ((ci * KF + (K - a)) * KF + (K - b)) * Cout + co;
+}
+
+// element i of the un-folded gradient [Cout][K][K][Cin]:
+//   fold 0: src[i];   fold 1: dW[co][kh][kw][ci] = 0.25 * sum_{dh,dw} dF[co][kh+dh][kw+dw][ci];   fold 2: the same sum without the
+//   factor;   fold 3: the row-padded slot of gim_conv2d_wgrad_rows_acc, [Cout][K][K * Cin rounded up to 16]
+__device__ __forceinline__ float unfold_load(const float* __restrict__ src, unsigned i, unsigned Cout, unsigned Cin, unsigned K, int fold) {
+    if (fold == 0) return src[i];
+    const unsigned r1 = i / Cin, ci = i - r1 * Cin;
+    const unsigned r2 = r1 / K, kw = r1 - r2 * K;
+    if (fold == 3) return src[r2 * ((K * Cin + 15u) & ~15u) + kw * Cin + ci];
+    const unsigned co = r2 / K, kh = r2 - co * K;
+    float g = 0.f;
+#pragma unroll
+    for (unsigned dh = 0; dh < 2; ++dh)
+#pragma unroll
+        for (unsigned dwd = 0; dwd < 2; ++dwd) g += src[fold_index(co, kh + dh, kw + dwd, ci, Cout, Cin, K, fold)];
+    return fold == 1 ? 0.25f * g : g;
+}
+
+// Spectral-norm chain rule dW = g / sigma - (<g, W> / sigma^2) u v^T for NV consecutive input channels of one (co, tap), with
+// inv = 1 / sigma and coef = <g, W> / sigma^2:  out[e] = g[e] * inv - (coef * u[co]) * v[(ci + e) * T + tap].
+// The element is (co, p = tap * Cin + ci); p may run past Kc = T * Cin (whole output channels are carried into co: a chunk
+// states the (co, p) of its first element once and adds the offset, so only layers with fewer weights per output channel than
+// the chunk wrap more than once) and ONE division by Cin is left per element.
+template <int NV>
+__device__ __forceinline__ void sn_chain(const float* g, float* out, float inv, float coef, const float* __restrict__ u,
+                                         const float* __restrict__ v, unsigned co, unsigned p, unsigned Kc, unsigned Cin, unsigned T) {
+    if (p >= Kc) {
+        const unsigned q = p / Kc;
+        co += q;
+        p -= q * Kc;
+    }
+    const unsigned tap = p / Cin, ci = p - tap * Cin;
+    const float cu = coef * u[co];
+    const float* vq = v + ci * T + tap;
+#pragma unroll
+    for (int e = 0; e < NV; ++e) out[e] = g[e] * inv - cu * vq[e * T];
+}
+
 __global__ __launch_bounds__(256) void wgrad_unfold_kernel(const float* __restrict__ src, const float* __restrict__ w,
                                                            float* __restrict__ dw, float* __restrict__ partial, int Cout, int Cin,
                                                            int K, int fold) {
     __shared__ float red[4];
-    const int KF = K + 1;
-    const long long n = (long long)Cout * K * K * Cin;
+    const unsigned n = (unsigned)Cout * K * K * Cin;
     float dot = 0.f;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const int ci = (int)(i % Cin);
-        long long rr = i / Cin;
-        const int kw = (int)(rr % K); rr /= K;
-        const int kh = (int)(rr % K);
-        const int co = (int)(rr / K);
-        float g = 0.f;
-#pragma unroll
-        for (int dh = 0; dh < 2; ++dh)
-#pragma unroll
-            for (int dwd = 0; dwd < 2; ++dwd) {
-                const int a = kh + dh, b = kw + dwd;
-                if (fold == 1) g += src[(((long long)co * KF + a) * KF + b) * Cin + ci];
-                else g += src[(((long long)ci * KF + (K - a)) * KF + (K - b)) * Cout + co];
-            }
-        if (fold == 1) g *= 0.25f;
+    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const float g = unfold_load(src, i, Cout, Cin, K, fold);
         dw[i] = g;
         if (w) dot += g * w[i];
     }
@@ -202,20 +305,16 @@ __global__ __launch_bounds__(256) void wgrad_unfold_kernel(const float* __restri
 __global__ __launch_bounds__(256) void wgrad_sn_apply_kernel(const float* __restrict__ g, float* __restrict__ dw, int accumulate,
                                                              const float* __restrict__ partial, int n_part,
                                                              const float* __restrict__ sigma, const float* __restrict__ u,
-                                                             const float* __restrict__ v, long long n, int Cin, int T) {
+                                                             const float* __restrict__ v, unsigned n, int Cin, int T) {
     __shared__ float red[4];
     float d = 0.f;
     for (int i = threadIdx.x; i < n_part; i += 256) d += partial[i];
     d = block_sum_256(d, red);
-    const float s = sigma[0];
-    const float inv = 1.0f / s;
+    const float inv = 1.0f / sigma[0];
     const float coef = d * inv * inv;
-    const int K = Cin * T;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const int co = (int)(i / K);
-        const int p = (int)(i - (long long)co * K);
-        const int tap = p / Cin, ci = p - tap * Cin;
-        const float val = g[i] * inv - coef * u[co] * v[ci * T + tap];
+    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        float val;
+        sn_chain<1>(g + i, &val, inv, coef, u, v, 0, i, Cin * T, Cin, T);
         dw[i] = accumulate ? dw[i] + val : val;
     }
 }
@@ -230,6 +329,8 @@ extern "C" int gim_wgrad_finish(const float* slabs, const float* bias_slabs, int
     hipStream_t st = (hipStream_t)stream;
     const int T = KH * KH;
     const long long n = (long long)Cout * Cin * T;
+    const long long nf = (long long)Cout * Cin * (KH + 1) * (KH + 1);   // the folded layout
+    GIM_CHECK_ARG(nf < (1LL << 31), "wgrad_finish: Cout*(KH+1)^2*Cin must be below 2^31");
     int blocks = (int)((n + 1023) / 1024);
     if (blocks > WF_BLOCKS) blocks = WF_BLOCKS;
     if (blocks < 1) blocks = 1;
@@ -245,7 +346,6 @@ extern "C" int gim_wgrad_finish(const float* slabs, const float* bias_slabs, int
         blocks = sblocks;  // number of <g, w> partials for the spectral apply
     } else {
         // 1) sum the slabs (folded layout) into scratch[512 ...], bias on the way; 2) un-fold into dw (+ <g, w>)
-        const long long nf = (long long)Cout * Cin * (KH + 1) * (KH + 1);
         float* fsum = scratch + WF_BLOCKS;
         int fb = (int)((nf + 63) / 64);
         if (fb > WF_BLOCKS) fb = WF_BLOCKS;
@@ -256,131 +356,11 @@ extern "C" int gim_wgrad_finish(const float* slabs, const float* bias_slabs, int
     }
     if (sigma) {
         hipLaunchKernelGGL(wgrad_sn_apply_kernel, dim3(blocks), dim3(256), 0, st, dw, acc_dw ? acc_dw : dw, acc_dw ? 1 : 0, scratch,
-                           blocks, sigma, u, v, n, Cin, T);
+                           blocks, sigma, u, v, (unsigned)n, Cin, T);
     } else if (acc_dw && !direct) {
         GIM_CHECK_ARG(false, "wgrad_finish: acc_dw without sigma is only supported for fold == 0");
     }
     return gim_check_launch("gim_wgrad_finish");
-}
-
-// -------------------------------------------------------------------------------------------------
-// batched power iteration: ONE round (one iteration of every conv of a model) in 4 launches.
-// The iterations are data independent, so a model runs all its rounds up front instead of 4 tiny launches
-// per conv call.  Job table and block->job maps are static per model; per-round outputs live at static
-// offsets from `out_base`.
-// -------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void snb_colpart_kernel(const gim_sn_job* __restrict__ jobs, const int4* __restrict__ tab,
-                                                          float* __restrict__ out_base) {
-    const int4 e = tab[blockIdx.x];  // {job, column block, row chunk, rows per chunk}
-    const gim_sn_job jb = jobs[e.x];
-    const int K = jb.Cin * jb.KH * jb.KH;
-    const int p = e.y * 256 + threadIdx.x;
-    if (p >= K) return;
-    const int c0 = e.z * e.w, c1 = min(jb.Cout, c0 + e.w);
-    float acc = 0.f;
-    for (int co = c0; co < c1; ++co) acc += jb.w[(long long)co * K + p] * jb.u[co];
-    (out_base + jb.off_scratch)[(long long)e.z * K + p] = acc;
-}
-
-// One block of 1024 threads per job (the jobs are few - one per conv - and a 256-thread block walking the 4608-5120 columns of
-// the largest ones was a 46 us chain of dependent-latency loads at the head of every forward pass).
-__global__ __launch_bounds__(1024) void snb_vnorm_kernel(const gim_sn_job* __restrict__ jobs, float* __restrict__ out_base, int training) {
-    __shared__ float red[16];
-    const gim_sn_job jb = jobs[blockIdx.x];
-    const int T = jb.KH * jb.KH, K = jb.Cin * T;
-    const int R = min(SN_R, (jb.Cout + 63) / 64);
-    float* part = out_base + jb.off_scratch;
-    float* v_phys = part + (long long)SN_R * K;
-    float* v_out = out_base + jb.off_v;
-    if (training) {
-        float ss = 0.f;
-        for (int p = threadIdx.x; p < K; p += 1024) {
-            float a = 0.f;
-            for (int r = 0; r < R; ++r) a += part[(long long)r * K + p];
-            v_phys[p] = a;
-            ss += a * a;
-        }
-        ss = wave_sum(ss);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
-        __syncthreads();
-        float tot = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) tot += red[i];
-        const float inv = 1.0f / fmaxf(sqrtf(tot), 1e-12f);
-        for (int p = threadIdx.x; p < K; p += 1024) {   // each thread re-reads only what it wrote itself
-            const float val = v_phys[p] * inv;
-            const int tap = p / jb.Cin, ci = p - tap * jb.Cin;
-            const int q = ci * T + tap;
-            v_phys[p] = val;
-            jb.v[q] = val;
-            v_out[q] = val;
-        }
-    } else {
-        for (int q = threadIdx.x; q < K; q += 1024) {
-            const int ci = q / T, tap = q - ci * T;
-            const float val = jb.v[q];
-            v_phys[tap * jb.Cin + ci] = val;
-            v_out[q] = val;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void snb_rowdot_kernel(const gim_sn_job* __restrict__ jobs, const int2* __restrict__ tab,
-                                                         float* __restrict__ out_base) {
-    const int2 e = tab[blockIdx.x];  // {job, row block}
-    const gim_sn_job jb = jobs[e.x];
-    const int K = jb.Cin * jb.KH * jb.KH;
-    const int co = e.y * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (co >= jb.Cout) return;
-    const float* v_phys = out_base + jb.off_scratch + (long long)SN_R * K;
-    float* tvec = out_base + jb.off_scratch + (long long)(SN_R + 1) * K;
-    const float* row = jb.w + (long long)co * K;
-    float acc = 0.f;
-    for (int p = lane; p < K; p += 64) acc += row[p] * v_phys[p];
-    acc = wave_sum(acc);
-    if (lane == 0) tvec[co] = acc;
-}
-
-__global__ __launch_bounds__(256) void snb_final_kernel(const gim_sn_job* __restrict__ jobs, float* __restrict__ out_base, int training) {
-    __shared__ float red[4];
-    const gim_sn_job jb = jobs[blockIdx.x];
-    const int K = jb.Cin * jb.KH * jb.KH;
-    const float* tvec = out_base + jb.off_scratch + (long long)(SN_R + 1) * K;
-    float* u_out = out_base + jb.off_u;
-    float inv = 0.f;
-    if (training) {
-        float ss = 0.f;
-        for (int c = threadIdx.x; c < jb.Cout; c += 256) ss += tvec[c] * tvec[c];
-        inv = 1.0f / fmaxf(sqrtf(block_sum_256(ss, red)), 1e-12f);
-    }
-    float dot = 0.f;
-    for (int c = threadIdx.x; c < jb.Cout; c += 256) {
-        float uv;
-        if (training) {
-            uv = tvec[c] * inv;
-            jb.u[c] = uv;
-        } else {
-            uv = jb.u[c];
-        }
-        u_out[c] = uv;
-        dot += uv * tvec[c];
-    }
-    dot = block_sum_256(dot, red);
-    if (threadIdx.x == 0) (out_base + jb.off_sigma)[0] = dot;
-}
-
-extern "C" int gim_spectral_sigma_batched(const gim_sn_job* jobs, int n_jobs, const int32_t* tab_cols, int n_col_blocks,
-                                          const int32_t* tab_rows, int n_row_blocks, float* out_base, int training, void* stream) {
-    GIM_CHECK_ARG(jobs && n_jobs > 0 && tab_cols && tab_rows && out_base && n_col_blocks > 0 && n_row_blocks > 0,
-                  "spectral_sigma_batched: bad args");
-    hipStream_t st = (hipStream_t)stream;
-    if (training)
-        hipLaunchKernelGGL(snb_colpart_kernel, dim3(n_col_blocks), dim3(256), 0, st, jobs, reinterpret_cast<const int4*>(tab_cols), out_base);
-    hipLaunchKernelGGL(snb_vnorm_kernel, dim3(n_jobs), dim3(1024), 0, st, jobs, out_base, training);
-    hipLaunchKernelGGL(snb_rowdot_kernel, dim3(n_row_blocks), dim3(256), 0, st, jobs, reinterpret_cast<const int2*>(tab_rows), out_base);
-    hipLaunchKernelGGL(snb_final_kernel, dim3(n_jobs), dim3(256), 0, st, jobs, out_base, training);
-    return gim_check_launch("gim_spectral_sigma_batched");
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -390,28 +370,6 @@ extern "C" int gim_spectral_sigma_batched(const gim_sn_job* jobs, int n_jobs, co
 // gradient bucket.  One block handles WGQ_CHUNK elements of one job (table built on the host, static per model).
 // -------------------------------------------------------------------------------------------------
 #define WGQ_CHUNK 4096
-
-// (All index arithmetic is 32-bit - the caller guarantees Cout*(K+1)^2*Cin < 2^31 per job, ops.WgradQueue checks it: the first
-//  version's 64-bit divisions per element made these two HBM-bound passes 3x slower than the bytes they move.)
-__device__ __forceinline__ float wgq_load(const gim_wgrad_job& jb, unsigned i) {
-    if (jb.fold == 0) return jb.src[i];
-    const unsigned K = jb.K, KF = K + 1, Cin = jb.Cin, Cout = jb.Cout;
-    const unsigned r1 = i / Cin, ci = i - r1 * Cin;
-    const unsigned r2 = r1 / K, kw = r1 - r2 * K;
-    if (jb.fold == 3)   // row-padded slot of gim_conv2d_wgrad_rows_acc: [Cout][K][K * Cin rounded up to 16]
-        return jb.src[r2 * ((K * Cin + 15u) & ~15u) + kw * Cin + ci];
-    const unsigned co = r2 / K, kh = r2 - co * K;
-    float g = 0.f;
-#pragma unroll
-    for (unsigned dh = 0; dh < 2; ++dh)
-#pragma unroll
-        for (unsigned dwd = 0; dwd < 2; ++dwd) {
-            const unsigned a = kh + dh, b = kw + dwd;
-            if (jb.fold == 1) g += jb.src[((co * KF + a) * KF + b) * Cin + ci];
-            else g += jb.src[((ci * KF + (K - a)) * KF + (K - b)) * Cout + co];
-        }
-    return jb.fold == 1 ? 0.25f * g : g;
-}
 
 __device__ __forceinline__ bool wgq_aligned16(const void* a, const void* b, const void* c) {
     return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
@@ -433,17 +391,17 @@ __global__ __launch_bounds__(256) void wgq_reduce_kernel(const gim_wgrad_job* __
         // every element covered once, so `partial` and `tmp` keep their meaning), reads G along co, turns the tile in LDS and
         // writes along ci.
         __shared__ float tile[64][65];
-        const unsigned K = jb.K, KF = K + 1, T = K * K, Cin = jb.Cin, Cout = jb.Cout, tiles_ci = Cin >> 6;
+        const unsigned K = jb.K, T = K * K, Cin = jb.Cin, Cout = jb.Cout, tiles_ci = Cin >> 6;
         const unsigned tap = (unsigned)e.y % T, r = (unsigned)e.y / T;
         const unsigned ci0 = (r % tiles_ci) << 6, co0 = (r / tiles_ci) << 6;
         const unsigned kh = tap / K, kw = tap - kh * K;
         const unsigned lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll 4
         for (unsigned j = 0; j < 16; ++j) {
-            const unsigned ci = ci0 + wv + 4 * j;
-            const float* base = jb.src + (((size_t)ci * KF + (K - kh)) * KF + (K - kw)) * Cout + co0 + lane;
-            // taps (K-kh-dh, K-kw-dw), dh, dw in {0, 1}
-            tile[wv + 4 * j][lane] = (base[0] + base[-(long)Cout]) + (base[-(long)(KF * Cout)] + base[-(long)((KF + 1) * Cout)]);
+            const unsigned ci = ci0 + wv + 4 * j, co = co0 + lane;
+            const float* s = jb.src;
+            tile[wv + 4 * j][lane] = (s[fold_index(co, kh, kw, ci, Cout, Cin, K, 2)] + s[fold_index(co, kh, kw + 1, ci, Cout, Cin, K, 2)]) +
+                                     (s[fold_index(co, kh + 1, kw, ci, Cout, Cin, K, 2)] + s[fold_index(co, kh + 1, kw + 1, ci, Cout, Cin, K, 2)]);
         }
         __syncthreads();
 #pragma unroll 4
@@ -476,7 +434,7 @@ __global__ __launch_bounds__(256) void wgq_reduce_kernel(const gim_wgrad_job* __
 #pragma unroll 4
         for (unsigned t = threadIdx.x; t < cnt; t += 256) {
             const unsigned i = i0 + t;
-            const float g = wgq_load(jb, i);
+            const float g = unfold_load(jb.src, i, jb.Cout, jb.Cin, jb.K, jb.fold);
             if (sn) {
                 if (jb.fold) jb.tmp[i] = g;
                 dot += g * jb.w[i];
@@ -507,44 +465,27 @@ __global__ __launch_bounds__(256) void wgq_apply_kernel(const gim_wgrad_job* __r
     const unsigned i0 = (unsigned)e.y * WGQ_CHUNK;
     const unsigned cnt = min((unsigned)WGQ_CHUNK, n - i0);
     const float* __restrict__ g = jb.fold ? jb.tmp : jb.src;
-    // (co, p) of the chunk's first element once per block; per element a carry (only layers with fewer than 4096 weights per
-    // output channel wrap more than once) and ONE 32-bit division by Cin
-    const unsigned co0 = i0 / Kc, p0 = i0 - co0 * Kc;
+    const unsigned co0 = i0 / Kc, p0 = i0 - co0 * Kc;   // (co, p) of the chunk's first element, once per block
     if (jb.exclusive && (Cin & 3) == 0 && wgq_aligned16(g, jb.grad_w, jb.grad_w)) {
         // the only job of this gradient in the pass: 16-byte read-modify-write (4 consecutive input channels share the output
         // channel and the tap)
         for (unsigned t = threadIdx.x * 4; t < cnt; t += 1024) {
-            unsigned p = p0 + t, co = co0;
-            if (p >= Kc) {
-                const unsigned q = p / Kc;
-                co += q;
-                p -= q * Kc;
-            }
-            const unsigned tap = p / Cin, ci = p - tap * Cin;
             const float4 gv = *reinterpret_cast<const float4*>(g + i0 + t);
-            const float cu = coef * jb.u[co];
-            const float* v = jb.v + ci * T + tap;
+            const float ge[4] = {gv.x, gv.y, gv.z, gv.w};
+            float val[4];
+            sn_chain<4>(ge, val, inv, coef, jb.u, jb.v, co0, p0 + t, Kc, Cin, T);
             float4* dst = reinterpret_cast<float4*>(jb.grad_w + i0 + t);
             float4 o = *dst;
-            o.x += gv.x * inv - cu * v[0];
-            o.y += gv.y * inv - cu * v[T];
-            o.z += gv.z * inv - cu * v[2 * T];
-            o.w += gv.w * inv - cu * v[3 * T];
+            o.x += val[0]; o.y += val[1]; o.z += val[2]; o.w += val[3];
             *dst = o;
         }
         return;
     }
 #pragma unroll 4
     for (unsigned t = threadIdx.x; t < cnt; t += 256) {
-        unsigned p = p0 + t, co = co0;
-        if (p >= Kc) {
-            const unsigned q = p / Kc;
-            co += q;
-            p -= q * Kc;
-        }
-        const unsigned tap = p / Cin, ci = p - tap * Cin;
-        const unsigned i = i0 + t;
-        atomicAdd(&jb.grad_w[i], g[i] * inv - coef * jb.u[co] * jb.v[ci * T + tap]);
+        float val;
+        sn_chain<1>(g + i0 + t, &val, inv, coef, jb.u, jb.v, co0, p0 + t, Kc, Cin, T);
+        atomicAdd(&jb.grad_w[i0 + t], val);
     }
 }
 

@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from oracle import portable_fill as pf
+from tests import finish_ref as fr
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -423,3 +424,96 @@ def assert_rect_wgrad_row_plan(case):
         assert plan[7] == 1 and plan[1:3] == [128, 96] and plan[4] == 3 * (Cin // 32) and plan[5] == Cout // 128, (case, plan)
     else:
         assert plan[7] == 0 and plan[1:3] != [128, 96], (case, plan)
+
+
+# ---- guarded device buffers and the fp64 comparison of the direct C ABI tests (test_gpu_finish_kernels.py, test_gpu_twin_entries.py) ----
+TOL = 3e-5
+GUARD = 64
+SENTINEL = 1.25e30     # guard bands
+JUNK = -7.5e28         # what an output holds before the call: an element the kernel leaves out cannot pass a comparison
+
+
+def dev():
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    return torch.device("cuda:0")
+
+
+def f32(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float32))
+
+
+def f64(a):
+    return np.asarray(a, dtype=np.float64)
+
+
+def _dev_tensor(a):
+    return torch.from_numpy(f32(a).reshape(-1)).to(dev())
+
+
+class Guarded:
+    """n floats between two guard bands, one allocation.  init: values (any shape) or None = JUNK."""
+
+    def __init__(self, name, n, init=None):
+        self.name, self.n = name, n
+        self.raw = torch.full((n + 2 * GUARD,), SENTINEL, dtype=torch.float32, device=dev())
+        self.t = self.raw[GUARD:GUARD + n]
+        self.fill(init)
+
+    def fill(self, init=None):
+        if init is None:
+            self.t.fill_(JUNK)
+        else:
+            self.t.copy_(_dev_tensor(init))
+
+    @property
+    def ptr(self):
+        return self.t.data_ptr()
+
+    def np(self):
+        return self.t.double().cpu().numpy()
+
+    def intact(self):
+        lo, hi = self.raw[:GUARD], self.raw[GUARD + self.n:]
+        return bool((lo == SENTINEL).all()) and bool((hi == SENTINEL).all())
+
+
+class Pool(list):
+    def new(self, name, n, init=None):
+        self.append(Guarded(name, n, init))
+        return self[-1]
+
+    def check(self, what=""):
+        torch.cuda.synchronize()
+        broken = [g.name for g in self if not g.intact()]
+        assert not broken, "%s wrote outside %s" % (what, broken)
+
+
+_WORST = {}
+
+
+def _report(group, what, got, ref, bound=None, scale=None, m=None, l2_ref=None):
+    """Prints and returns (relative L2 error, largest |got - ref| / bound); bound = gamma(m) * scale unless given.  Where the bound
+    is zero the values must be equal.  l2_ref: another reference for the L2 error (the chained one of the power iterations)."""
+    got, ref = f64(got).reshape(-1), f64(ref).reshape(-1)
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    assert np.isfinite(got).all(), what
+    if bound is None:
+        bound = fr.gamma(m) * f64(scale).reshape(-1)
+    bound = np.broadcast_to(f64(bound).reshape(-1), ref.shape)
+    err = np.abs(got - ref)
+    pos = bound > 0
+    ratio = float((err[pos] / bound[pos]).max()) if pos.any() else 0.0
+    if (err[~pos] > 0).any():
+        ratio = float("inf")
+    l2 = relerr(torch.from_numpy(got), torch.from_numpy(ref if l2_ref is None else f64(l2_ref).reshape(-1)))
+    w = _WORST.setdefault(group, [0.0, 0.0])
+    w[0], w[1] = max(w[0], l2), max(w[1], ratio)
+    print("FINISH %s %s: L2 %.3e (TOL %.0e)  elementwise error / bound %.4f%s   [group worst so far: %.3e, %.4f]"
+          % (group, what, l2, TOL, ratio, "" if m is None else " (m = %d)" % m, w[0], w[1]))
+    return l2, ratio
+
+
+def _check(group, what, got, ref, bound=None, scale=None, m=None, l2_ref=None):
+    l2, ratio = _report(group, what, got, ref, bound, scale, m, l2_ref)
+    assert l2 < TOL, (what, "L2", l2)
+    assert ratio <= 1.0, (what, "elementwise error / bound", ratio)
