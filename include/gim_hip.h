@@ -497,6 +497,17 @@ int gim_absdiff(const float* a, const float* b, float* y, int64_t n, void* strea
  *       (each may be NULL): the same sums are also ADDED there (the parameters' .grad in the optimizer's bucket).
  *   gim_bn_pool_bwd_dx (ops.BnReluMaxPool2Fn.backward): dz = gamma * invstd * (dyhat - dbeta / M - xhat * dgamma / M), the
  *       convolution's dY, for all four pixels of every window.
+ *   gim_bn_stats_record (ops.bn_stats_record): one rank's share of the statistics in data-parallel training: record [2][C] = the mean
+ *       of the rank's M rows (M >= 1) and M2, the sum of squared deviations from that mean - stage 1 and the slab combine of
+ *       gim_bn_stats in the same order, not finished: neither invstd nor the running statistics are written.  One row gives the
+ *       row itself and M2 = 0 exactly.  partials as for gim_bn_stats.
+ *   gim_bn_stats_merge (ops.bn_stats_merge): records [R][2][C] (device, rank order) with the HOST array counts[R] of their row counts
+ *       (each >= 1, their sum M_total >= 2), R <= 64: one launch combines a channel's R triples in rank order with Chan's formula and
+ *       finishes as gim_bn_stats does over M_total rows (the same device function): mean, invstd, the running statistics with the
+ *       unbiased M2 / (M_total - 1), num_batches_tracked += 1.  R = 1 on a record of gim_bn_stats_record gives the bits of
+ *       gim_bn_stats; every rank that merges the same gathered records gets the same bits.
+ *   gim_bn_pool_bwd_dx_total (ops.BnReluMaxPool2Fn.backward with sync): gim_bn_pool_bwd_dx with dgamma / dbeta the sums over ALL
+ *       ranks and M_total (>= N * H * W) all ranks' pre-pool rows in place of M; the local sums come from gim_bn_pool_bwd_reduce.
  *   gim_absdiff_bwd (ops.AbsDiffFn.backward): da = sign(a - b) * d, db = -da, sign(0) = 0; n % 4 == 0.
  *   gim_logit_accuracy (baseline_training.SiameseTrainer.train_step): out[0] = share of the n logits with (logit >= 0) == (row < n_pos). */
 int gim_bn_slabs(int64_t rows);
@@ -510,6 +521,12 @@ int gim_bn_pool_bwd_reduce(const float* dp, const float* z, const float* gamma, 
                            int N, int H, int W, int C, void* stream);
 int gim_bn_pool_bwd_dx(const float* dp, const float* z, const float* gamma, const float* beta, const float* mean, const float* invstd,
                        const float* dgamma, const float* dbeta, float* dz, int N, int H, int W, int C, void* stream);
+int gim_bn_stats_record(const float* z, float* partials, float* record, int64_t M, int C, void* stream);
+int gim_bn_stats_merge(const float* records, const int64_t* counts, int R, int C, float* mean, float* invstd, float* running_mean,
+                       float* running_var, int64_t* num_batches_tracked, float momentum, float eps, void* stream);
+int gim_bn_pool_bwd_dx_total(const float* dp, const float* z, const float* gamma, const float* beta, const float* mean,
+                             const float* invstd, const float* dgamma, const float* dbeta, float* dz, int N, int H, int W, int C,
+                             int64_t M_total, void* stream);
 int gim_absdiff_bwd(const float* a, const float* b, const float* d, float* da, float* db, int64_t n, void* stream);
 int gim_logit_accuracy(const float* logits, int n_pos, int n, float* out, void* stream);
 
@@ -526,6 +543,8 @@ int gim_logit_accuracy(const float* logits, int n_pos, int n, float* out, void* 
  *       also dslope[c] = sum_{yhat <= 0} dy * yhat); acc_* (each may be NULL): the same sums are also ADDED there (a parameter's
  *       .grad in the optimizer's bucket).
  *   gim_bn_bwd_dx     : dz = gamma * invstd * (dyhat - dbeta / M - xhat * dgamma / M).
+ *   gim_bn_bwd_dx_total : the same for one rank of data-parallel training: z holds the rank's M rows, dgamma / dbeta are the sums
+ *       over ALL ranks and M_total (>= M) all ranks' rows, in place of M in the formula.
  *   gim_prelu_fwd / gim_prelu_bwd : y = x > 0 ? x : slope[c] * x (slopes of any sign; slope == NULL: ReLU); backward in one pass:
  *       dx = dy * (x > 0 ? 1 : slope[c]) (x == 0 takes the slope, as torch does) and dslope[c] = sum_{x <= 0} dy * x
  *       (partials / dslope / acc_dslope only with a slope).
@@ -551,6 +570,9 @@ int gim_bn_bwd_reduce(const float* dy, const float* z, const float* gamma, const
                       float* acc_dbeta, float* acc_dslope, int64_t M, int C, void* stream);
 int gim_bn_bwd_dx(const float* dy, const float* z, const float* gamma, const float* beta, const float* mean, const float* invstd,
                   const float* slope, const float* dgamma, const float* dbeta, float* dz, int64_t M, int C, void* stream);
+int gim_bn_bwd_dx_total(const float* dy, const float* z, const float* gamma, const float* beta, const float* mean, const float* invstd,
+                        const float* slope, const float* dgamma, const float* dbeta, float* dz, int64_t M, int64_t M_total, int C,
+                        void* stream);
 int gim_prelu_fwd(const float* x, const float* slope, float* y, int64_t M, int C, void* stream);
 int gim_prelu_bwd(const float* dy, const float* x, const float* slope, float* dx, float* partials, float* dslope, float* acc_dslope,
                   int64_t M, int C, void* stream);

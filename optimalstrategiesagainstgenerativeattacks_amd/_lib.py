@@ -138,11 +138,15 @@ SIGNATURES = {
     "gim_bn_relu_maxpool2_fwd": [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "gim_bn_pool_bwd_reduce": [P, P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "gim_bn_pool_bwd_dx": [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
+    "gim_bn_stats_record": [P, P, P, c_int64, c_int, P],
+    "gim_bn_stats_merge": [P, POINTER(c_int64), c_int, c_int, P, P, P, P, P, c_float, c_float, P],
+    "gim_bn_pool_bwd_dx_total": [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int64, P],
     "gim_absdiff_bwd": [P, P, P, P, P, c_int64, P],
     "gim_logit_accuracy": [P, c_int, c_int, P, P],
     "gim_bn_apply_fwd": [P, P, P, P, P, P, P, c_int64, c_int, P],
     "gim_bn_bwd_reduce": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int, P],
     "gim_bn_bwd_dx": [P, P, P, P, P, P, P, P, P, P, c_int64, c_int, P],
+    "gim_bn_bwd_dx_total": [P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int, P],
     "gim_prelu_fwd": [P, P, P, c_int64, c_int, P],
     "gim_prelu_bwd": [P, P, P, P, P, P, P, c_int64, c_int, P],
     "gim_se_tail_bwd": [P, P, P, P, P, c_int, c_int, c_int, c_int, P],

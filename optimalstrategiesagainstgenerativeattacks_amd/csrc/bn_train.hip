@@ -12,6 +12,10 @@
 // (the slab's first row), which gives the slab's (count, mean, M2) with a cancellation of the order (mean_slab - K)^2 / var_slab = O(1)
 // whatever the offset of the map; stage 2 combines the slabs' triples with Chan's formula.
 //
+// Data-parallel training: a rank keeps the combine's (mean, M2) of its rows as a record instead of finishing it (gim_bn_stats_record);
+// gim_bn_stats_merge combines the ranks' records in rank order with the same formula and the same finish, and the dz pass takes the
+// row count of all ranks (gim_bn_pool_bwd_dx_total) with all ranks' sums.
+//
 // The arg-max of a pooling window is RECOMPUTED in the backward from the four z values (the backward reads z anyway for xhat), not
 // stored by the forward.  The affine is applied to each of the four values before the maximum (gamma may be negative); ties go to the
 // first maximum in row-major window order, as torch.nn.MaxPool2d.
@@ -69,16 +73,15 @@ __device__ __forceinline__ void bn_combine(BnAcc& t, float nb, float pa, float p
         t.n = nn;
     }
 }
-__global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ partials, int n_slabs, long long rps, long long M, int C,
-                                                          float* __restrict__ mean, float* __restrict__ invstd,
-                                                          float* __restrict__ running_mean, float* __restrict__ running_var,
-                                                          long long* __restrict__ nbt, float momentum, float eps) {
-    __shared__ float red[3][BN_FG * BN_FC];
+// the combine of one channel's slabs in the order above; all 256 threads call it, the result is valid in the thread it returns true for
+// (group 0 of a channel < C)
+__device__ __forceinline__ bool bn_combine_slabs(const float* __restrict__ partials, int n_slabs, long long rps, long long M, int C,
+                                                 float (*red)[BN_FG * BN_FC], BnAcc& t) {
     const int ci = threadIdx.x % BN_FC, g = threadIdx.x / BN_FC;
     const int c = blockIdx.x * BN_FC + ci;
     const int per = (n_slabs + BN_FG - 1) / BN_FG;      // <= 16
     const int s0 = g * per;
-    BnAcc t = {0.f, 0.f, 0.f};
+    t = {0.f, 0.f, 0.f};
     if (c < C) {
         float pa[RS_MAX_SLABS / BN_FG], pb[RS_MAX_SLABS / BN_FG];
 #pragma unroll
@@ -109,9 +112,14 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
         red[2][g * BN_FC + ci] = t.b;
     }
     __syncthreads();
-    if (g != 0 || c >= C) return;
+    if (g != 0 || c >= C) return false;
     for (int k = 8; k < BN_FG; k += 8) bn_combine(t, red[0][k * BN_FC + ci], red[1][k * BN_FC + ci], red[2][k * BN_FC + ci]);
-    const float a = t.a, b = t.b;
+    return true;
+}
+// the finish of channel c from its (mean a, M2 b) over M rows: shared by the one-process statistics and the merge of several ranks'
+__device__ __forceinline__ void bn_finish(int c, float a, float b, long long M, float* __restrict__ mean, float* __restrict__ invstd,
+                                          float* __restrict__ running_mean, float* __restrict__ running_var,
+                                          long long* __restrict__ nbt, float momentum, float eps) {
     const float var = b / (float)M;
     mean[c] = a;
     invstd[c] = 1.0f / sqrtf(var + eps);
@@ -120,6 +128,44 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
         running_var[c] = (1.0f - momentum) * running_var[c] + momentum * (b / (float)(M - 1));
     }
     if (nbt && c == 0) *nbt += 1;
+}
+__global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ partials, int n_slabs, long long rps, long long M, int C,
+                                                          float* __restrict__ mean, float* __restrict__ invstd,
+                                                          float* __restrict__ running_mean, float* __restrict__ running_var,
+                                                          long long* __restrict__ nbt, float momentum, float eps) {
+    __shared__ float red[3][BN_FG * BN_FC];
+    BnAcc t;
+    if (!bn_combine_slabs(partials, n_slabs, rps, M, C, red, t)) return;
+    bn_finish(blockIdx.x * BN_FC + threadIdx.x % BN_FC, t.a, t.b, M, mean, invstd, running_mean, running_var, nbt, momentum, eps);
+}
+
+// ---------------------------------------------------------------- statistics of one rank among several (data-parallel training)
+// the same combine, kept as the rank's record [2][C] = (mean, M2 about that mean) of its M rows instead of being finished
+__global__ __launch_bounds__(256) void bn_record_kernel(const float* __restrict__ partials, int n_slabs, long long rps, long long M, int C,
+                                                        float* __restrict__ record) {
+    __shared__ float red[3][BN_FG * BN_FC];
+    BnAcc t;
+    if (!bn_combine_slabs(partials, n_slabs, rps, M, C, red, t)) return;
+    const int c = blockIdx.x * BN_FC + threadIdx.x % BN_FC;
+    record[c] = t.a;
+    record[C + c] = t.b;
+}
+// records [R][2][C] in rank order, n[r] rows each: one thread per channel combines the R triples in rank order (into an empty
+// accumulator the first combine is exact: R = 1 gives the bits of bn_finalize_kernel), then the finish over the total row count.
+// Every rank that merges the same records gets the same bits.
+constexpr int BN_MAX_RANKS = 64;
+struct BnCounts {
+    long long n[BN_MAX_RANKS];
+};
+__global__ __launch_bounds__(256) void bn_merge_kernel(const float* __restrict__ records, BnCounts counts, int R, long long M, int C,
+                                                       float* __restrict__ mean, float* __restrict__ invstd,
+                                                       float* __restrict__ running_mean, float* __restrict__ running_var,
+                                                       long long* __restrict__ nbt, float momentum, float eps) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    BnAcc t = {0.f, 0.f, 0.f};
+    for (int r = 0; r < R; ++r) bn_combine(t, (float)counts.n[r], records[(long long)(2 * r) * C + c], records[(long long)(2 * r + 1) * C + c]);
+    bn_finish(c, t.a, t.b, M, mean, invstd, running_mean, running_var, nbt, momentum, eps);
 }
 
 // ---------------------------------------------------------------- stage 2 of the plain sums: out[k][c] = sum over slabs
@@ -250,14 +296,15 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_slab_kernel(const float* __re
 }
 
 // ---------------------------------------------------------------- backward: dz = gamma * invstd * (dyhat - dbeta / M - xhat * dgamma / M)
+// M = m_total, the rows dgamma and dbeta were summed over: the map's own 4 Mp, or all ranks' rows with all ranks' sums
 __global__ __launch_bounds__(256) void bn_pool_bwd_dx_kernel(const float* __restrict__ dp, const float* __restrict__ z,
                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
                                                              const float* __restrict__ mean, const float* __restrict__ invstd,
                                                              const float* __restrict__ dgamma, const float* __restrict__ dbeta,
-                                                             float* __restrict__ dz, long long Mp, int Ho, int Wo, int C) {
+                                                             float* __restrict__ dz, long long Mp, int Ho, int Wo, int C, long long m_total) {
     const int C4 = C >> 2, W = Wo * 2;
     const long long n_out = Mp * C4, row = (long long)W * C;
-    const float inv_m = 1.0f / (float)(Mp * 4);
+    const float inv_m = 1.0f / (float)m_total;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_out; i += (long long)gridDim.x * 256) {
         const int c = (int)(i % C4) * 4;
         const BnChan p = bn_chan<false>(gamma, beta, mean, invstd, nullptr, c);
@@ -340,6 +387,40 @@ extern "C" int gim_bn_stats(const float* z, float* partials, float* mean, float*
     return gim_check_launch("gim_bn_stats");
 }
 
+extern "C" int gim_bn_stats_record(const float* z, float* partials, float* record, int64_t M, int C, void* stream) {
+    GIM_CHECK_ARG(M >= 1 && M < (1ll << 40) && C > 0 && C % 4 == 0 && C <= (1 << 18), "bn_stats_record: bad dims (M >= 1 rows, C % 4 == 0)");
+    GIM_CHECK_ARG(z && partials && record, "bn_stats_record: null pointer");
+    GIM_CHECK_ARG(aligned16(z), "bn_stats_record: z must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const long long rps = slab_rows(M);
+    const int ns = slab_count(M);
+    hipLaunchKernelGGL(bn_stats_slab_kernel, dim3((C + RS_CB - 1) / RS_CB, ns), dim3(256), 0, st, z, partials, (long long)M, C, rps);
+    hipLaunchKernelGGL(bn_record_kernel, dim3((C + BN_FC - 1) / BN_FC), dim3(256), 0, st, partials, ns, rps, (long long)M, C, record);
+    return gim_check_launch("gim_bn_stats_record");
+}
+
+extern "C" int gim_bn_stats_merge(const float* records, const int64_t* counts, int R, int C, float* mean, float* invstd,
+                                  float* running_mean, float* running_var, int64_t* num_batches_tracked, float momentum, float eps,
+                                  void* stream) {
+    GIM_CHECK_ARG(counts, "bn_stats_merge: null pointer (counts)");      // the sizes are checked before the device pointers
+    GIM_CHECK_ARG(R >= 1 && R <= BN_MAX_RANKS, "bn_stats_merge: 1 <= R <= 64 records");
+    GIM_CHECK_ARG(C > 0 && C % 4 == 0 && C <= (1 << 18), "bn_stats_merge: bad dims (C % 4 == 0)");
+    GIM_CHECK_ARG(!running_mean == !running_var, "bn_stats_merge: running_mean and running_var are given together or not at all");
+    GIM_CHECK_ARG(momentum >= 0.f && momentum <= 1.f && eps >= 0.f, "bn_stats_merge: momentum in [0, 1], eps >= 0");
+    BnCounts n = {};
+    long long total = 0;
+    for (int r = 0; r < R; ++r) {
+        GIM_CHECK_ARG(counts[r] >= 1 && counts[r] < (1ll << 40), "bn_stats_merge: every rank's row count must be at least 1");
+        n.n[r] = counts[r];
+        total += counts[r];
+    }
+    GIM_CHECK_ARG(total >= 2 && total < (1ll << 40), "bn_stats_merge: batch statistics need at least two rows in all");
+    GIM_CHECK_ARG(records && mean && invstd, "bn_stats_merge: null pointer");
+    hipLaunchKernelGGL(bn_merge_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, records, n, R, total, C, mean, invstd,
+                       running_mean, running_var, (long long*)num_batches_tracked, momentum, eps);
+    return gim_check_launch("gim_bn_stats_merge");
+}
+
 extern "C" int gim_bn_relu_maxpool2_fwd(const float* z, const float* gamma, const float* beta, const float* mean, const float* invstd,
                                         float* p, int N, int H, int W, int C, void* stream) {
     GIM_CHECK_ARG(z && gamma && beta && mean && invstd && p, "bn_relu_maxpool2_fwd: null pointer");
@@ -369,9 +450,9 @@ extern "C" int gim_bn_pool_bwd_reduce(const float* dp, const float* z, const flo
     return gim_check_launch("gim_bn_pool_bwd_reduce");
 }
 
-extern "C" int gim_bn_pool_bwd_dx(const float* dp, const float* z, const float* gamma, const float* beta, const float* mean,
-                                  const float* invstd, const float* dgamma, const float* dbeta, float* dz, int N, int H, int W, int C,
-                                  void* stream) {
+static int bn_pool_bwd_dx(const char* name, const float* dp, const float* z, const float* gamma, const float* beta, const float* mean,
+                          const float* invstd, const float* dgamma, const float* dbeta, float* dz, int N, int H, int W, int C,
+                          long long m_total, void* stream) {
     GIM_CHECK_ARG(dp && z && gamma && beta && mean && invstd && dgamma && dbeta && dz, "bn_pool_bwd_dx: null pointer");
     if (bn_check_map("bn_pool_bwd_dx: bad dims (H, W even, C % 4 == 0)", N, H, W, C)) return GIM_E_BADARG;
     GIM_CHECK_ARG(aligned16(dp) && aligned16(z) && aligned16(gamma) && aligned16(beta) && aligned16(mean) && aligned16(invstd) &&
@@ -379,8 +460,24 @@ extern "C" int gim_bn_pool_bwd_dx(const float* dp, const float* z, const float* 
                   "bn_pool_bwd_dx: pointers must be 16-byte aligned");
     const long long Mp = (long long)N * (H / 2) * (W / 2);
     hipLaunchKernelGGL(bn_pool_bwd_dx_kernel, dim3(blocks256(Mp * (C / 4))), dim3(256), 0, (hipStream_t)stream, dp, z, gamma, beta, mean, invstd,
-                       dgamma, dbeta, dz, Mp, H / 2, W / 2, C);
-    return gim_check_launch("gim_bn_pool_bwd_dx");
+                       dgamma, dbeta, dz, Mp, H / 2, W / 2, C, m_total);
+    return gim_check_launch(name);
+}
+
+extern "C" int gim_bn_pool_bwd_dx(const float* dp, const float* z, const float* gamma, const float* beta, const float* mean,
+                                  const float* invstd, const float* dgamma, const float* dbeta, float* dz, int N, int H, int W, int C,
+                                  void* stream) {
+    return bn_pool_bwd_dx("gim_bn_pool_bwd_dx", dp, z, gamma, beta, mean, invstd, dgamma, dbeta, dz, N, H, W, C,
+                          4ll * N * (H / 2) * (W / 2), stream);      // (bad dims are refused before the count is read)
+}
+
+extern "C" int gim_bn_pool_bwd_dx_total(const float* dp, const float* z, const float* gamma, const float* beta, const float* mean,
+                                        const float* invstd, const float* dgamma, const float* dbeta, float* dz, int N, int H, int W,
+                                        int C, int64_t M_total, void* stream) {
+    GIM_CHECK_ARG(M_total >= 4ll * N * (H / 2) * (W / 2) && M_total < (1ll << 40),
+                  "bn_pool_bwd_dx_total: M_total must be at least the map's own N * H * W rows");
+    return bn_pool_bwd_dx("gim_bn_pool_bwd_dx_total", dp, z, gamma, beta, mean, invstd, dgamma, dbeta, dz, N, H, W, C, (long long)M_total,
+                          stream);
 }
 
 extern "C" int gim_absdiff_bwd(const float* a, const float* b, const float* d, float* da, float* db, int64_t n, void* stream) {

@@ -407,22 +407,35 @@ extern "C" int gim_bn_bwd_reduce(const float* dy, const float* z, const float* g
     return gim_check_launch("gim_bn_bwd_reduce");
 }
 
-extern "C" int gim_bn_bwd_dx(const float* dy, const float* z, const float* gamma, const float* beta, const float* mean, const float* invstd,
-                             const float* slope, const float* dgamma, const float* dbeta, float* dz, int64_t M, int C, void* stream) {
+static int bn_bwd_dx(const char* name, const float* dy, const float* z, const float* gamma, const float* beta, const float* mean,
+                     const float* invstd, const float* slope, const float* dgamma, const float* dbeta, float* dz, int64_t M, int C,
+                     int64_t M_total, void* stream) {
     GIM_CHECK_ARG(dy && z && gamma && beta && mean && invstd && dgamma && dbeta && dz, "bn_bwd_dx: null pointer");
     if (ir_check_rows("bn_bwd_dx: bad dims (M > 0 rows, C % 4 == 0)", M, C)) return GIM_E_BADARG;
     GIM_CHECK_ARG(aligned16(dy) && aligned16(z) && aligned16(gamma) && aligned16(beta) && aligned16(mean) && aligned16(invstd) &&
                       aligned16(slope) && aligned16(dgamma) && aligned16(dbeta) && aligned16(dz),
                   "bn_bwd_dx: pointers must be 16-byte aligned");
     const long long n4 = (long long)M * (C / 4);
-    const float inv_m = 1.0f / (float)M;
+    const float inv_m = 1.0f / (float)M_total;
     if (slope)
         hipLaunchKernelGGL(bn_bwd_dx_kernel<true>, dim3(blocks256(n4)), dim3(256), 0, (hipStream_t)stream, dy, z, gamma, beta, mean, invstd,
                            slope, dgamma, dbeta, dz, n4, C / 4, inv_m);
     else
         hipLaunchKernelGGL(bn_bwd_dx_kernel<false>, dim3(blocks256(n4)), dim3(256), 0, (hipStream_t)stream, dy, z, gamma, beta, mean, invstd,
                            slope, dgamma, dbeta, dz, n4, C / 4, inv_m);
-    return gim_check_launch("gim_bn_bwd_dx");
+    return gim_check_launch(name);
+}
+
+extern "C" int gim_bn_bwd_dx(const float* dy, const float* z, const float* gamma, const float* beta, const float* mean, const float* invstd,
+                             const float* slope, const float* dgamma, const float* dbeta, float* dz, int64_t M, int C, void* stream) {
+    return bn_bwd_dx("gim_bn_bwd_dx", dy, z, gamma, beta, mean, invstd, slope, dgamma, dbeta, dz, M, C, M, stream);
+}
+
+extern "C" int gim_bn_bwd_dx_total(const float* dy, const float* z, const float* gamma, const float* beta, const float* mean,
+                                   const float* invstd, const float* slope, const float* dgamma, const float* dbeta, float* dz, int64_t M,
+                                   int64_t M_total, int C, void* stream) {
+    GIM_CHECK_ARG(M_total >= M && M_total < (1ll << 40), "bn_bwd_dx_total: M_total must be at least the M rows of z");
+    return bn_bwd_dx("gim_bn_bwd_dx_total", dy, z, gamma, beta, mean, invstd, slope, dgamma, dbeta, dz, M, C, M_total, stream);
 }
 
 extern "C" int gim_prelu_fwd(const float* x, const float* slope, float* y, int64_t M, int C, void* stream) {

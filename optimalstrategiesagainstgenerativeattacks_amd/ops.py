@@ -2287,6 +2287,17 @@ def _req_rows(x, what):
     return x, x.numel() // C, C
 
 
+def _req_running(what, C, running_mean, running_var, num_batches_tracked, momentum):
+    if momentum is None:
+        raise NotImplementedError("%s: momentum=None (cumulative moving average) is not implemented" % what)
+    for name, v in (("running_mean", running_mean), ("running_var", running_var)):
+        if v is not None and (tuple(_req(v, name).shape) != (C,) or not v.is_contiguous()):
+            raise RuntimeError("%s: %s must be a contiguous [C] tensor" % (what, name))
+    if num_batches_tracked is not None and not (num_batches_tracked.is_cuda and num_batches_tracked.dtype == torch.int64):
+        raise RuntimeError("%s: num_batches_tracked must be a CUDA int64 tensor" % what)
+    return None if num_batches_tracked is None else num_batches_tracked.data_ptr()
+
+
 def bn_stats(z, eps=1e-5, running_mean=None, running_var=None, num_batches_tracked=None, momentum=0.1):
     """(mean [C], invstd [C]) over the M >= 2 rows of any [..., C] tensor with C % 4 == 0 (an NHWC map of any size, [B, C] of a
     BatchNorm1d): the biased variance, as nn.BatchNorm normalises in training mode; with running_mean / running_var /
@@ -2295,19 +2306,129 @@ def bn_stats(z, eps=1e-5, running_mean=None, running_var=None, num_batches_track
     z, M, C = _req_rows(z, "z")
     if M < 2:
         raise RuntimeError("batch statistics need at least two rows, got %s" % (tuple(z.shape),))
-    if momentum is None:
-        raise NotImplementedError("bn_stats: momentum=None (cumulative moving average) is not implemented")
-    for name, v in (("running_mean", running_mean), ("running_var", running_var)):
-        if v is not None and (tuple(_req(v, name).shape) != (C,) or not v.is_contiguous()):
-            raise RuntimeError("bn_stats: %s must be a contiguous [C] tensor" % name)
-    if num_batches_tracked is not None and not (num_batches_tracked.is_cuda and num_batches_tracked.dtype == torch.int64):
-        raise RuntimeError("bn_stats: num_batches_tracked must be a CUDA int64 tensor")
+    nbt = _req_running("bn_stats", C, running_mean, running_var, num_batches_tracked, momentum)
     stats = torch.empty((2, C), device=z.device, dtype=torch.float32)
     partials = _slab_partials(M, C, 2, z.device)      # (mean, M2) per slab and channel
-    nbt = None if num_batches_tracked is None else num_batches_tracked.data_ptr()
     check(lib.gim_bn_stats(_p(z), _p(partials), _p(stats), _p(stats, C), _p(running_mean), _p(running_var), nbt, M, C,
                            float(momentum), float(eps), _stream()), "bn_stats")
     return stats[0], stats[1]
+
+
+# Data-parallel training: BatchNorm is the one operator of the baselines that couples the images of a batch.  A rank computes the
+# record of its rows (bn_stats_record), the ranks' records are gathered and every rank merges them in rank order (bn_stats_merge):
+# the same bits everywhere, so the replicas' running statistics stay equal without a broadcast.  In the backward the two per-channel
+# sums that enter dz are all-reduced and dz takes 1 / (all ranks' rows); the PARAMETER gradients stay the local sums - the optimizer's
+# bucket is all-reduced once more in FusedAdam.step.
+BN_MAX_RANKS = 64      # the merge kernel's limit (csrc/bn_train.hip)
+
+
+def bn_stats_record(z):
+    """One rank's share of the batch statistics: [2, C] = (mean, M2 = sum of squared deviations from that mean) over the M >= 1 rows
+    of z [..., C], C % 4 == 0."""
+    z, M, C = _req_rows(z, "z")
+    record = torch.empty((2, C), device=z.device, dtype=torch.float32)
+    partials = _slab_partials(M, C, 2, z.device)
+    check(_lib.load().gim_bn_stats_record(_p(z), _p(partials), _p(record), M, C, _stream()), "bn_stats_record")
+    return record
+
+
+def bn_stats_merge(records, counts, eps, running_mean=None, running_var=None, num_batches_tracked=None, momentum=0.1):
+    """(mean [C], invstd [C]) of the rows behind records [R, 2, C] (bn_stats_record of R <= 64 ranks, in rank order; counts: their
+    row counts, host integers >= 1 that sum to >= 2), combined in rank order with Chan's formula and finished as bn_stats finishes:
+    the running statistics move with the unbiased variance over all rows.  R = 1 gives the bits of bn_stats."""
+    records = _req(records, "records")
+    if records.dim() != 3 or records.shape[1] != 2 or records.shape[2] % 4:
+        raise RuntimeError("bn_stats_merge: records must be [R, 2, C] with C %% 4 == 0, got %s" % (tuple(records.shape),))
+    R, _, C = records.shape
+    counts = [int(n) for n in counts]
+    if len(counts) != R:
+        raise RuntimeError("bn_stats_merge: %d records but %d row counts" % (R, len(counts)))
+    nbt = _req_running("bn_stats_merge", C, running_mean, running_var, num_batches_tracked, momentum)
+    stats = torch.empty((2, C), device=records.device, dtype=torch.float32)
+    check(_lib.load().gim_bn_stats_merge(_p(records), (ctypes.c_int64 * R)(*counts), R, C, _p(stats), _p(stats, C), _p(running_mean),
+                                         _p(running_var), nbt, float(momentum), float(eps), _stream()), "bn_stats_merge")
+    return stats[0], stats[1]
+
+
+class DistSync:
+    """The `sync` of batch_norm / bn_relu_maxpool2 over torch.distributed (group: a process group, None for the default one).
+    What a sync is: `rank`, `world`, all_gather(t) -> [world, *t.shape] in rank order, all_reduce_(t) (sum, in place)."""
+
+    def __init__(self, group=None):
+        import torch.distributed as dist
+        self._dist, self.group = dist, group
+        self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
+
+    def all_gather(self, t):
+        out = torch.empty((self.world,) + tuple(t.shape), device=t.device, dtype=t.dtype)
+        self._dist.all_gather(list(out.unbind(0)), t, group=self.group)
+        return out
+
+    def all_reduce_(self, t):
+        self._dist.all_reduce(t, op=self._dist.ReduceOp.SUM, group=self.group)
+        return t
+
+
+def default_sync():
+    """A DistSync when torch.distributed is initialised with more than one rank, else None (the single-process path)."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        return DistSync()
+    return None
+
+
+def _synced(sync):
+    return sync is not None and sync.world > 1
+
+
+def _batch_stats(z, sync, eps, running_mean, running_var, num_batches_tracked, momentum):
+    """(mean, invstd) of the whole batch, of which z is this rank's equal share; without a sync z is the whole batch (bn_stats)."""
+    if not _synced(sync):
+        return bn_stats(z, eps, running_mean, running_var, num_batches_tracked, momentum)
+    if sync.world > BN_MAX_RANKS:
+        raise RuntimeError("batch statistics are merged over at most %d ranks, got %d" % (BN_MAX_RANKS, sync.world))
+    rows = z.numel() // z.shape[-1]
+    records = sync.all_gather(bn_stats_record(z))
+    return bn_stats_merge(records, [rows] * sync.world, eps, running_mean, running_var, num_batches_tracked, momentum)
+
+
+def _total_sums(sums, sync):
+    """The (dgamma, dbeta) that enter dz: all ranks' sums.  `sums` itself stays local - it is what the parameters receive."""
+    return sync.all_reduce_(sums[:2].clone()) if _synced(sync) else sums
+
+
+def bn_pool_fwd(z, weight, bias, mean, invstd):
+    """maxpool2(relu((z - mean) * invstd * weight + bias)) of an NHWC map with GIVEN statistics; no autograd."""
+    N, H, W, C = z.shape
+    p = torch.empty((N, H // 2, W // 2, C), device=z.device, dtype=torch.float32)
+    check(_lib.load().gim_bn_relu_maxpool2_fwd(_p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(p), N, H, W, C, _stream()),
+          "bn_relu_maxpool2_fwd")
+    return p
+
+
+def bn_pool_bwd_sums(dp, z, weight, bias, mean, invstd, acc=(None, None), out=None):
+    """[2, C] = (dgamma, dbeta) of bn_pool_fwd over THIS map's rows (written to `out` where given); acc: (weight.grad, bias.grad)
+    buffers the sums are also ADDED to."""
+    N, H, W, C = z.shape
+    sums = torch.empty((2, C), device=z.device, dtype=torch.float32) if out is None else out
+    partials = _slab_partials(N * (H // 2) * (W // 2), C, 2, z.device)
+    check(_lib.load().gim_bn_pool_bwd_reduce(_p(dp), _p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(partials), _p(sums),
+                                             _p(sums, C), _p(acc[0]), _p(acc[1]), N, H, W, C, _stream()), "bn_pool_bwd_reduce")
+    return sums
+
+
+def bn_pool_bwd_dx(dp, z, weight, bias, mean, invstd, sums, total_rows=None):
+    """dz of bn_pool_fwd from sums = (dgamma, dbeta).  total_rows: the pre-pool rows of ALL ranks when sums are all ranks' totals
+    (None: this map's own N * H * W rows)."""
+    lib = _lib.load()
+    N, H, W, C = z.shape
+    dz = torch.empty_like(z)
+    args = (_p(dp), _p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(sums), _p(sums, C), _p(dz), N, H, W, C)
+    if total_rows is None:
+        check(lib.gim_bn_pool_bwd_dx(*args, _stream()), "bn_pool_bwd_dx")
+    else:
+        check(lib.gim_bn_pool_bwd_dx_total(*args, int(total_rows), _stream()), "bn_pool_bwd_dx_total")
+    return dz
 
 
 class BnReluMaxPool2Fn(Function):
@@ -2317,46 +2438,39 @@ class BnReluMaxPool2Fn(Function):
     is the optimizer's bucket (then None goes back to autograd), as the convolutions' weight gradients are."""
 
     @staticmethod
-    def forward(ctx, z, weight, bias, running_mean, running_var, num_batches_tracked, momentum, eps):
-        lib = _lib.load()
+    def forward(ctx, z, weight, bias, running_mean, running_var, num_batches_tracked, momentum, eps, sync=None):
         z = _req_map(z, "z")
-        N, H, W, C = z.shape
+        C = z.shape[3]
         weight, bias = _req(weight, "weight"), _req(bias, "bias")
         if tuple(weight.shape) != (C,) or tuple(bias.shape) != (C,):
             raise RuntimeError("bn_relu_maxpool2: weight and bias must be [C = %d]" % C)
-        mean, invstd = bn_stats(z, eps, running_mean, running_var, num_batches_tracked, momentum)
-        p = torch.empty((N, H // 2, W // 2, C), device=z.device, dtype=torch.float32)
-        check(lib.gim_bn_relu_maxpool2_fwd(_p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(p), N, H, W, C, _stream()),
-              "bn_relu_maxpool2_fwd")
+        mean, invstd = _batch_stats(z, sync, eps, running_mean, running_var, num_batches_tracked, momentum)
+        p = bn_pool_fwd(z, weight, bias, mean, invstd)
         ctx.save_for_backward(z, weight, bias, mean, invstd)
+        ctx.sync = sync
         return p
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dp):
-        lib = _lib.load()
         z, weight, bias, mean, invstd = ctx.saved_tensors
-        N, H, W, C = z.shape
         dp = _req(dp, "dp")
-        st = _stream()
-        sums = torch.empty((2, C), device=z.device, dtype=torch.float32)      # dgamma, dbeta
-        partials = _slab_partials(N * (H // 2) * (W // 2), C, 2, z.device)
         need = ctx.needs_input_grad
-        (acc_w, acc_b), (dw, db) = _channel_grads(need[1:3], (weight, bias), sums)
-        check(lib.gim_bn_pool_bwd_reduce(_p(dp), _p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(partials), _p(sums), _p(sums, C),
-                                         _p(acc_w), _p(acc_b), N, H, W, C, st), "bn_pool_bwd_reduce")
+        sums = torch.empty((2, z.shape[3]), device=z.device, dtype=torch.float32)      # dgamma, dbeta of this rank's rows
+        acc, (dw, db) = _channel_grads(need[1:3], (weight, bias), sums)
+        bn_pool_bwd_sums(dp, z, weight, bias, mean, invstd, acc, sums)
         dz = None
         if need[0]:
-            dz = torch.empty_like(z)
-            check(lib.gim_bn_pool_bwd_dx(_p(dp), _p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(sums), _p(sums, C), _p(dz),
-                                         N, H, W, C, st), "bn_pool_bwd_dx")
-        return dz, dw, db, None, None, None, None, None
+            total = z.numel() // z.shape[3] * ctx.sync.world if _synced(ctx.sync) else None
+            dz = bn_pool_bwd_dx(dp, z, weight, bias, mean, invstd, _total_sums(sums, ctx.sync), total)
+        return dz, dw, db, None, None, None, None, None, None
 
 
-def bn_relu_maxpool2(z, weight, bias, running_mean, running_var, num_batches_tracked, momentum=0.1, eps=1e-5):
+def bn_relu_maxpool2(z, weight, bias, running_mean, running_var, num_batches_tracked, momentum=0.1, eps=1e-5, sync=None):
     """maxpool2(relu(batch_norm(z, batch statistics))) of an NHWC map -> [N, H/2, W/2, C]; differentiable in z, weight and bias
-    (once); the running statistics and num_batches_tracked move as nn.BatchNorm2d's do in training mode."""
-    return BnReluMaxPool2Fn.apply(z, weight, bias, running_mean, running_var, num_batches_tracked, momentum, eps)
+    (once); the running statistics and num_batches_tracked move as nn.BatchNorm2d's do in training mode.  sync (see DistSync): z is
+    this rank's equal share of the batch, the statistics and dz are the whole batch's; None or world == 1: one process."""
+    return BnReluMaxPool2Fn.apply(z, weight, bias, running_mean, running_var, num_batches_tracked, momentum, eps, sync)
 
 
 class AbsDiffFn(Function):
@@ -2426,51 +2540,82 @@ def _req_label(label, B):
     return label if label.is_contiguous() else label.contiguous()
 
 
+def bn_apply(z, weight, bias, mean, invstd, slope=None):
+    """(z - mean) * invstd * weight + bias over the rows of z [..., C] with GIVEN statistics, then prelu(., slope); no autograd."""
+    y = torch.empty_like(z)
+    C = z.shape[-1]
+    check(_lib.load().gim_bn_apply_fwd(_p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(slope), _p(y), z.numel() // C, C, _stream()),
+          "bn_apply_fwd")
+    return y
+
+
+def bn_bwd_sums(dy, z, weight, bias, mean, invstd, slope=None, acc=(None, None, None), out=None):
+    """[3, C] = (dgamma, dbeta, dslope) of bn_apply over THIS tensor's rows (written to `out` where given; the dslope row only with a
+    slope); acc: (weight.grad, bias.grad, slope.grad) buffers the sums are also ADDED to."""
+    C = z.shape[-1]
+    M = z.numel() // C
+    sums = torch.empty((3, C), device=z.device, dtype=torch.float32) if out is None else out
+    partials = _slab_partials(M, C, 3, z.device)
+    check(_lib.load().gim_bn_bwd_reduce(_p(dy), _p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(slope), _p(partials), _p(sums),
+                                        _p(sums, C), _p(sums, 2 * C) if slope is not None else None, _p(acc[0]), _p(acc[1]), _p(acc[2]),
+                                        M, C, _stream()), "bn_bwd_reduce")
+    return sums
+
+
+def bn_bwd_dx(dy, z, weight, bias, mean, invstd, slope, sums, total_rows=None):
+    """dz of bn_apply from sums = (dgamma, dbeta).  total_rows: the rows of ALL ranks when sums are all ranks' totals (None: this
+    tensor's own rows)."""
+    lib = _lib.load()
+    C = z.shape[-1]
+    M = z.numel() // C
+    dz = torch.empty_like(z)
+    args = (_p(dy), _p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(slope), _p(sums), _p(sums, C), _p(dz), M)
+    if total_rows is None:
+        check(lib.gim_bn_bwd_dx(*args, C, _stream()), "bn_bwd_dx")
+    else:
+        check(lib.gim_bn_bwd_dx_total(*args, int(total_rows), C, _stream()), "bn_bwd_dx_total")
+    return dz
+
+
 class BatchNormFn(Function):
     """y = batch_norm(z) with BATCH statistics over the rows of z [..., C] (nn.BatchNorm2d on an NHWC map, nn.BatchNorm1d on [B, C]
     in training mode), the running statistics updated in place; slope: the per-channel PReLU behind it, in the same pass.  Saved
     for backward: z and the two [C] statistics, not the normalised map."""
 
     @staticmethod
-    def forward(ctx, z, weight, bias, slope, running_mean, running_var, num_batches_tracked, momentum, eps):
-        lib = _lib.load()
+    def forward(ctx, z, weight, bias, slope, running_mean, running_var, num_batches_tracked, momentum, eps, sync=None):
         z, M, C = _req_rows(z, "z")
         weight, bias = _req_chan(weight, "weight", C), _req_chan(bias, "bias", C)
         slope = None if slope is None else _req_chan(slope, "slope", C)
-        mean, invstd = bn_stats(z, eps, running_mean, running_var, num_batches_tracked, momentum)
-        y = torch.empty_like(z)
-        check(lib.gim_bn_apply_fwd(_p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(slope), _p(y), M, C, _stream()), "bn_apply_fwd")
+        mean, invstd = _batch_stats(z, sync, eps, running_mean, running_var, num_batches_tracked, momentum)
+        y = bn_apply(z, weight, bias, mean, invstd, slope)
         ctx.save_for_backward(z, weight, bias, mean, invstd, slope)
+        ctx.sync = sync
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
-        lib = _lib.load()
         z, weight, bias, mean, invstd, slope = ctx.saved_tensors
         C = z.shape[-1]
-        M = z.numel() // C
         dy = _req(dy, "dy")
-        st = _stream()
-        sums = torch.empty((3, C), device=z.device, dtype=torch.float32)      # dgamma, dbeta, dslope
-        partials = _slab_partials(M, C, 3, z.device)
+        sums = torch.empty((3, C), device=z.device, dtype=torch.float32)      # dgamma, dbeta, dslope of this rank's rows
         need = ctx.needs_input_grad
-        (acc_w, acc_b, acc_s), (dw, db, ds) = _channel_grads(need[1:4], (weight, bias, slope), sums)
-        check(lib.gim_bn_bwd_reduce(_p(dy), _p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(slope), _p(partials), _p(sums),
-                                    _p(sums, C), _p(sums, 2 * C) if slope is not None else None, _p(acc_w), _p(acc_b), _p(acc_s), M, C, st),
-              "bn_bwd_reduce")
+        acc, (dw, db, ds) = _channel_grads(need[1:4], (weight, bias, slope), sums)
+        bn_bwd_sums(dy, z, weight, bias, mean, invstd, slope, acc, sums)
         dz = None
         if need[0]:
-            dz = torch.empty_like(z)
-            check(lib.gim_bn_bwd_dx(_p(dy), _p(z), _p(weight), _p(bias), _p(mean), _p(invstd), _p(slope), _p(sums), _p(sums, C), _p(dz),
-                                    M, C, st), "bn_bwd_dx")
-        return dz, dw, db, ds, None, None, None, None, None
+            total = z.numel() // C * ctx.sync.world if _synced(ctx.sync) else None
+            dz = bn_bwd_dx(dy, z, weight, bias, mean, invstd, slope, _total_sums(sums, ctx.sync), total)
+        return dz, dw, db, ds, None, None, None, None, None, None
 
 
-def batch_norm(z, weight, bias, running_mean, running_var, num_batches_tracked, momentum=0.1, eps=1e-5, slope=None):
+def batch_norm(z, weight, bias, running_mean, running_var, num_batches_tracked, momentum=0.1, eps=1e-5, slope=None, sync=None):
     """batch_norm(z, batch statistics) over the rows of z [..., C], optionally followed by prelu(., slope); differentiable in z, weight,
-    bias and slope (once); the running statistics and num_batches_tracked move as nn.BatchNorm's do in training mode."""
-    return BatchNormFn.apply(z, weight, bias, slope, running_mean, running_var, num_batches_tracked, momentum, eps)
+    bias and slope (once); the running statistics and num_batches_tracked move as nn.BatchNorm's do in training mode.  sync (see
+    DistSync): z is this rank's equal share of the batch (one row is enough), the statistics and dz are the whole batch's; None or
+    world == 1: one process."""
+    return BatchNormFn.apply(z, weight, bias, slope, running_mean, running_var, num_batches_tracked, momentum, eps, sync)
 
 
 class PReLUFn(Function):
