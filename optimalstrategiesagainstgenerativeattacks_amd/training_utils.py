@@ -78,10 +78,15 @@ class EpisodeParallel(DataParallelMock):
         return out[0] if len(out) == 1 else tuple(out)
 
     def broadcast_parameters(self):
-        """Make every rank start from rank 0's parameters and buffers."""
+        """Make every rank continue from rank 0's parameters and buffers.  Each tensor is received into a detached copy (same
+        memory layout) and copied in under no_grad: a write through ``t.data`` would not advance ``t._version``, and the
+        re-laid-out weight copies of ops._WT_CACHE made by an earlier forward pass would then pass for current."""
         if self.world_size > 1:
-            for t in list(self.module.parameters()) + list(self.module.buffers()):
-                dist.broadcast(t.data, src=0)
+            with torch.no_grad():
+                for t in list(self.module.parameters()) + list(self.module.buffers()):
+                    buf = t.detach().clone()
+                    dist.broadcast(buf, src=0)
+                    t.copy_(buf)
 
 
 def pin_rank_to_cores(local_rank=None, local_world=None):

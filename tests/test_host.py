@@ -175,6 +175,51 @@ def test_episode_data_parallel_equals_big_batch_gloo():
     assert relerr(bufs[0], au["src_encoder.down_blocks.0.conv_r1.weight_u"]) < 1e-12
 
 
+def _broadcast_worker(rank, world, port, q):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    sys.path.insert(0, ROOT)
+    from optimalstrategiesagainstgenerativeattacks_amd.training_utils import EpisodeParallel
+    torch.manual_seed(100 + rank)      # the ranks start from DIFFERENT values
+    mod = torch.nn.Module()
+    mod.weight = torch.nn.Parameter(torch.randn(6, 3, 3, 3).contiguous(memory_format=torch.channels_last))    # a conv weight as the engine stores it
+    mod.bias = torch.nn.Parameter(torch.randn(6))
+    mod.register_buffer("weight_u", torch.randn(6))
+    tensors = dict(mod.named_parameters(), **dict(mod.named_buffers()))
+    before = {k: t._version for k, t in tensors.items()}
+    strides = {k: t.stride() for k, t in tensors.items()}
+    EpisodeParallel(mod).broadcast_parameters()
+    q.put((rank, {k: t.detach().clone() for k, t in tensors.items()}, before, {k: t._version for k, t in tensors.items()},
+           all(t.stride() == strides[k] and t.requires_grad == (k != "weight_u") for k, t in tensors.items())))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_broadcast_parameters_advances_version_counters_gloo():
+    """EpisodeParallel.broadcast_parameters over 2 gloo ranks: both ranks end with rank 0's values, and every parameter's and
+    buffer's _version has advanced on BOTH ranks - what the derived-weight cache (ops._WT_CACHE) keys on, so a broadcast behind
+    a forward pass cannot leave re-laid-out copies of the old weights in use (a write through .data would: it is invisible)."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = 31500 + (os.getpid() % 2000)
+    procs = [ctx.Process(target=_broadcast_worker, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    got = dict((r[0], r[1:]) for r in (q.get(timeout=300), q.get(timeout=300)))
+    for p in procs:
+        p.join(timeout=300)
+        assert p.exitcode == 0
+    torch.manual_seed(100)
+    w0 = torch.randn(6, 3, 3, 3)
+    b0, u0 = torch.randn(6), torch.randn(6)
+    for rank in (0, 1):
+        vals, before, after, layout_kept = got[rank]
+        assert torch.equal(vals["weight"], w0) and torch.equal(vals["bias"], b0) and torch.equal(vals["weight_u"], u0), rank
+        for k in vals:
+            assert after[k] > before[k], (rank, k, before[k], after[k])
+        assert layout_kept, rank
+
+
 def test_logger_mirror_and_training_loop_cadence(tmp_path):
     """The caller loop of training/gim_img_training.py:186-354 on a stub trainer (no GPU): n_au_steps gating of the generator
     step, log / save / eval cadences keyed on global_step, one device->host fetch per log point, Logger round trip."""
