@@ -1,6 +1,7 @@
 """The optimisation-step protocol of the reference's ``training/gim_img_training.py``
 (im_eval_step :76, au_eval_step :85, im_train_step :157, au_train_step :169) on the MI355X engine, plus a fused
 convenience ``gim_step`` (= im_train_step then au_train_step, as train_epoch does at :225-239)."""
+import contextlib
 import itertools
 import os
 
@@ -17,25 +18,87 @@ from .training_utils import DataParallelMock, EpisodeParallel, adjust_batch_size
 _OVERLAP = os.environ.get("GIM_NO_STEP_OVERLAP") is None  # A/B switch
 
 
-def im_eval_step(trainer, leaked_sample, si_sample, z=None):
+def _micro_batches(micro_batches, *tensors):
+    """The checked number A of micro-batches of a step on these [B, ...] tensors (None entries are skipped).  ValueError for
+    anything but an integer >= 1 that divides B - raised before the step touches the GPU."""
+    A = micro_batches
+    if isinstance(A, bool) or not isinstance(A, int):
+        raise ValueError("micro_batches must be an integer >= 1, got %r" % (A,))
+    if A < 1:
+        raise ValueError("micro_batches must be >= 1, got %d" % A)
+    for t in tensors:
+        if t is not None and t.size(0) % A != 0:
+            raise ValueError("a local batch of %d episodes cannot be cut into %d equal micro-batches" % (t.size(0), A))
+    return A
+
+
+def _micro_batch(sn, j, A, *tensors):
+    """(context, slices) of micro-batch j of A: equal slices along dim 0, cut the way EpisodeParallel.shard cuts ranks, each a
+    leaf of its own.  A == 1: the tensors themselves and a context that does nothing - the plain step.  Otherwise the context
+    is sn's (mb.SNReplay): micro-batch 0 runs the spectral-norm power iterations, the others take its results."""
+    if A == 1:
+        return contextlib.nullcontext(), tensors
+    out = []
+    for t in tensors:
+        per = None if t is None else t.size(0) // A
+        out.append(None if t is None else t[j * per:(j + 1) * per].detach())
+    return sn.micro_batch(j), tuple(out)
+
+
+def _whole_batch_z(trainer, A, leaked_sample, z):
+    """The latent noise of an accumulated generator pass that was given none: drawn here for the WHOLE batch, by the call the
+    impersonator's forward makes, so that the slices see - and the generator consumes - the random numbers of the whole-batch step."""
+    if A == 1 or z is not None:
+        return z
+    mod = trainer.module
+    return torch.randn((leaked_sample.size(0), mod.n, mod.impersonator.style_dim), device=leaked_sample.device)
+
+
+def _merged(outs, cat):
+    """One return tuple from the tuples of the micro-batches: positions in `cat` hold per-episode tensors and are concatenated
+    in batch order, the others hold means over the slice's episodes and become the mean over the (equal) slices: the mean over
+    the whole batch.  Device work only."""
+    if len(outs) == 1:
+        return outs[0]
+    return tuple(torch.cat(v, 0) if i in cat else torch.stack(v).mean(0) for i, v in enumerate(zip(*outs)))
+
+
+_IM_CAT, _AU_CAT = (1, 2), (6, 7, 8)   # fake_sample, au_out; pred_on_real, pred_on_fake, fake_sample
+
+
+def im_eval_step(trainer, leaked_sample, si_sample, z=None, micro_batches=1):
+    A = _micro_batches(micro_batches, leaked_sample, si_sample, z)
     trainer.module.impersonator.eval()
-    with torch.no_grad():
-        loss, fake_sample, au_out = trainer.forward(mode='impersonator_forward', leaked_sample=leaked_sample,
-                                                    si_sample=si_sample, **({} if z is None else {"z": z}))
-        loss = loss.mean()
-    return loss.detach(), fake_sample.detach(), au_out.detach()
+    z = _whole_batch_z(trainer, A, leaked_sample, z)
+    sn, outs = mb.SNReplay(), []
+    for j in range(A):
+        ctx, (leaked, si, z_) = _micro_batch(sn, j, A, leaked_sample, si_sample, z)
+        with ctx, torch.no_grad():
+            loss, fake_sample, au_out = trainer.forward(mode='impersonator_forward', leaked_sample=leaked,
+                                                        si_sample=si, **({} if z_ is None else {"z": z_}))
+            loss = loss.mean()
+        outs.append((loss.detach(), fake_sample.detach(), au_out.detach()))
+    return _merged(outs, _IM_CAT)
 
 
-def au_eval_step(trainer, real_sample, fake_sample, si_sample):
-    trainer.module.authenticator.eval()
-    with torch.no_grad():
-        (loss, loss_on_real, loss_on_fake, reg, out_on_real, out_on_fake, pred_on_real, pred_on_fake,
-         fake_sample) = trainer.forward(mode='authenticator_forward', fake_sample=fake_sample, real_sample=real_sample,
-                                        si_sample=si_sample, grad=False)
-        loss = loss.mean()
+def _au_outputs(out):
+    (loss, loss_on_real, loss_on_fake, reg, out_on_real, out_on_fake, pred_on_real, pred_on_fake, fake_sample) = out
     return (loss.detach(), loss_on_real.detach().mean(), loss_on_fake.detach().mean(), reg.detach().mean(),
             out_on_real.detach().mean(), out_on_fake.detach().mean(),
             pred_on_real.detach(), pred_on_fake.detach(), fake_sample.detach())
+
+
+def au_eval_step(trainer, real_sample, fake_sample, si_sample, micro_batches=1):
+    A = _micro_batches(micro_batches, real_sample, fake_sample, si_sample)
+    trainer.module.authenticator.eval()
+    sn, outs = mb.SNReplay(), []
+    for j in range(A):
+        ctx, (real, fake, si) = _micro_batch(sn, j, A, real_sample, fake_sample, si_sample)
+        with ctx, torch.no_grad():
+            out = trainer.forward(mode='authenticator_forward', fake_sample=fake, real_sample=real, si_sample=si, grad=False)
+            out = (out[0].mean(),) + tuple(out[1:])
+        outs.append(_au_outputs(out))
+    return _merged(outs, _AU_CAT)
 
 
 def _backward(loss, opt):
@@ -54,44 +117,60 @@ def _backward(loss, opt):
             loss.backward()
 
 
-def _opt_step(opt):
-    """The optimizer step behind _backward(loss, opt): un-scales by the static scale, or - dynamic mode - by the scaler's own."""
+def _opt_step(opt, micro_batches=1):
+    """The optimizer step behind _backward(loss, opt): un-scales by the static scale, or - dynamic mode - by the scaler's own.
+    micro_batches = A: A backward passes have added into the bucket since zero_grad(); the one update takes their mean.  (The loss
+    scale is the same for all A: the static one is a host constant, the dynamic one moves inside this call only - where an
+    infinity left by ANY of the A passes makes the guarded kernel skip the update and halve the scale, once.)"""
     if opt.dynamic_scaler() is not None:
-        opt.step()
+        opt.step(micro_batches=micro_batches)
     else:
         sc, opt.loss_scaler = opt.loss_scaler, None   # (a scaler left from dynamic mode keeps its state, unused)
         try:
-            opt.step(grad_scale=1.0 / ops.loss_scale())
+            opt.step(grad_scale=1.0 / ops.loss_scale(), micro_batches=micro_batches)
         finally:
             opt.loss_scaler = sc
 
 
-def im_train_step(trainer, leaked_sample, si_sample, z=None):
+def im_train_step(trainer, leaked_sample, si_sample, z=None, micro_batches=1):
+    """micro_batches = A > 1: ONE generator update from A forward / backward passes on equal slices of the batch (see gim_step)."""
+    A = _micro_batches(micro_batches, leaked_sample, si_sample, z)
+    opt = trainer.module.impersonator_opt
     trainer.module.impersonator.train()
-    trainer.module.impersonator_opt.zero_grad()
-    loss, fake_sample, au_out = trainer.forward(mode='impersonator_forward', leaked_sample=leaked_sample,
-                                                si_sample=si_sample, **({} if z is None else {"z": z}))
-    loss = loss.mean()
-    _backward(loss, trainer.module.impersonator_opt)
-    _opt_step(trainer.module.impersonator_opt)
-    return loss.detach(), fake_sample.detach(), au_out.detach()
+    opt.zero_grad()
+    z = _whole_batch_z(trainer, A, leaked_sample, z)
+    sn, outs = mb.SNReplay(), []
+    for j in range(A):
+        ctx, (leaked, si, z_) = _micro_batch(sn, j, A, leaked_sample, si_sample, z)
+        with ctx:
+            loss, fake_sample, au_out = trainer.forward(mode='impersonator_forward', leaked_sample=leaked,
+                                                        si_sample=si, **({} if z_ is None else {"z": z_}))
+            loss = loss.mean()
+            _backward(loss, opt)
+        outs.append((loss.detach(), fake_sample.detach(), au_out.detach()))
+    _opt_step(opt, A)
+    return _merged(outs, _IM_CAT)
 
 
-def au_train_step(trainer, real_sample, fake_sample, si_sample):
+def au_train_step(trainer, real_sample, fake_sample, si_sample, micro_batches=1):
+    """micro_batches = A > 1: ONE discriminator update from A forward / backward passes on equal slices of the batch (see gim_step)."""
+    A = _micro_batches(micro_batches, real_sample, fake_sample, si_sample)
+    opt = trainer.module.authenticator_opt
     trainer.module.authenticator.train()
-    trainer.module.authenticator_opt.zero_grad()
-    (loss, loss_on_real, loss_on_fake, reg, out_on_real, out_on_fake, pred_on_real, pred_on_fake,
-     fake_sample) = trainer.forward(mode='authenticator_forward', fake_sample=fake_sample, real_sample=real_sample,
-                                    si_sample=si_sample)
-    loss = loss.mean()
-    _backward(loss, trainer.module.authenticator_opt)
-    _opt_step(trainer.module.authenticator_opt)
-    return (loss.detach(), loss_on_real.detach().mean(), loss_on_fake.detach().mean(), reg.detach().mean(),
-            out_on_real.detach().mean(), out_on_fake.detach().mean(),
-            pred_on_real.detach(), pred_on_fake.detach(), fake_sample.detach())
+    opt.zero_grad()
+    sn, outs = mb.SNReplay(), []
+    for j in range(A):
+        ctx, (real, fake, si) = _micro_batch(sn, j, A, real_sample, fake_sample, si_sample)
+        with ctx:
+            out = trainer.forward(mode='authenticator_forward', fake_sample=fake, real_sample=real, si_sample=si)
+            out = (out[0].mean(),) + tuple(out[1:])
+            _backward(out[0], opt)
+        outs.append(_au_outputs(out))
+    _opt_step(opt, A)
+    return _merged(outs, _AU_CAT)
 
 
-def gim_step(trainer, leaked_sample, real_sample, si_sample, z=None, overlap=None, defer_join=False):
+def gim_step(trainer, leaked_sample, real_sample, si_sample, z=None, overlap=None, defer_join=False, micro_batches=1):
     """One training iteration on one episode batch: generator step then discriminator step on the fake
     sample produced with the pre-update generator (training/gim_img_training.py:225-239, n_au_steps=1).
 
@@ -105,61 +184,79 @@ def gim_step(trainer, leaked_sample, real_sample, si_sample, z=None, overlap=Non
     or outputs are next needed (ops.join_lanes(): inside the trainer's forward modes, save(), and by callers before they read
     the returned discriminator statistics).
     overlap=False (or GIM_NO_STEP_OVERLAP=1) runs the two steps back to back; hipGraph capture does (a hipGraph replays
-    parallel branches slower than eager streams run them: 234 vs 282 episodes/s)."""
+    parallel branches slower than eager streams run them: 234 vs 282 episodes/s).
+
+    micro_batches = A > 1 - gradient accumulation: the same iteration on a batch that does not fit one pass.  The batch is cut into A
+    equal slices (dim 0); each slice runs the generator's forward and backward and, on lane 1, the discriminator's; the gradients
+    add up in the optimizers' buckets (zeroed once); each optimizer then makes ONE update with the bucket scaled by 1 / A - the
+    step on the whole batch, since the networks have no BatchNorm and every loss is a mean over episodes.  The spectral-norm power
+    iterations run in the first slice only (mb.SNReplay), learning-rate schedule, global step and Adam's counter move once.  Losses and
+    mean outputs are returned as means over the slices, per-episode outputs concatenated; nothing is read back in between."""
+    A = _micro_batches(micro_batches, leaked_sample, real_sample, si_sample, z)
     if overlap is None:
         overlap = _OVERLAP
     if not (overlap and leaked_sample.is_cuda):
-        im = im_train_step(trainer, leaked_sample, si_sample, z=z)
-        au = au_train_step(trainer, real_sample, im[1], si_sample)
+        im = im_train_step(trainer, leaked_sample, si_sample, z=z, micro_batches=A)
+        au = au_train_step(trainer, real_sample, im[1], si_sample, micro_batches=A)
         return im, au
     from .gim_img_models import lane_stream
     mod = trainer.module
     cur = torch.cuda.current_stream()
     dstream = lane_stream(leaked_sample.device, 1)
+    sn, ims, aus = mb.SNReplay(), [], []
 
-    # generator: forward on the caller's stream
     ops.mark_phase("step start")
     mod.impersonator.train()
     mod.impersonator_opt.zero_grad()
-    loss, fake_sample, au_out = trainer.forward(mode='impersonator_forward', leaked_sample=leaked_sample,
-                                                si_sample=si_sample, **({} if z is None else {"z": z}))
-    loss = loss.mean()
-    fake_d = fake_sample.detach()
-    ops.mark_phase("G forward done")
-    ops.stream_wait(dstream, cur)            # lane 1 forks here: everything up to the generator's forward is visible to it
-    for t in (fake_d, real_sample, si_sample):
-        t.record_stream(dstream)
+    z = _whole_batch_z(trainer, A, leaked_sample, z)
+    for j in range(A):
+        last = j == A - 1
+        ctx, (leaked, real, si, z_) = _micro_batch(sn, j, A, leaked_sample, real_sample, si_sample, z)
+        with ctx:
+            # generator: forward on the caller's stream
+            loss, fake_sample, au_out = trainer.forward(mode='impersonator_forward', leaked_sample=leaked,
+                                                        si_sample=si, **({} if z_ is None else {"z": z_}))
+            loss = loss.mean()
+            fake_d = fake_sample.detach()
+            ops.mark_phase("G forward done")
+            ops.stream_wait(dstream, cur)            # lane 1 forks here: everything up to the generator's forward is visible to it
+            for t in (fake_d, real, si):
+                t.record_stream(dstream)
 
-    # generator: backward on the caller's stream (enqueued first: it is the longer dependency chain; enqueueing the discriminator's
-    # FORWARD ahead of it - so that lane 1 starts ~8 ms of host time earlier - was measured 4 % SLOWER, 406 vs 423 episodes/s over
-    # three alternating pairs on one box: lane 1's early kernels take the chip from the critical lane; profiles/r04_d_*)
-    _backward(loss, mod.impersonator_opt)
-    ops.mark_phase("G backward done")
-    gbwd_done = cur.record_event()
-    # generator's Adam right away: nothing on lane 1 reads the generator's weights, and with several GPUs its gradient
-    # all-reduce (the larger bucket, 246 MB) then runs under the discriminator step instead of after it
-    _opt_step(mod.impersonator_opt)
-    ops.mark_phase("G update done")
-    im = (loss.detach(), fake_d, au_out.detach())
+            # generator: backward on the caller's stream (enqueued first: it is the longer dependency chain; enqueueing the discriminator's
+            # FORWARD ahead of it - so that lane 1 starts ~8 ms of host time earlier - was measured 4 % SLOWER, 406 vs 423 episodes/s over
+            # three alternating pairs on one box: lane 1's early kernels take the chip from the critical lane; profiles/r04_d_*)
+            _backward(loss, mod.impersonator_opt)
+            ops.mark_phase("G backward done")
+            if last:
+                gbwd_done = cur.record_event()
+                # generator's Adam right away: nothing on lane 1 reads the generator's weights, and with several GPUs its gradient
+                # all-reduce (the larger bucket, 246 MB) then runs under the discriminator step instead of after it
+                _opt_step(mod.impersonator_opt, A)
+                ops.mark_phase("G update done")
+            ims.append((loss.detach(), fake_d, au_out.detach()))
 
-    # discriminator step on lane 1
-    with torch.cuda.stream(dstream), ops.lane(1):
-        ops.mark_phase("D start")
-        mod.authenticator.train()
-        mod.authenticator_opt.zero_grad()
-        (dloss, loss_on_real, loss_on_fake, reg, out_on_real, out_on_fake, pred_on_real, pred_on_fake,
-         fake_out) = trainer.forward(mode='authenticator_forward', fake_sample=fake_d, real_sample=real_sample,
-                                     si_sample=si_sample)
-        dloss = dloss.mean()
-        ops.mark_phase("D forward done")
-        _backward(dloss, mod.authenticator_opt)
-        ops.mark_phase("D backward done")
-        dstream.wait_event(gbwd_done)   # the generator's backward reads the weights this update overwrites
-        _opt_step(mod.authenticator_opt)
-        ops.mark_phase("D update done")
-        au = (dloss.detach(), loss_on_real.detach().mean(), loss_on_fake.detach().mean(), reg.detach().mean(),
-              out_on_real.detach().mean(), out_on_fake.detach().mean(),
-              pred_on_real.detach(), pred_on_fake.detach(), fake_out.detach())
+            # discriminator step on lane 1 (a slice's passes: under this slice's generator backward and the next slice's forward)
+            with torch.cuda.stream(dstream), ops.lane(1):
+                ops.mark_phase("D start")
+                if j == 0:
+                    mod.authenticator.train()
+                    mod.authenticator_opt.zero_grad()
+                out = trainer.forward(mode='authenticator_forward', fake_sample=fake_d, real_sample=real, si_sample=si)
+                out = (out[0].mean(),) + tuple(out[1:])
+                ops.mark_phase("D forward done")
+                _backward(out[0], mod.authenticator_opt)
+                ops.mark_phase("D backward done")
+                if last:
+                    dstream.wait_event(gbwd_done)   # the generator's backward reads the weights this update overwrites
+                    _opt_step(mod.authenticator_opt, A)
+                    ops.mark_phase("D update done")
+                aus.append(_au_outputs(out))
+    im = _merged(ims, _IM_CAT)
+    au = aus[0]
+    if A > 1:
+        with torch.cuda.stream(dstream):
+            au = _merged(aus, _AU_CAT)
     if defer_join:
         ops.defer_join(dstream)
     else:
@@ -245,15 +342,20 @@ def eval_step(device, trainer, ds, logger, batch_size):
 
 def train_epoch(device, logger, epoch, trainer, train_ds, val_ds, train_batch_size, val_batch_size, num_workers,
                 save_every, eval_every, save_imgs_every, train_eval_indices, val_eval_indices,
-                tb_log_every=100, tb_log_enc_every=500, n_au_steps=1, dbg=False):
+                tb_log_every=100, tb_log_enc_every=500, n_au_steps=1, dbg=False, micro_batches=1):
     """training/gim_img_training.py:186-354.  Same protocol and cadences; the generator step and the discriminator step of
     an iteration are issued through gim_step (overlapped on two streams) when the generator trains this iteration.  Nothing
-    is fetched from the device between log points."""
+    is fetched from the device between log points.  micro_batches = A: every iteration accumulates its gradients over A slices of
+    the rank's batch (gim_step); an iteration stays one global step, one learning-rate step and one update per optimizer."""
+    _micro_batches(micro_batches)
+    if (train_batch_size // _world()[1]) % micro_batches != 0:
+        raise ValueError("a local batch of %d episodes cannot be cut into %d equal micro-batches" % (train_batch_size // _world()[1], micro_batches))
     buf = {k_: [] for k_ in ("au_loss", "au_loss_on_real", "au_loss_on_fake", "au_reg", "au_out_on_real", "au_out_on_fake",
                              "au_pred_on_real", "au_pred_on_fake", "im_loss")}
     rank, _ = _world()
     batches, n_batches = _batches(train_ds, train_batch_size, True, num_workers, device)
     num_iters = min(50, n_batches) if dbg else n_batches
+    mbs = {} if micro_batches == 1 else {"micro_batches": micro_batches}
     for data_batch in tqdm(itertools.islice(batches, num_iters), total=num_iters, desc='Training', disable=rank != 0):
         trainer.module.do_global_step()
         trainer.module.update_learning_rate()
@@ -261,10 +363,10 @@ def train_epoch(device, logger, epoch, trainer, train_ds, val_ds, train_batch_si
         global_step = trainer.module.global_step
 
         if (global_step + 1) % n_au_steps == 0:
-            (im_loss, fake_sample, _), au = gim_step(trainer, leaked_sample, real_sample, si_sample, defer_join=True)
+            (im_loss, fake_sample, _), au = gim_step(trainer, leaked_sample, real_sample, si_sample, defer_join=True, **mbs)
         else:
-            im_loss, fake_sample, _ = im_eval_step(trainer=trainer, leaked_sample=leaked_sample, si_sample=si_sample)
-            au = au_train_step(trainer=trainer, real_sample=real_sample, fake_sample=fake_sample, si_sample=si_sample)
+            im_loss, fake_sample, _ = im_eval_step(trainer=trainer, leaked_sample=leaked_sample, si_sample=si_sample, **mbs)
+            au = au_train_step(trainer=trainer, real_sample=real_sample, fake_sample=fake_sample, si_sample=si_sample, **mbs)
         au_loss, au_loss_on_real, au_loss_on_fake, au_reg, au_out_on_real, au_out_on_fake, au_pred_on_real, au_pred_on_fake, fake_sample = au
         buf["im_loss"].append(im_loss.view(1))
         for k_, v in (("au_loss", au_loss), ("au_loss_on_real", au_loss_on_real), ("au_loss_on_fake", au_loss_on_fake),
@@ -331,13 +433,14 @@ def train_epoch(device, logger, epoch, trainer, train_ds, val_ds, train_batch_si
 def train_gim_imgs(device_name, device_ids, outdir, train_ds, val_ds, authenticator, impersonator, m, n, k,
                    reg_param, remove_noise_mean, au_lr, im_lr, beta1, beta2, env_noise_mapping_lr, lr_gamma, milestones,
                    resume_from_ckpt, n_epochs, batch_size, num_workers, save_every, eval_every, save_imgs_every,
-                   train_eval_indices, val_eval_indices, n_au_steps=1, dbg=False):
-    """training/gim_img_training.py:356-441.  `device_ids` keeps its meaning as "the GPUs of the job": with more than one,
+                   train_eval_indices, val_eval_indices, n_au_steps=1, dbg=False, micro_batches=1):
+    """training/gim_img_training.py:356-441.  micro_batches: see train_epoch.  `device_ids` keeps its meaning as "the GPUs of the job": with more than one,
     launch one process per GPU (torchrun) - each process builds the same trainer, takes its slice of every global batch
     and the two optimizers all-reduce their gradient buckets over RCCL (EpisodeParallel replaces nn.DataParallel)."""
     from .gim_img_trainer import GIMImgTrainer
     from .gim_img_models import stream_concurrency_check
     from .training_utils import pin_rank_to_cores
+    _micro_batches(micro_batches)
     if dist.is_initialized() and not torch.cuda.is_initialized():
         pin_rank_to_cores()   # a core set per rank, before the first GPU call (the runtime's helper threads inherit it)
     device = get_device(device_type=device_name, device_ids=device_ids)
@@ -368,7 +471,8 @@ def train_gim_imgs(device_name, device_ids, outdir, train_ds, val_ds, authentica
                         train_batch_size=adjust_batch_size(len(train_ds), batch_size, n_devices),
                         val_batch_size=adjust_batch_size(len(val_ds), batch_size, n_devices),
                         num_workers=num_workers, save_every=save_every, eval_every=eval_every, save_imgs_every=save_imgs_every,
-                        train_eval_indices=train_eval_indices, val_eval_indices=val_eval_indices, n_au_steps=n_au_steps, dbg=dbg)
+                        train_eval_indices=train_eval_indices, val_eval_indices=val_eval_indices, n_au_steps=n_au_steps, dbg=dbg,
+                        micro_batches=micro_batches)
         except KeyboardInterrupt:
             print("\nKeyboardInterrupt\nSaving checkpoint...\n")
             if rank == 0:

@@ -83,6 +83,63 @@ class MLP(nn.Module):
         return x
 
 
+class SNReplay:
+    """The spectral-norm state of ONE accumulated optimizer step (gim_img_training, micro_batches > 1).  The power iterations
+    depend on the weights and on u only, and the weights do not move between the micro-batches of a step: micro-batch 0 runs
+    them as a plain step does and every site (an SNPlan, or an SNConv2d called without one) keeps what each of its calls
+    produced; inside micro-batches 1 .. A-1 call number c of a site takes what call number c took in micro-batch 0.  So the
+    accumulated step advances weight_u / weight_v exactly as one step on the whole batch does, and every slice is
+    normalised by the same sigma."""
+
+    def __init__(self):
+        self.micro = 0
+
+    def micro_batch(self, j):
+        """Context of micro-batch j: SN sites called inside record (j == 0) or replay (j > 0)."""
+        return _SNMicroBatch(self, j)
+
+
+class _SNMicroBatch:
+    def __init__(self, state, j):
+        self.state, self.j = state, j
+
+    def __enter__(self):
+        self.prev = _SN_REPLAY[0]
+        self.state.micro = self.j
+        _SN_REPLAY[0] = self.state
+
+    def __exit__(self, *exc):
+        _SN_REPLAY[0] = self.prev
+
+
+_SN_REPLAY = [None]    # the SNReplay of the accumulated step being issued (host-side selection, like ops.lane), or None
+
+
+class _SNTape:
+    """What the calls of one SN site produced in micro-batch 0 of an accumulated step, in call order."""
+
+    def __init__(self):
+        self.state, self.items, self.micro, self.pos = None, [], 0, 0
+
+    def next(self, state, key, make):
+        """The item of this site's next call: made (and kept) in micro-batch 0, handed out again afterwards.  `key` is what the
+        call must have in common with the recorded one (an SNPlan's rounds)."""
+        if self.state is not state:       # first call of this site in a new accumulated step
+            self.state, self.items, self.micro, self.pos = state, [], 0, 0
+        if self.micro != state.micro:
+            self.micro, self.pos = state.micro, 0
+        if state.micro == 0:
+            item = make()
+            self.items.append((key, item))
+            return item
+        if self.pos >= len(self.items) or self.items[self.pos][0] != key:
+            raise RuntimeError("accumulated step: micro-batch %d makes spectral-norm call %d %r of a site, which micro-batch 0 "
+                               "did not make: the micro-batches of a step must run the same forward passes" % (state.micro, self.pos, key))
+        item = self.items[self.pos][1]
+        self.pos += 1
+        return item
+
+
 class SNConv2d(nn.Module):
     """nn.utils.spectral_norm(nn.Conv2d(in, out, k, padding=(k-1)//2)) restated
     (call sites models/model_blocks.py:492-495,522-526,744-750,792-793,836-840).
@@ -109,6 +166,7 @@ class SNConv2d(nn.Module):
         self.register_buffer("weight_v", v)
 
         self._sn_queue = collections.deque()  # (sigma, u, v) triples precomputed by an SNPlan round
+        self._sn_tape = _SNTape()   # calls made without a plan inside an accumulated step (SNReplay)
         self._wants_fold = False    # set by the first folded() call: SNPlan.run then folds this conv together with the others
         self._fold_slot = (kernel_size + 1, "fold")     # where ops._WT_CACHE keeps the folded weights F of weight_orig
 
@@ -128,6 +186,9 @@ class SNConv2d(nn.Module):
         guard = None
         if self._sn_queue:
             sigma, u_s, v_s, guard = self._sn_queue.popleft()
+        elif _SN_REPLAY[0] is not None:    # no plan in front of this call: the same record / replay rule, per conv
+            sigma, u_s, v_s = self._sn_tape.next(_SN_REPLAY[0], None, lambda: ops.spectral_sigma(
+                self.weight_orig, self.weight_u, self.weight_v, self.training))
         else:
             sigma, u_s, v_s = ops.spectral_sigma(self.weight_orig, self.weight_u, self.weight_v, self.training)
         if fork_pool_slope is not None:
@@ -158,6 +219,7 @@ class SNPlan:
         self.convs = [c for c in convs if isinstance(c, SNConv2d)]
         self._gen = 0      # number of run() calls so far; run g writes buffer set g & 1
         self._bufs = {}
+        self._tape = _SNTape()
         self._tables = ops._TableCache("SNPlan", 1)     # (every conv's w, u, v address) -> job table of the power iterations
         self._fold_tables = ops._TableCache("SNPlan folds", None, skip_in_capture=True)   # (w address of the stale convs) -> fold table + outputs
 
@@ -192,10 +254,31 @@ class SNPlan:
             views.append((o_s, o_u, Cout, o_v, K))
         return ops._DeviceTable(jobs, cols, rows, extra=(len(jobs), len(cols), len(rows), off, views))
 
-    @torch.no_grad()
     def run(self, rounds, training):
+        """Queue (sigma, u, v, guard) for the next `rounds` calls of every conv.  Inside micro-batch j > 0 of an accumulated step
+        (SNReplay) the k-th run() queues again what the k-th run() of micro-batch 0 queued - the same views of the same persistent
+        buffers, under their original (plan, generation) guard - and launches nothing: _gen stays, so ops.ConvFn's staleness check
+        sees the step as the single step it is."""
         if not self.convs:
             return
+        state = _SN_REPLAY[0]
+        if state is None:
+            return self._launch(rounds, training)
+
+        def record():
+            self._launch(rounds, training)
+            return [tuple(c._sn_queue) for c in self.convs]
+        queued = self._tape.next(state, rounds, record)    # (`training` is micro-batch 0's: what the whole-batch step would use)
+        if state.micro > 0:
+            if self.stale(queued[0][0][3][1]):
+                raise RuntimeError("accumulated step: the spectral-norm buffers of micro-batch 0 were overwritten by forward passes "
+                                   "outside the step")
+            for c, q in zip(self.convs, queued):
+                c._sn_queue.clear()
+                c._sn_queue.extend(q)
+
+    @torch.no_grad()
+    def _launch(self, rounds, training):
         w0 = self.convs[0].weight_orig
         if not (w0.is_cuda and w0.dtype == torch.float32):
             raise RuntimeError("weights must be CUDA float32 (got %s on %s): the GIM engine has no CPU path" % (w0.dtype, w0.device))

@@ -237,12 +237,17 @@ class FusedAdam(torch.optim.Optimizer):
             self._lr_cache = lrs
 
     @torch.no_grad()
-    def step(self, closure=None, grad_scale=1.0):
+    def step(self, closure=None, grad_scale=1.0, micro_batches=1):
         """grad_scale multiplies the gradient bucket inside the Adam kernel (together with the 1 / world_size of the data-parallel
         average): 1 / S after a backward pass of S * loss (the loss scale of the fp16 matrix path, ops.loss_scale).  With a
         loss_scaler the kernel takes 1 / S from the scaler's device state (pass grad_scale = 1) and the update is skipped when the
-        bucket - after the all-reduce, so on every rank alike - holds an inf or a NaN."""
+        bucket - after the all-reduce, so on every rank alike - holds an inf or a NaN.
+        micro_batches = A: the bucket holds the SUM of the gradients of A local mean losses (an accumulated step of
+        gim_img_training: A backward passes since zero_grad()); the kernel's scale takes the 1 / A of their mean as it takes the
+        1 / world_size, so N ranks x A micro-batches are scaled by 1 / (N A) and all-reduced once."""
         assert closure is None
+        if micro_batches != 1:
+            grad_scale = grad_scale / micro_batches
         lib = _lib.load()
         self._ensure()
         self._sync_grads()
