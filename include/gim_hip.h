@@ -42,6 +42,11 @@ int gim_version(void);
  *   pool    = 1: the output is avgpool2(conv) ([N][H/2][W/2][Cout]; nn.AvgPool2d(2), models/model_blocks.py:502,509),
  *                computed as ONE stride-2 convolution with the (KH+1)^2-tap folded weights (16/36 of the FLOPs
  *                for KH = 3, 100/324 for KH = 9).  Needs ups = 0 and wfold = 1.
+ *   pool    = 2: (gim_conv2d_fwd, gim_conv2d_wgrad*, KH = 3, fp32) the same pooled output from the PRE-FILTERED input: `x` is
+ *                p = gim_box2_fwd(x) [N][H+1][W+1][Cin], the stride-1 2x2 mean of the zero-padded activated map, and
+ *                avgpool2(conv3x3(a))[Y][X] = sum_{ta,tb} w[ta][tb] * p[2Y+ta][2X+tb]: ONE stride-2 convolution with the conv's own
+ *                9 taps (9/36 of the FLOPs), no zero-padding tap.  `w` and the weight gradient are in the plain layout (wfold = 0);
+ *                pre_slope must be 1 (gim_box2_fwd applies the LeakyReLU).  The input gradient runs the folded form (pool = 1).
  *   wfold   = 1: `w` points to the folded weights F of gim_conv2d_fold_weights ([Cout][KH+1][KH+1][Cin]).  With
  *                ups = 1 the convolution of the upsampled image is computed in its sub-pixel form (4 output-parity
  *                classes, ((KH+1)/2)^2 taps each on the LOW-resolution x): same FLOP ratios as above.
@@ -280,6 +285,10 @@ int gim_avgpool2_fwd(const float* x, float* y, int N, int H, int W, int C, void*
  * gim_scale_add_fwd_act): LeakyReLU is inverted on the fly (x = a for a > 0, a / in_slope otherwise), so that the skip path of a
  * ResBlockDown (models/model_blocks.py:499-503, which reads the RAW block input) can share the activated copy its conv path reads. */
 int gim_avgpool2_fwd_act(const float* x, float* y, int N, int H, int W, int C, float in_slope, void* stream);
+/* The operand of the pre-filtered pool convolution (gim_conv_shape.pool = 2): p [N][H+1][W+1][C],
+ * p[n][y][x] = 1/4 * sum_{dy,dx in {0,1}} lrelu(x, slope)[n][y-1+dy][x-1+dx] with zeros outside the map (slope = 1: x is used as stored,
+ * e.g. already activated by its producer).  One streaming pass: C % 4 == 0, 16-byte aligned pointers, N*(H+1)*(W+1)*C/4 < 2^31. */
+int gim_box2_fwd(const float* x, float* p, int N, int H, int W, int C, float slope, void* stream);
 /* Gradient fan-in of a tensor with several consumers in ONE pass (autograd's AccumulateGrad / input-buffer additions, one launch
  * per extra consumer): out = a + b (+ c) (+ d) (c, d may be NULL);  and the ResBlockDown form (models/model_blocks.py:499-510:
  * x feeds the conv path and, through AvgPool2d, the skip path): out = g + avgpool2_bwd(dy_pooled), g and out [N][H][W][C]. */

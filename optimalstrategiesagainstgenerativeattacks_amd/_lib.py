@@ -69,6 +69,7 @@ SIGNATURES = {
     "gim_norm_bwd": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "gim_avgpool2_fwd": [P, P, c_int, c_int, c_int, c_int, P],
     "gim_avgpool2_fwd_act": [P, P, c_int, c_int, c_int, c_int, c_float, P],
+    "gim_box2_fwd": [P, P, c_int, c_int, c_int, c_int, c_float, P],
     "gim_add_n": [P, P, P, P, P, c_int64, P],
     "gim_add_avgpool2_bwd": [P, P, P, c_int, c_int, c_int, c_int, P],
     "gim_avgpool2_bwd": [P, P, c_int, c_int, c_int, c_int, P],

@@ -1616,8 +1616,11 @@ static int check_shape(const gim_conv_shape* s) {
     GIM_CHECK_ARG(s->ups == 0 || s->ups == 1, "conv: ups must be 0 or 1");
     GIM_CHECK_ARG(ilog2_exact(s->H) >= 0 && ilog2_exact(s->W) >= 0, "conv: H and W must be powers of two");
     GIM_CHECK_ARG(!s->ups || (s->H >= 2 && s->W >= 2), "conv: ups needs H, W >= 2");
-    GIM_CHECK_ARG(!s->pool || (!s->ups && s->H >= 2 && s->W >= 2 && s->wfold), "conv: pool needs ups == 0, H, W >= 2 and folded weights");
-    GIM_CHECK_ARG(!s->wfold || s->pool || s->ups, "conv: wfold only with pool or ups");
+    GIM_CHECK_ARG(s->pool >= 0 && s->pool <= 2, "conv: pool must be 0, 1 (folded weights) or 2 (pre-filtered input)");
+    GIM_CHECK_ARG(s->pool != 1 || (!s->ups && s->H >= 2 && s->W >= 2 && s->wfold), "conv: pool needs ups == 0, H, W >= 2 and folded weights");
+    GIM_CHECK_ARG(s->pool != 2 || (s->KH == 3 && !s->ups && s->H >= 2 && s->W >= 2 && !s->wfold && s->prec == 0 && s->pre_slope == 1.f),
+                  "conv: pool = 2 (pre-filtered input) needs KH == 3, ups == 0, H, W >= 2, the plain weights, the fp32 matrix path and pre_slope = 1");
+    GIM_CHECK_ARG(!s->wfold || s->pool == 1 || s->ups, "conv: wfold only with pool = 1 or ups");
     GIM_CHECK_ARG((long long)s->N * s->H * s->W < (1ll << 31), "conv: too many output pixels");
     GIM_CHECK_ARG(s->prec >= 0 && s->prec <= 2, "conv: prec must be 0 (fp32 MFMA), 1 (fp16 operands, fp32 accumulate; saturating) or 2 (the same, non-saturating)");
     return GIM_OK;
@@ -1653,6 +1656,20 @@ static Geo geo_s2(const gim_conv_shape* s, bool flip) {
     return g;
 }
 
+// pre-filtered pool (pool = 2, 3x3): stride-2 gather of the conv's OWN taps from the (H+1) x (W+1) box-filtered map p (gim_box2_fwd),
+// which carries the zero padding and the 2x2 mean - avgpool2(conv3x3(a))[Y][X] = sum_{ta,tb} W[ta][tb] * p[2Y+ta][2X+tb]: 9 taps
+// instead of the fold's 16, no padding tap, no 1/4 factor; logical grid (H/2, W/2)
+static Geo geo_box(const gim_conv_shape* s) {
+    Geo g{};
+    geo_grid(g, s->N, s->H / 2, s->W / 2);
+    g.Hin = s->H + 1; g.Win = s->W + 1; g.ups = 0;
+    g.s_in = g.s_in_x = 2; g.off_y = g.off_x = 0; g.Th = g.Tw = g.KF = g.KFw = s->KH;
+    g.wa_base = g.wb_base = 0;
+    g.wa_step = g.wb_step = 1;
+    g.os = 1;
+    return g;
+}
+
 // 4 parity classes: logical grid (H/2, W/2), output image (H, W), gathered image (H/2, W/2)
 static Geo geo_pc(const gim_conv_shape* s, int kind) {
     Geo g{};
@@ -1675,11 +1692,12 @@ static Geo geo_pc(const gim_conv_shape* s, int kind) {
 
 // Launch configurations measured per layer shape on an MI355X (tools/conv_autotune.py writes conv_tune_table.inc):
 // {kind (0 fwd-style, 1 dgrad-style, 2 wgrad, 4 dgrad on transposed weights), M, Ca, Cb, Ktot, parity classes,
-//  tile config, split-K | wgrad slice target}.
+//  tile config, split-K | wgrad slice target}.  conv_tune_box.inc: the rows of the pre-filtered pool geometry (kind 7 forward; wgrad: class key 4).
 // Shapes that are not in the table use the heuristics below.
 struct TuneEntry { int kind, M, Ca, Cb, Ktot, pc, tile, ks; };
 static const TuneEntry g_tune[] = {
 #include "conv_tune_table.inc"
+#include "conv_tune_box.inc"
     {-1, 0, 0, 0, 0, 0, 0, 0}};
 static const TuneEntry* tune_lookup(int kind, int M, int Ca, int Cb, int Ktot, int pc) {
     for (const TuneEntry* e = g_tune; e->kind >= 0; ++e)
@@ -2014,25 +2032,27 @@ static bool tiny_route(const gim_conv_shape* s) { return s->tune_tile == 0 && s-
 // dx is at half resolution in the sub-pixel form only (a plain upsample's dx is produced at the full one)
 static void image_elems(const gim_conv_shape* s, bool dx_side, size_t& xi, size_t& yi) {
     const int half = dx_side ? (s->ups && s->wfold ? 1 : 0) : s->ups;
-    xi = (size_t)(s->H >> half) * (s->W >> half) * s->Cin;
-    yi = (size_t)(s->H >> s->pool) * (s->W >> s->pool) * s->Cout;
+    xi = s->pool == 2 ? (size_t)(s->H + 1) * (s->W + 1) * s->Cin : (size_t)(s->H >> half) * (s->W >> half) * s->Cin;
+    yi = (size_t)(s->H >> (s->pool ? 1 : 0)) * (s->W >> (s->pool ? 1 : 0)) * s->Cout;
 }
 
 static int fwd_call(ConvCall& c, const float* x, const float* w, const float* bias, const float* sigma, const float* residual, float* y,
                     const gim_conv_shape* s) {
     const bool up_fold = s->ups && s->wfold;
-    int rc = convp_begin(c, s->pool ? geo_s2(s, false) : (up_fold ? geo_pc(s, 0) : geo_plain(s, false)), s->Cin, s->Cout, s->Cin, 0, s,
+    // (pool = 2: table rows of kind 7 - the rows of kind 0 were measured on the plain, folded and sub-pixel geometries)
+    int rc = convp_begin(c, s->pool == 2 ? geo_box(s) : (s->pool ? geo_s2(s, false) : (up_fold ? geo_pc(s, 0) : geo_plain(s, false))), s->Cin, s->Cout,
+                         s->Cin, s->pool == 2 ? 7 : 0, s,
                          "conv: one image of the gathered tensor exceeds 2 GiB (32-bit buffer offsets)");
     if (rc) return rc;
     ConvP& p = c.p;
     p.x = x; p.w = w; p.bias = bias; p.sigma = sigma; p.res = residual; p.y = y;
     p.Cin_w = s->Cin;
-    p.pre_slope = s->pre_slope; p.out_scale = s->pool ? 0.25f : 1.f; p.res_ups = s->res_ups;
+    p.pre_slope = s->pre_slope; p.out_scale = s->pool == 1 ? 0.25f : 1.f; p.res_ups = s->res_ups;
     rc = set_post_slope(p, s->post_slope);
     if (rc) return rc;
     p.f16 = s->prec;
     c.gen = gen_fwd(s->Cin, x, w);
-    return set_y_elems(c, (size_t)s->N * (s->H >> s->pool) * (s->W >> s->pool) * s->Cout,
+    return set_y_elems(c, (size_t)s->N * (s->H >> (s->pool ? 1 : 0)) * (s->W >> (s->pool ? 1 : 0)) * s->Cout,
                        "conv: one image of the output exceeds 2 GiB (32-bit buffer offsets)");
 }
 
@@ -2132,6 +2152,7 @@ static int dgrad_call(ConvCall& c, const float* dy, const float* w, const float*
                       const gim_conv_shape* s, bool transposed, const float* res_half, float res_scale) {
     const bool up_fold = s->ups && s->wfold;
     GIM_CHECK_ARG(!(mask_x && s->ups && !up_fold), "conv dgrad: mask_x with ups == 1 needs folded weights");
+    GIM_CHECK_ARG(s->pool != 2, "conv dgrad: pool = 2 is a forward / wgrad geometry (the input gradient runs the folded form, pool = 1)");
     int rc = convp_begin(c, s->pool ? geo_pc(s, 1) : (up_fold ? geo_s2(s, true) : geo_plain(s, true)), s->Cout, s->Cin, s->Cout, 1, s,
                          "conv: one image of the gathered tensor exceeds 2 GiB (32-bit buffer offsets)");
     if (rc) return rc;
@@ -2487,15 +2508,16 @@ static WgPlan wgrad_plan(const gim_conv_shape* s0, bool rows_form, int combine, 
     const gim_conv_shape* s = &v;
     const bool up_fold = s->ups && s->wfold;
     const int KF = s->wfold ? s->KH + 1 : s->KH;
+    const int half = (s->wfold || s->pool == 2) ? 1 : 0;   // the grid of the streamed operand: folds and the pre-filtered pool run on (H/2, W/2)
     q.rows = up_fold ? s->Cin : s->Cout;
     q.cols = KF * KF * (up_fold ? s->Cout : s->Cin);
-    const long long M = (long long)s->N * (s->H >> (s->wfold ? 1 : 0)) * (s->W >> (s->wfold ? 1 : 0));
+    const long long M = (long long)s->N * (s->H >> half) * (s->W >> half);
     q.M = (int)M;
     // launch choice: the caller's (gim_conv_shape.tune_tile / tune_wgrad), else the table row of this shape, else the heuristic
     int target = s->tune_wgrad > 0 ? s->tune_wgrad : 0;
     int tile = s->tune_tile > 0 ? s->tune_tile : 0;
     if (!target && !tile && s->tune_tile == 0) {
-        const int pcw = (s->pool ? 1 : 0) + (up_fold ? 2 : 0);
+        const int pcw = (s->pool == 2 ? 4 : (s->pool ? 1 : 0)) + (up_fold ? 2 : 0);   // (4: the pre-filtered pool's own rows, conv_tune_box.inc)
         const TuneEntry* te = tune_lookup(2, (int)M, q.rows, q.cols, s->KH, pcw);
         if (te) { target = te->ks; tile = te->tile; q.table_hit = 1; }
     }
@@ -2631,7 +2653,7 @@ static int wgrad_call(WgP& p, WgPlan& q, const float* dy, const float* x, float*
     else if (up_fold)   // the roles swap: x is streamed, dy gathered with stride 2
         rc = wgp_fill(p, q, geo_s2(s, false), {x, s->Cin, s->pre_slope}, {dy, s->Cout, 1.f}, s->Cout);
     else
-        rc = wgp_fill(p, q, s->pool ? geo_s2(s, false) : geo_plain(s, false), {dy, s->Cout, 1.f}, {x, s->Cin, s->pre_slope}, s->Cin);
+        rc = wgp_fill(p, q, s->pool == 2 ? geo_box(s) : (s->pool ? geo_s2(s, false) : geo_plain(s, false)), {dy, s->Cout, 1.f}, {x, s->Cin, s->pre_slope}, s->Cin);
     p.slabs = slabs; p.bias_slabs = bias_slabs;
     return rc;
 }

@@ -65,6 +65,42 @@ extern "C" int gim_avgpool2_fwd_act(const float* x, float* y, int N, int H, int 
     hipLaunchKernelGGL(avgpool2_fwd_act_kernel, dim3(pw_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, y, N, H, W, C, 1.0f / in_slope);
     return gim_check_launch("gim_avgpool2_fwd_act");
 }
+// Stride-1 2x2 mean of the zero-padded, activated map: p[n][y][x][c] = 1/4 * sum_{dy,dx in {0,1}} lrelu(x)[y-1+dy][x-1+dx] on the
+// (H+1) x (W+1) grid - the operand of the pre-filtered pool convolution (gim_conv_shape.pool = 2).  One thread per 16 bytes of p:
+// four 16-byte loads (neighbouring threads share them through the cache: each element of x is read from HBM once), one store.
+typedef float pw_f32x4 __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(256) void box2_fwd_kernel(const float* __restrict__ x, float* __restrict__ p, int N, int H, int W, int C4, float slope) {
+    const int Hp = H + 1, Wp = W + 1;
+    const unsigned total = (unsigned)N * Hp * Wp * C4;
+    const pw_f32x4* __restrict__ x4 = (const pw_f32x4*)x;
+    pw_f32x4* __restrict__ p4 = (pw_f32x4*)p;
+    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+        const unsigned c = i % (unsigned)C4;
+        unsigned r = i / (unsigned)C4;
+        const int xo = (int)(r % (unsigned)Wp); r /= (unsigned)Wp;
+        const int yo = (int)(r % (unsigned)Hp);
+        const int n = (int)(r / (unsigned)Hp);
+        pw_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            const int iy = yo - 1 + (d >> 1), ix = xo - 1 + (d & 1);
+            if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
+                const pw_f32x4 v = x4[((long long)(n * H + iy) * W + ix) * C4 + c];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[e] += v[e] > 0.f ? v[e] : v[e] * slope;
+            }
+        }
+        p4[i] = acc * 0.25f;
+    }
+}
+extern "C" int gim_box2_fwd(const float* x, float* p, int N, int H, int W, int C, float slope, void* stream) {
+    GIM_CHECK_ARG(x && p && N > 0 && H >= 1 && W >= 1 && C > 0 && (C & 3) == 0 && !((uintptr_t)x & 15) && !((uintptr_t)p & 15) && slope >= 0.f && slope <= 1.f,
+                  "box2_fwd: bad args (C % 4 == 0, 16-byte aligned pointers, slope in [0, 1])");
+    const long long n = (long long)N * (H + 1) * (W + 1) * (C / 4);
+    GIM_CHECK_ARG(n < (1ll << 31) && (long long)N * H * W < (1ll << 31), "box2_fwd: more than 2^31 16-byte groups (32-bit index arithmetic): split the batch");
+    hipLaunchKernelGGL(box2_fwd_kernel, dim3(pw_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, p, N, H, W, C / 4, slope);
+    return gim_check_launch("gim_box2_fwd");
+}
 // Gradient fan-in of a tensor with several consumers, in one pass (autograd would add the incoming gradients pairwise, one
 // launch and one full read-modify-write each): out = a + b (+ c) (+ d);  and the ResBlockDown form, where the second consumer
 // is the 2x2 average pool of the skip path: out = g + avgpool2_bwd(dy_pooled) without materialising the un-pooled gradient.

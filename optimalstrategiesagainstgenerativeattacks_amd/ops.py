@@ -80,7 +80,8 @@ def mark_phase(name):
 
 class count_flops:
     """with ops.count_flops() as c: ...   ->  c[(kind, cfg)] = [launches, executed FLOPs per launch]; kinds fwd / dgrad / wgrad / bgemm;
-    cfg = (N, H, W, Cin, Cout, KH, ups, pool, fold) for convolutions and linears (H = W = KH = 1), (batch, M, N, K) for bgemm."""
+    cfg = (N, H, W, Cin, Cout, KH, ups, pool, fold) for convolutions and linears (H = W = KH = 1), (batch, M, N, K) for bgemm;
+    pool = 2: the forward / wgrad launches of a pooled 3x3 conv on the box-filtered input (9 taps; its dgrad counts under pool = 1)."""
 
     def __enter__(self):
         global _FLOPS
@@ -96,6 +97,8 @@ class count_flops:
 def conv_executed_flops(N, H, W, Cin, Cout, KH, ups, pool, fold):
     """2 * MACs one forward (= one dgrad = one wgrad) launch of this convolution executes.  (H, W) is the resolution the
     unfused conv would run at (after the nearest upsample, before the average pool)."""
+    if pool == 2:            # ONE stride-2 conv with the conv's own K^2 taps on the box-filtered input (_pool_route "box")
+        return 2.0 * N * (H >> 1) * (W >> 1) * Cin * Cout * KH * KH
     if fold and pool:        # ONE stride-2 conv, (K+1)^2 taps, on the pooled grid
         return 2.0 * N * (H >> 1) * (W >> 1) * Cin * Cout * (KH + 1) ** 2
     if fold and ups:         # 4 parity classes on the low-resolution grid, ((K+1)/2)^2 taps each
@@ -701,7 +704,12 @@ class ConvGeom(collections.namedtuple("ConvGeom", "N H W Cin Cout KH ups pre_slo
     def shape(self, kind, pre_slope=None):
         """The caller's own gim_conv_shape for a launch of `kind` ("fwd" / "dgrad" / "wgrad" of _TUNE_OVERRIDE; None: no override)."""
         return _tuned(_shape(self.N, self.H, self.W, self.Cin, self.Cout, self.KH, self.ups, self.pre_slope if pre_slope is None else pre_slope,
-                             1 if self.pool else 0, self.fold, 1 if self.res_ups else 0), kind, self.key)
+                             self.key[7], self.fold, 1 if self.res_ups else 0), kind, self.key)
+
+    def box(self):
+        """The forward / wgrad launches of this POOLED 3x3 call on the box-filtered input p [N, H+1, W+1, Cin] (gim_conv_shape.pool = 2:
+        the conv's own 9 taps, plain weight layout) - a key of its own for the plan cache, _TUNE_OVERRIDE and count_flops."""
+        return self._replace(fold=0, pre_slope=1.0, key=self.key[:7] + (2, 0))
 
     def linear_map(self):
         """The conv as a linear map of its input: no prologue, bias or residual (ConvDgradFn's adjoints)."""
@@ -714,6 +722,7 @@ _ROWS_FORM = os.environ.get("GIM_NO_ROWS_FORM") is None   # row-contiguous K for
 _MERGED_SUBPIXEL = os.environ.get("GIM_NO_MERGED_SUBPIXEL") is None   # stacked parity classes for the 9x9 64->3 layer
 _NARROW_DGRAD_T = os.environ.get("GIM_NO_NARROW_DGRAD_T") is None
 _NARROW_XFOLD = os.environ.get("GIM_NO_NARROW_XFOLD") is None
+_BOX_POOL = os.environ.get("GIM_NO_BOX_POOL") is None   # pooled 3x3 convs: forward / wgrad on the box-filtered input (9 taps, not the fold's 16)
 
 
 def _fwd_route(g, tune_tile):
@@ -727,6 +736,27 @@ def _fwd_route(g, tune_tile):
     if _MERGED_SUBPIXEL and g.ups and g.KH >= 5 and (g.KH & 3) == 1 and g.Cout <= 4 and not g.has_res:
         return "subpixel"
     return "plain"
+
+
+def _pool_route(g, prec, tune_tile=0):
+    """Forward and weight gradient of a pooled convolution: "fold" (ONE stride-2 conv over the (K+1)^2 folded taps of x) or "box" (a
+    streaming 2x2 box filter of the zero-padded activated x - gim_box2_fwd - then ONE stride-2 conv with the conv's own 9 taps:
+    9/36 instead of 16/36 of the unfused FLOPs; the weight gradient reads the saved box map).  Eligible: 3x3, gathered channels % 16
+    == 0 (16-byte loads), fp32 matrix path (`prec` 0), no launch override on the folded key (`tune_tile`).  The input gradient keeps
+    the fold on either route (its box form would need an odd-sized (H+1) x (W+1) output grid)."""
+    if not (_BOX_POOL and g.pool) or g.linear or g.ups or g.KH != 3 or g.Cin % 16 != 0 or prec != 0 or tune_tile != 0:
+        return "fold"
+    return "box"
+
+
+def _fwd_launch(g, tap_slope=None):
+    """-> (geometry, gim_conv_shape) of the forward launch of g: g.box() where _pool_route says "box", else g itself."""
+    sh = g.shape("fwd", tap_slope)
+    # (a launch override on the folded key, forward or weight gradient, asks for the folded launches)
+    if g.pool and _pool_route(g, sh.prec, sh.tune_tile or (1 if ("wgrad", g.key) in _TUNE_OVERRIDE else 0)) == "box":
+        g = g.box()
+        sh = g.shape("fwd")
+    return g, sh
 
 
 def _xfold_factor(Cin, W):
@@ -781,8 +811,8 @@ def _stores_activated(g, post_slope):
     """Does the forward of g write lrelu(y, post_slope)?  (Not a split-K launch; "subpixel" activates in its depth-to-space copy.)"""
     if not (_ACT_STORAGE and post_slope != 1.0) or g.linear:
         return False
-    sh = g.shape("fwd")
-    return _fwd_route(g, sh.tune_tile) == "subpixel" or _launch_plan(sh, 0, g.key).ksplit == 1
+    gl, sh = _fwd_launch(g)
+    return _fwd_route(g, sh.tune_tile) == "subpixel" or _launch_plan(sh, 0, gl.key).ksplit == 1
 
 
 def _merged_subpixel(x, w, ups, res, sh):
@@ -792,7 +822,8 @@ def _merged_subpixel(x, w, ups, res, sh):
 
 class ConvFn(Function):
     """y = [avgpool2]( conv(up2^ups(lrelu(x, pre_slope)), w) ) / sigma + bias + res   (NHWC; linear when x is 2-D).
-    pool: the 2x2 average pool behind the conv is folded into ONE stride-2 convolution; ups with a KxK kernel
+    pool: the 2x2 average pool behind the conv is folded into ONE stride-2 convolution (over the folded taps of x, or - _pool_route
+    "box": forward and wgrad of 3x3 layers - over the conv's own taps of the box-filtered x); ups with a KxK kernel
     (K > 1) runs in its sub-pixel form on the low-resolution input: neither pooling nor upsampling costs conv FLOPs.
     res_ups: the residual is stored at half the output resolution."""
     N_EXTRA = 11    # forward's inputs behind (x, w, bias, res): backward hands None back for each
@@ -805,11 +836,11 @@ class ConvFn(Function):
         g = ConvGeom.of(x, w, ups, pre_slope, pool, res_ups, bias, res, x_act)
         N, H, W, Cin, Cout, KH = g.N, g.H, g.W, g.Cin, g.Cout, g.KH
         tap_slope = 1.0 if x_act else pre_slope
-        sh = g.shape("fwd", tap_slope)
+        gl, sh = _fwd_launch(g, tap_slope)    # gl is not g: the pooled conv runs on the box-filtered input (_pool_route)
         route = _fwd_route(g, sh.tune_tile)
         # post_slope != 1: store lrelu(y) for the ONLY reader of y, which runs with x_act (callers ask _stores_activated; refused here otherwise)
         if post_slope != 1.0 and route != "subpixel":
-            if g.linear or _launch_plan(sh, 0, g.key).ksplit > 1:
+            if g.linear or _launch_plan(sh, 0, gl.key).ksplit > 1:
                 raise RuntimeError("conv: an activated output (post_slope) cannot be combined with a split-K launch or a linear layer")
             sh.post_slope = post_slope
         if res is not None:
@@ -833,6 +864,11 @@ class ConvFn(Function):
             check(lib.gim_conv2d_fwd(_p(x), _p(wm), None, _p(sigma), None, _p(y4), shm, _stream()), "conv2d_fwd")
             y = torch.empty(g.out_shape, device=x.device, dtype=torch.float32)
             check(lib.gim_depth_to_space2(_p(y4), _p(bias), _p(y), N, H >> 1, W >> 1, Cout, post_slope, _stream()), "depth_to_space2")
+        elif gl is not g:    # box filter (applies the LeakyReLU unless x is stored activated), then the conv's own 9 taps at stride 2
+            xp = torch.empty((N, H + 1, W + 1, Cin), device=x.device, dtype=torch.float32)
+            check(lib.gim_box2_fwd(_p(x), _p(xp), N, H, W, Cin, tap_slope, _stream()), "box2_fwd")
+            y = _conv_out(sh, 0, gl.key, g.out_shape, x.device)
+            check(lib.gim_conv2d_fwd(_p(xp), _p(wp), _p(bias), _p(sigma), _p(res), _p(y), sh, _stream()), "conv2d_fwd")
         else:
             y = _conv_out(sh, 0, g.key, g.out_shape, x.device)
             if g.fold and wf is None:
@@ -842,7 +878,7 @@ class ConvFn(Function):
         ctx.cfg = g
         ctx.guard = guard
         if _FLOPS is not None:
-            _note_conv("fwd", g, sh, 0)
+            _note_conv("fwd", gl, sh, 0)
         return y
 
     @staticmethod
@@ -855,6 +891,10 @@ class ConvFn(Function):
             raise RuntimeError("the spectral-norm state (sigma, u, v) of this forward pass was overwritten by later forward "
                                "passes of the same model: run backward before the third forward")
         need = ctx.needs_input_grad
+        box = g.pool and xp is not None     # forward on the box-filtered input xp: the weight gradient reads it, the input gradient keeps the fold
+        if g.fold and wf is None and need[0]:
+            with torch.no_grad():
+                wf = _folded(weight_phys(w), g.Cout, g.Cin, g.KH)
         if _second_order():
             if g.ups or g.res_ups:
                 raise NotImplementedError("second-order backward of an upsampling convolution is not on the R1 path")
@@ -867,7 +907,10 @@ class ConvFn(Function):
         if need[0]:
             dx = _conv_dgrad(lib, dy, x, wp, wf, sigma, g.shape("dgrad"), g, st, w, getattr(ctx, "dgrad_res", None))
         want_b = g.has_bias and need[2]
-        if need[1]:     # (x_act: the stored x is already lrelu(x): no activation on the wgrad operand)
+        if need[1] and box:
+            gb = g.box()
+            dw, db = _conv_wgrad(lib, dy, xp, w, wp, bias, sigma, u_s, v_s, gb.shape("wgrad"), gb, want_b, st)
+        elif need[1]:     # (x_act: the stored x is already lrelu(x): no activation on the wgrad operand)
             dw, db = _conv_wgrad(lib, dy, x, w, wp, bias, sigma, u_s, v_s, g.shape("wgrad", 1.0 if g.x_act else None), g, want_b, st, xp)
         elif want_b:
             db = torch.empty(g.Cout, device=dev, dtype=torch.float32)
