@@ -449,6 +449,18 @@ int gim_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const
 int gim_adam_step_scaled(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_end, const float* lr,
                          int n_seg, float beta1, float beta2, float eps, float grad_scale, int32_t* step, void* state, void* stream);
 
+/* Averaged agents: the exponential moving average of a flat parameter buffer (training/utils.py:96-101, accumulate; called by
+ * optim.FusedAdam.step behind the Adam launches): avg[i] = decay * avg[i] + (1 - decay) * p[i] in fp32, 1 - decay formed once in
+ * fp32.  0 <= decay < 1; avg and p 16-byte aligned and disjoint.  scaler_state NULL: always update.  Otherwise it is the
+ * GIM_SCALER_WORDS words of gim_adam_step_scaled (4-byte aligned), and every workgroup returns before it touches avg when word [7]
+ * is set: behind gim_adam_step_scaled on the same stream a skipped optimizer step is a skipped average step, with no host read.
+ * decay is passed by value and there is no device counter, so a captured graph replays the call as it was recorded. */
+int gim_ema_update(float* avg, const float* p, int64_t n, float decay, const void* scaler_state, void* stream);
+
+/* Swaps the contents of two disjoint 16-byte aligned buffers of n 32-bit words in one pass (optim.FusedAdam.averaged_weights: live
+ * weights <-> averages, pointers unchanged).  Moves bit patterns: NaN payloads and -0 survive; two calls are the identity. */
+int gim_buffer_exchange(float* a, float* b, int64_t n, void* stream);
+
 /* ---- Inference of the baseline authenticators (baselines/siamese/models.py:14-56,97-114, baselines/arcface/models.py:16-164,214-237
  * as authentication_eval/eval_gim_on_authentication.py:47-72,109-128 runs them: eval mode, no_grad).  Forward only. ----
  *

@@ -256,31 +256,53 @@ def get_arcface_authenticator(device, ckpt_path, args_dict):
     return Authenticator(get_arcface_au_function(arcface.to(device)), th=arcface.th)
 
 
-def _gim_authenticator_from_ckpt(device, ckpt_path, args_dict):
+def _gim_state(ckpt_path, agent, averaged):
+    """The state dict of `agent` in a GIM checkpoint; averaged: with the parameters of its "averaged" entry laid over it (the
+    spectral-norm u, v stay the live ones).  KeyError when the run kept no average of that agent."""
+    payload = torch.load(ckpt_path, map_location='cpu')
+    sd = payload[agent]
+    if averaged:
+        entry = payload.get('averaged') or {}
+        if agent not in entry:
+            raise KeyError("checkpoint %s has no averaged %s" % (ckpt_path, agent))
+        sd = dict(sd)
+        sd.update(entry[agent]['state'])
+    return sd
+
+
+def _gim_authenticator_from_ckpt(device, ckpt_path, args_dict, averaged=False):
     from .gim_img_models import get_au
     au = get_au(img_size=args_dict['img_size'], img_channels=args_dict['img_channels'], style_dim=args_dict['style_dim'])
-    au.load_state_dict(torch.load(ckpt_path, map_location='cpu')['authenticator'])
-    return get_gim_authenticator(au.to(device))
+    au.load_state_dict(_gim_state(ckpt_path, 'authenticator', averaged))
+    agent = get_gim_authenticator(au.to(device))
+    agent.model = au
+    return agent
 
 
-def _gim_impersonator_from_ckpt(device, ckpt_path, args_dict):
+def _gim_impersonator_from_ckpt(device, ckpt_path, args_dict, averaged=False):
     from .gim_img_models import get_im
     im = get_im(img_size=args_dict['img_size'], img_channels=args_dict['img_channels'], style_dim=args_dict['style_dim'],
                 use_img_att=args_dict['use_img_att'], num_env_noise_layers=args_dict['num_env_noise_layers'])
-    im.load_state_dict(torch.load(ckpt_path, map_location='cpu')['impersonator'])
-    return get_gim_impersonator(im.to(device), args_dict)
+    im.load_state_dict(_gim_state(ckpt_path, 'impersonator', averaged))
+    agent = get_gim_impersonator(im.to(device), args_dict)
+    agent.model = im
+    return agent
 
 
-def get_authenticator(device, au_type, ckpt_path, args_dict):
+def get_authenticator(device, au_type, ckpt_path, args_dict, averaged=False):
+    """averaged: the GIM authenticator on its averaged weights (checkpoint entry "averaged"); the baselines keep none."""
     makers = {'gim': _gim_authenticator_from_ckpt, 'siamese': get_siamese_authenticator, 'arcface': get_arcface_authenticator}
     if au_type not in makers:
         raise ValueError("unsupported authenticator type %r (gim | siamese | arcface)" % (au_type,))
+    if au_type == 'gim':
+        return _gim_authenticator_from_ckpt(device, ckpt_path, args_dict, averaged=averaged)
     return makers[au_type](device, ckpt_path, args_dict)
 
 
-def get_impersonator(device, im_type, ckpt_path, ds, args_dict):
+def get_impersonator(device, im_type, ckpt_path, ds, args_dict, averaged=False):
+    """averaged: the GIM impersonator on its averaged weights (checkpoint entry "averaged")."""
     if im_type == 'gim':
-        return _gim_impersonator_from_ckpt(device, ckpt_path, args_dict)
+        return _gim_impersonator_from_ckpt(device, ckpt_path, args_dict, averaged=averaged)
     if im_type == 'replay':
         return Impersonator(replay_impersonator)
     if im_type == 'rnd_src':
@@ -299,11 +321,12 @@ def get_exp_args_from_dir(outdir, ckpt_dir, specific_model=None):
 
 
 def eval_game_for_pair(device, au_type, im_type, au_outdir, im_outdir, ds, batch_size, num_workers, ckpt_dir='ckpts',
-                       specific_model=None):
+                       specific_model=None, averaged=False):
     au_ckpt_path, au_args_dict = get_exp_args_from_dir(au_outdir, ckpt_dir, specific_model=specific_model)
     im_ckpt_path, im_args_dict = get_exp_args_from_dir(im_outdir, ckpt_dir, specific_model=specific_model)
-    au_agent = get_authenticator(device=device, au_type=au_type, ckpt_path=au_ckpt_path, args_dict=au_args_dict)
-    im_agent = get_impersonator(device=device, im_type=im_type, ckpt_path=im_ckpt_path, ds=ds, args_dict=im_args_dict)
+    avg = {"averaged": True} if averaged else {}   # (passed only when asked for: the default call is what it was)
+    au_agent = get_authenticator(device=device, au_type=au_type, ckpt_path=au_ckpt_path, args_dict=au_args_dict, **avg)
+    im_agent = get_impersonator(device=device, im_type=im_type, ckpt_path=im_ckpt_path, ds=ds, args_dict=im_args_dict, **avg)
     acc, acc_on_fake, acc_on_real, auc = eval_authenticator_and_impersonator(
         device=device, ds=ds, batch_size=batch_size, num_workers=num_workers, authenticator=au_agent, impersonator=im_agent)
     return float(acc), float(acc_on_fake), float(acc_on_real), float(auc)
@@ -313,9 +336,9 @@ TABLE_COLUMNS = ('au_type', 'im_type', 'ds_root', 'gim_exp_dir', 'm', 'n', 'k', 
 
 
 def eval_authentication_task(device, ds, m, n, k, batch_size, num_workers, gim_exp_dir, csv_file_path, specific_model=None,
-                             baseline_exp_dir=None, baseline_type=None):
+                             baseline_exp_dir=None, baseline_type=None, averaged=False):
     """The result table: authenticator gim (and the baseline, if one is named) against impersonators gim, replay, rnd_src -
-    one CSV row each, in that order.  Returns the rows."""
+    one CSV row each, in that order.  Returns the rows.  averaged: the GIM agents run on their averaged weights."""
     out_dir = os.path.dirname(csv_file_path)
     if out_dir and not os.path.isdir(out_dir):
         os.makedirs(out_dir)
@@ -325,7 +348,8 @@ def eval_authentication_task(device, ds, m, n, k, batch_size, num_workers, gim_e
             print("running {} vs. {}".format(au_type, im_type))
             acc, acc_on_fake, acc_on_real, auc = eval_game_for_pair(
                 device=device, au_type=au_type, im_type=im_type, au_outdir=gim_exp_dir if au_type == 'gim' else baseline_exp_dir,
-                im_outdir=gim_exp_dir, ds=ds, batch_size=batch_size, num_workers=num_workers, specific_model=specific_model)
+                im_outdir=gim_exp_dir, ds=ds, batch_size=batch_size, num_workers=num_workers, specific_model=specific_model,
+                **({"averaged": True} if averaged else {}))
             rows.append(dict(zip(TABLE_COLUMNS, (au_type, im_type, getattr(ds, "root", ""), gim_exp_dir, m, n, k,
                                                  acc, acc_on_fake, acc_on_real, auc))))
             print({c: rows[-1][c] for c in ('au_type', 'im_type', 'acc', 'acc_on_fake', 'acc_on_real')})

@@ -28,9 +28,6 @@ struct AdamSeg {
     long long end[ADAM_MAX_SEG];
 };
 
-enum ScalerWord { SC_SCALE = 0, SC_INV_SCALE, SC_INTERVAL, SC_CLEAN, SC_OVERFLOW, SC_SKIPPED, SC_MIN_SCALE, SC_LAST_OVERFLOW };
-static_assert(SC_LAST_OVERFLOW + 1 == GIM_SCALER_WORDS, "scaler state layout (gim_hip.h)");
-
 // GUARDED: `state` = the loss scaler's words; gscale is multiplied by its 1 / scale, and a set overflow word skips the update
 template <bool GUARDED>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,

@@ -30,6 +30,10 @@ static inline int gim_check_launch(const char* what) {
     return GIM_OK;
 }
 
+// the loss scaler's device words (layout: gim_hip.h, gim_adam_step_scaled); adam.hip writes them, ema.hip reads the last one
+enum ScalerWord { SC_SCALE = 0, SC_INV_SCALE, SC_INTERVAL, SC_CLEAN, SC_OVERFLOW, SC_SKIPPED, SC_MIN_SCALE, SC_LAST_OVERFLOW };
+static_assert(SC_LAST_OVERFLOW + 1 == GIM_SCALER_WORDS, "scaler state layout (gim_hip.h)");
+
 static inline int ilog2_exact(int v) {  // returns -1 if v is not a power of two
     if (v <= 0 || (v & (v - 1))) return -1;
     int l = 0;

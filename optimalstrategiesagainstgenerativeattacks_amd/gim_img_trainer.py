@@ -11,7 +11,7 @@ Differences that do not change any result of the training loop:
     (ops.ConvDgradFn and friends); no torch operator is on that path either.
 """
 import os
-from contextlib import contextmanager
+from contextlib import ExitStack, contextmanager
 
 import torch
 import torch.nn as nn
@@ -91,8 +91,51 @@ class GimTrainerBase(nn.Module):
         with torch.no_grad():
             return self.impersonator(leaked_sample=leaked_sample, n=self.n, remove_noise_mean=self.remove_noise_mean, z=z)
 
+    # ---- averaged agents: an exponential moving average of each agent's weights, kept by its optimizer (optim.FusedAdam) ----
+    def _agents(self):
+        return (("impersonator", self.impersonator, self.impersonator_opt), ("authenticator", self.authenticator, self.authenticator_opt))
+
+    def _init_averaging(self, im_ema_decay, au_ema_decay):
+        """None = off: no buffer, no launch, no checkpoint entry.  Call after _init_checkpoints."""
+        for (_, _, opt), decay in zip(self._agents(), (im_ema_decay, au_ema_decay)):
+            if decay is not None:
+                opt.enable_averaging(decay)
+        self._averaged = _Averaged(self)
+        self.checkpoint_io.register_optional(averaged=self._averaged)
+
+    def averages(self):
+        """True when at least one agent keeps an average."""
+        return any(opt.averaging is not None for _, _, opt in self._agents())
+
+    @contextmanager
+    def averaged(self):
+        """Inside, every agent that averages runs on its averaged weights, and both agents are in eval mode: a train-mode forward
+        runs a power iteration and would move the live weight_u / weight_v from the averaged weights.  sigma is u^T W_avg v with
+        the live u, v.  The previous modes come back on exit, and the live weights bit for bit."""
+        agents = self._agents()
+        modes = [net.training for _, net, _ in agents]
+        with ExitStack() as stack:
+            for _, _, opt in agents:
+                if opt.averaging is not None:
+                    stack.enter_context(opt.averaged_weights())
+            try:
+                for _, net, _ in agents:
+                    net.eval()
+                yield self
+            finally:
+                for (_, net, _), mode in zip(agents, modes):
+                    net.train(mode)
+
     def resume_from_ckpt(self, ckpt_path):
-        self.checkpoint_io.load(ckpt_path)
+        averaged = getattr(self, "_averaged", None)
+        if averaged is not None:
+            averaged.loaded = set()
+        found = self.checkpoint_io.load(ckpt_path) != (-1, -1)
+        if averaged is not None and found:
+            # a file without the entry (or without this agent): the average starts from the loaded weights
+            for name, _, opt in self._agents():
+                if opt.averaging is not None and name not in averaged.loaded:
+                    opt.reset_average()
         print("Resuming training from iteration {}".format(self.global_step))
 
     def get_global_step(self):
@@ -126,11 +169,38 @@ class _LossScalers:
                 sc.load_state_dict(sd[name])
 
 
+class _Averaged:
+    """Checkpoint entry "averaged": {agent: {"decay": d, "state": {parameter name as in the module's state_dict: average}}} for
+    the agents that keep an average.  Absent when none does, so the file then has the reference's keys only.  Loading restores
+    the values; the decay stays the one the trainer was built with."""
+
+    def __init__(self, trainer):
+        self.agents = trainer._agents
+        self.loaded = set()   # the agents the most recent load_state_dict() restored (resume_from_ckpt resets the others)
+
+    def state_dict(self):
+        out = {}
+        for name, net, opt in self.agents():
+            if opt.averaging is not None:
+                avg = opt.average_state()
+                out[name] = {"decay": opt.averaging,
+                             "state": {k: avg[p].detach().clone() for k, p in net.named_parameters() if p in avg}}
+        return out or None
+
+    def load_state_dict(self, sd):
+        for name, net, opt in self.agents():
+            if opt.averaging is not None and name in sd:
+                params = dict(net.named_parameters())
+                opt.load_average({params[k]: v for k, v in sd[name]["state"].items()})
+                self.loaded.add(name)
+
+
 class GIMImgTrainer(GimTrainerBase):
     IM_GROUPS = ("src_encoder", "env_encoder", "env_decoder", "img2img", "img_att", "env_noise_mapper")
 
     def __init__(self, outdir, m, n, k, authenticator, impersonator, au_lr, im_lr, env_noise_mapping_lr,
-                 beta1=0., beta2=0.99, lr_milestones=(), lr_gamma=0.3, reg_param=10., remove_noise_mean=True):
+                 beta1=0., beta2=0.99, lr_milestones=(), lr_gamma=0.3, reg_param=10., remove_noise_mean=True,
+                 im_ema_decay=None, au_ema_decay=None):
         super().__init__()
         self._init_agents(m, n, k, authenticator, impersonator, reg_param, remove_noise_mean)
         betas = (beta1, beta2)
@@ -145,6 +215,7 @@ class GIMImgTrainer(GimTrainerBase):
         self._init_checkpoints(outdir)
         self.checkpoint_io.register_optional(loss_scalers=_LossScalers(authenticator_opt=self.authenticator_opt,
                                                                        impersonator_opt=self.impersonator_opt))
+        self._init_averaging(im_ema_decay, au_ema_decay)
 
     def authenticator_forward(self, fake_sample, real_sample, si_sample, grad=True):
         ops.join_lanes()

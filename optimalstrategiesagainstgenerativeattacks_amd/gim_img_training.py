@@ -291,6 +291,23 @@ def sample_and_save_imgs(device, logger, trainer, ds, ds_prefix, indices, dbg=Fa
                 save_imgs(logger=logger, img_sample=data["si_sample"].unsqueeze(0).to(device), category=cat, k="si", global_step=global_step)
 
 
+def _averages(trainer):
+    """Does the wrapped trainer keep averaged agents (GimTrainerBase.averages)?  A trainer without the notion keeps none."""
+    fn = getattr(trainer.module, "averages", None)
+    return fn is not None and fn()
+
+
+def sample_and_save_avg_imgs(device, logger, trainer, ds, ds_prefix, indices):
+    """One more image row per sampled index, k="impersonator_avg": the averaged impersonator's sample (eval mode, trainer.averaged())."""
+    with trainer.module.averaged():
+        global_step = trainer.module.get_global_step()
+        for idx in indices:
+            leaked_sample = ds[idx]["leaked_sample"].unsqueeze(0).to(device)
+            fake_sample = trainer.forward(mode='impersonator_sample', leaked_sample=leaked_sample)
+            save_imgs(logger=logger, img_sample=fake_sample, category="{} imgs_{:04}".format(ds_prefix, idx), k="impersonator_avg",
+                      global_step=global_step)
+
+
 def _world():
     return (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
 
@@ -310,9 +327,10 @@ def _batches(ds, batch_size, shuffle, num_workers, device):
     return it(), len(loader)
 
 
-def eval_step(device, trainer, ds, logger, batch_size):
+def eval_step(device, trainer, ds, logger, batch_size, category_suffix=""):
     """training/gim_img_training.py:98-154: one pass over `ds` with both agents in eval mode; per-batch statistics stay
-    on the device and are fetched once at the end."""
+    on the device and are fetched once at the end.  category_suffix: appended to the scalars' category names (the pass on the
+    averaged agents logs under "... (averaged)")."""
     keys = ("au_loss", "au_loss_on_real", "au_loss_on_fake", "au_out_on_real", "au_out_on_fake", "au_acc", "au_acc_on_real",
             "au_acc_on_fake", "im_loss")
     acc = {k_: [] for k_ in keys}
@@ -337,7 +355,7 @@ def eval_step(device, trainer, ds, logger, batch_size):
              ('eval au out', 'au out on real'), ('eval au out', 'au out on fake'), ('eval accuracy', 'dis acc'),
              ('eval accuracy', 'dis acc on real'), ('eval accuracy', 'dis acc on fake'), ('eval losses', 'gen loss'))
     for (category, k_), v in zip(names, means):
-        logger.add_scalar(category=category, k=k_, v=v, global_step=global_step)
+        logger.add_scalar(category=category + category_suffix, k=k_, v=v, global_step=global_step)
 
 
 def train_epoch(device, logger, epoch, trainer, train_ds, val_ds, train_batch_size, val_batch_size, num_workers,
@@ -346,7 +364,9 @@ def train_epoch(device, logger, epoch, trainer, train_ds, val_ds, train_batch_si
     """training/gim_img_training.py:186-354.  Same protocol and cadences; the generator step and the discriminator step of
     an iteration are issued through gim_step (overlapped on two streams) when the generator trains this iteration.  Nothing
     is fetched from the device between log points.  micro_batches = A: every iteration accumulates its gradients over A slices of
-    the rank's batch (gim_step); an iteration stays one global step, one learning-rate step and one update per optimizer."""
+    the rank's batch (gim_step); an iteration stays one global step, one learning-rate step and one update per optimizer.
+    A trainer that keeps averaged agents (im_ema_decay / au_ema_decay) adds, behind the existing calls: one image row
+    "impersonator_avg" per sampled index at save_imgs_every and a second eval pass on the averaged agents at eval_every."""
     _micro_batches(micro_batches)
     if (train_batch_size // _world()[1]) % micro_batches != 0:
         raise ValueError("a local batch of %d episodes cannot be cut into %d equal micro-batches" % (train_batch_size // _world()[1], micro_batches))
@@ -425,16 +445,25 @@ def train_epoch(device, logger, epoch, trainer, train_ds, val_ds, train_batch_si
             lg = logger if rank == 0 else None
             sample_and_save_imgs(device=device, logger=lg, trainer=trainer, ds=train_ds, ds_prefix='train', indices=train_eval_indices, dbg=dbg)
             sample_and_save_imgs(device=device, logger=lg, trainer=trainer, ds=val_ds, ds_prefix='val', indices=val_eval_indices, dbg=dbg)
+            if _averages(trainer):   # behind the train-mode samples, whose call stream and u / v effects stay as they are
+                sample_and_save_avg_imgs(device=device, logger=lg, trainer=trainer, ds=train_ds, ds_prefix='train', indices=train_eval_indices)
+                sample_and_save_avg_imgs(device=device, logger=lg, trainer=trainer, ds=val_ds, ds_prefix='val', indices=val_eval_indices)
         if global_step % eval_every == 0:
             eval_step(device=device, trainer=trainer, ds=val_ds, logger=logger, batch_size=val_batch_size)
+            if _averages(trainer):
+                with trainer.module.averaged():
+                    eval_step(device=device, trainer=trainer, ds=val_ds, logger=logger, batch_size=val_batch_size,
+                              category_suffix=" (averaged)")
     ops.join_lanes()
 
 
 def train_gim_imgs(device_name, device_ids, outdir, train_ds, val_ds, authenticator, impersonator, m, n, k,
                    reg_param, remove_noise_mean, au_lr, im_lr, beta1, beta2, env_noise_mapping_lr, lr_gamma, milestones,
                    resume_from_ckpt, n_epochs, batch_size, num_workers, save_every, eval_every, save_imgs_every,
-                   train_eval_indices, val_eval_indices, n_au_steps=1, dbg=False, micro_batches=1):
-    """training/gim_img_training.py:356-441.  micro_batches: see train_epoch.  `device_ids` keeps its meaning as "the GPUs of the job": with more than one,
+                   train_eval_indices, val_eval_indices, n_au_steps=1, dbg=False, micro_batches=1,
+                   im_ema_decay=None, au_ema_decay=None):
+    """training/gim_img_training.py:356-441.  micro_batches: see train_epoch.  im_ema_decay / au_ema_decay: keep an exponential moving
+    average of the impersonator's / authenticator's weights (GIMImgTrainer; None = off).  `device_ids` keeps its meaning as "the GPUs of the job": with more than one,
     launch one process per GPU (torchrun) - each process builds the same trainer, takes its slice of every global batch
     and the two optimizers all-reduce their gradient buckets over RCCL (EpisodeParallel replaces nn.DataParallel)."""
     from .gim_img_trainer import GIMImgTrainer
@@ -455,7 +484,7 @@ def train_gim_imgs(device_name, device_ids, outdir, train_ds, val_ds, authentica
     trainer = GIMImgTrainer(outdir=outdir, m=m, n=n, k=k, authenticator=authenticator, impersonator=impersonator,
                             au_lr=au_lr, im_lr=im_lr, env_noise_mapping_lr=env_noise_mapping_lr, beta1=beta1, beta2=beta2,
                             lr_milestones=milestones, lr_gamma=lr_gamma, reg_param=reg_param,
-                            remove_noise_mean=remove_noise_mean).to(device)
+                            remove_noise_mean=remove_noise_mean, im_ema_decay=im_ema_decay, au_ema_decay=au_ema_decay).to(device)
     if resume_from_ckpt:
         trainer.resume_from_ckpt(ckpt_path=resume_from_ckpt)
         trainer.to(device)

@@ -13,7 +13,9 @@ Replaces the two ``torch.optim.Adam`` instances of the reference trainer
 ``state_dict()`` / ``load_state_dict()`` keep torch.optim.Adam's format (per-parameter ``step`` /
 ``exp_avg`` / ``exp_avg_sq``; group keys lr, betas, eps, weight_decay, amsgrad), so reference checkpoints load.
 """
+import math
 import os
+from contextlib import contextmanager
 
 import torch
 import torch.distributed as dist
@@ -125,6 +127,10 @@ class FusedAdam(torch.optim.Optimizer):
         self.grad_divisor = None  # set by dp: world size for the post-all-reduce average
         self.loss_scaler = None        # a LossScaler: step() tests the bucket, skips on inf / NaN and un-scales by the DEVICE scale
         self.allreduce_timing = None   # a list: step() appends the (before, after) events of its gradient all-reduce (bench.py)
+        self._avg_decay = None         # averaged agent (enable_averaging): the decay; flat_avg exists from the build on
+        self.flat_avg = None
+        self._avg_carry = None         # {parameter: average} waiting for the next (re)build of the flat buffers
+        self._swapped = False          # inside averaged_weights(): flat_p holds the averages
 
     def dynamic_scaler(self):
         """The LossScaler the step functions use (created on first use from ops.set_loss_scale's settings), or None when the loss
@@ -179,6 +185,8 @@ class FusedAdam(torch.optim.Optimizer):
         self._step_dev = torch.full((1,), self._host_step, dtype=torch.int32, device=dev)
         self._built = True
         self._publish_state()
+        if self._avg_decay is not None:
+            self._alloc_average()
 
     def _publish_state(self):
         """Expose the flat moments through ``self.state`` in torch.optim.Adam's per-parameter format."""
@@ -196,6 +204,8 @@ class FusedAdam(torch.optim.Optimizer):
         for p, (o, n) in self._offsets.items():
             if p.data_ptr() != self.flat_p.data_ptr() + 4 * o:  # e.g. module.to() / load after build
                 self._sync_host_step()
+                if self.flat_avg is not None:   # the averages move with their parameters, as the moments do through self.state
+                    self._avg_carry = self._average_views()
                 self._built = False
                 self._build()
                 return
@@ -219,6 +229,7 @@ class FusedAdam(torch.optim.Optimizer):
 
     # ------------------------------------------------------------------ optimizer protocol
     def zero_grad(self, set_to_none=False):
+        self._not_swapped("zero_grad()")
         self._ensure()
         from . import ops
         ops.reset_wgrad_queues()
@@ -246,6 +257,7 @@ class FusedAdam(torch.optim.Optimizer):
         gim_img_training: A backward passes since zero_grad()); the kernel's scale takes the 1 / A of their mean as it takes the
         1 / world_size, so N ranks x A micro-batches are scaled by 1 / (N A) and all-reduced once."""
         assert closure is None
+        self._not_swapped("step()")
         if micro_batches != 1:
             grad_scale = grad_scale / micro_batches
         lib = _lib.load()
@@ -263,6 +275,12 @@ class FusedAdam(torch.optim.Optimizer):
             check(lib.gim_adam_step_scaled(*args, self.loss_scaler.words.data_ptr(), torch.cuda.current_stream().cuda_stream), "adam_step_scaled")
         else:
             check(lib.gim_adam_step(*args, torch.cuda.current_stream().cuda_stream), "adam_step")
+        if self._avg_decay is not None:
+            # one update per step(), behind the Adam launches on the same stream; with a loss scaler the kernel reads the scaler's
+            # "last call skipped" word (scaler_update_kernel has just written it): a skipped step leaves the average alone
+            check(lib.gim_ema_update(self.flat_avg.data_ptr(), self.flat_p.data_ptr(), self.flat_p.numel(), self._avg_decay,
+                                     self.loss_scaler.words.data_ptr() if self.loss_scaler is not None else None,
+                                     torch.cuda.current_stream().cuda_stream), "ema_update")
         self.note_steps(1)
 
     def note_steps(self, k):
@@ -271,6 +289,93 @@ class FusedAdam(torch.optim.Optimizer):
         self._host_step += k
         for p in self._offsets:
             p._gim_epoch = getattr(p, "_gim_epoch", 0) + k
+
+    def _bump_epochs(self):
+        """Every cached copy of every parameter goes stale (ops._WT_CACHE keys on weights_epoch); Adam's step count stays."""
+        for p in self._offsets:
+            p._gim_epoch = getattr(p, "_gim_epoch", 0) + 1
+
+    # ------------------------------------------------------------------ averaged agent
+    # flat_avg = decay * flat_avg + (1 - decay) * flat_p after every applied step (training/utils.py:96-101, accumulate), in the
+    # layout of flat_p (padding zeros, which both kernels keep).  It starts as a copy of the weights, so there is no bias to correct.
+    @property
+    def averaging(self):
+        """The decay of the weight average, or None when averaging is off."""
+        return self._avg_decay
+
+    def enable_averaging(self, decay):
+        d = float(decay)
+        d32 = torch.tensor(d, dtype=torch.float32).item() if not math.isnan(d) else d   # what the kernel is given
+        if not (0.0 <= d32 < 1.0):
+            raise ValueError("enable_averaging: decay must be in [0, 1) as a float32, got %r" % (decay,))
+        self._avg_decay = d
+        if self._built and self.flat_avg is None:
+            self._alloc_average()
+
+    def disable_averaging(self):
+        self._not_swapped("disable_averaging()")
+        self._avg_decay = self.flat_avg = self._avg_carry = None
+
+    def _alloc_average(self):
+        carry, self._avg_carry = self._avg_carry or {}, None
+        self.flat_avg = self.flat_p.clone()
+        with torch.no_grad():
+            for p, (o, n) in self._offsets.items():
+                if p in carry:
+                    _view_like(self.flat_avg[o:o + n], p).copy_(carry[p])
+
+    def _average_views(self):
+        return {p: _view_like(self.flat_avg[o:o + n], p) for p, (o, n) in self._offsets.items()}
+
+    def _averaging_ready(self, what):
+        if self._avg_decay is None:
+            raise RuntimeError("FusedAdam.%s: averaging is off (enable_averaging)" % what)
+        self._not_swapped(what)
+        self._ensure()
+
+    def _not_swapped(self, what):
+        if self._swapped:
+            raise RuntimeError("FusedAdam.%s inside averaged_weights(): the parameters hold the averages" % what)
+
+    def average_state(self):
+        """{parameter: its average}, views of the flat buffer in each parameter's logical shape."""
+        self._averaging_ready("average_state()")
+        return self._average_views()
+
+    @torch.no_grad()
+    def load_average(self, mapping):
+        """Copy averages in: {parameter: tensor of its shape}; parameters the mapping does not have keep theirs."""
+        self._averaging_ready("load_average()")
+        views = self._average_views()
+        for p, t in mapping.items():
+            views[p].copy_(t)
+
+    @torch.no_grad()
+    def reset_average(self):
+        """average = weights, as at enable_averaging."""
+        self._averaging_ready("reset_average()")
+        self.flat_avg.copy_(self.flat_p)
+
+    def _exchange(self):
+        check(_lib.load().gim_buffer_exchange(self.flat_p.data_ptr(), self.flat_avg.data_ptr(), self.flat_p.numel(),
+                                              torch.cuda.current_stream().cuda_stream), "buffer_exchange")
+        self._bump_epochs()
+
+    @contextmanager
+    def averaged_weights(self):
+        """Inside, every parameter holds its average: flat_p and flat_avg trade contents (one kernel, no pointer moves, so
+        _ensure() sees nothing) and every cached weight copy goes stale; the exit trades them back, also when the body raises.
+        step() and zero_grad() raise inside, and so does a second averaged_weights()."""
+        from . import ops
+        self._averaging_ready("averaged_weights()")
+        ops.join_lanes()   # a discriminator step still running on lane 1 (gim_step(defer_join=True)) writes these weights
+        self._exchange()
+        self._swapped = True
+        try:
+            yield self
+        finally:
+            self._exchange()
+            self._swapped = False
 
     # ------------------------------------------------------------------ checkpoint format
     def state_dict(self):
