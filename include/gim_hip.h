@@ -457,6 +457,21 @@ int gim_adam_step_scaled(float* p, const float* g, float* m, float* v, int64_t n
  * decay is passed by value and there is no device counter, so a captured graph replays the call as it was recorded. */
 int gim_ema_update(float* avg, const float* p, int64_t n, float decay, const void* scaler_state, void* stream);
 
+/* Optimistic Adam (Daskalakis et al., "Training GANs with Optimism", Algorithm 1; called by optim.FusedAdam.step behind the Adam
+ * launches and in front of gim_ema_update): the correction that turns Adam's step along d_t into a step along
+ * d_t + omega (d_t - d_{t-1}).  With t = step[0], the counter AFTER Adam advanced it, bc1 = 1 - beta1^t and bc2s = sqrt(1 - beta2^t)
+ * (formed in double, rounded to float, as gim_adam_step forms them), in fp32 per element:
+ *   d = (m[i] / bc1) / (sqrt(v[i]) / bc2s + eps);   p[i] -= (lr[segment of i] * omega) * (d - prev[i]);   prev[i] = d
+ * m and v are the moments gim_adam_step has just written, seg_end / lr / n_seg its segment table (1..16 segments; the ends need not
+ * be multiples of 4).  0 <= omega <= 1; omega == 0 records only: prev = d, p is neither read nor written.  p, prev, m, v 16-byte
+ * aligned, prev disjoint from the other three; step and scaler_state 4-byte aligned.  scaler_state NULL: always run.  Otherwise it
+ * is the GIM_SCALER_WORDS words of gim_adam_step_scaled, and every workgroup returns before it touches p or prev when word [7] is
+ * set: a skipped optimizer step is a skipped correction, with no host read.  Every workgroup also returns while step[0] < 1 (no
+ * applied step, no direction).  omega is passed by value and everything else is read on the device, so a captured graph replays it. */
+int gim_adam_optimism(float* p, float* prev, const float* m, const float* v, int64_t n, const int64_t* seg_end, const float* lr,
+                      int n_seg, float beta1, float beta2, float eps, float omega, const int32_t* step, const void* scaler_state,
+                      void* stream);
+
 /* Swaps the contents of two disjoint 16-byte aligned buffers of n 32-bit words in one pass (optim.FusedAdam.averaged_weights: live
  * weights <-> averages, pointers unchanged).  Moves bit patterns: NaN payloads and -0 survive; two calls are the identity. */
 int gim_buffer_exchange(float* a, float* b, int64_t n, void* stream);

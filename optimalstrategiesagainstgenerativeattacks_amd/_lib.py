@@ -121,6 +121,7 @@ SIGNATURES = {
     "gim_adam_step_scaled": [P, P, P, P, c_int64, P, P, c_int, c_float, c_float, c_float, c_float, P, P, P],
     "gim_ema_update": [P, P, c_int64, c_float, P, P],
     "gim_buffer_exchange": [P, P, c_int64, P],
+    "gim_adam_optimism": [P, P, P, P, c_int64, P, P, c_int, c_float, c_float, c_float, c_float, P, P, P],
     "gim_spin": [c_int, P],
     "gim_pad_image": [P, P, c_int, c_int, c_int, c_int, c_int, c_float, P],
     "gim_conv2d_pack_rows_weights": [P, P, c_int, c_int, c_int, P],

@@ -74,6 +74,18 @@ static inline int blocks256(long long n) {
     return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
 }
 
+// the streaming passes over flat optimizer buffers (ema.hip, oadam.hip) launch adam.hip's grid: one pass of it covers 4096 * 256 * 4 floats
+static inline long long stream_blocks(long long n) {
+    long long blocks = (n + 1023) / 1024;
+    return blocks > 4096 ? 4096 : blocks;
+}
+
+// byte ranges [a, a + 4n) and [b, b + 4n) share an element (a == b included)
+static inline bool ranges_overlap(const void* a, const void* b, int64_t n) {
+    const uintptr_t ua = (uintptr_t)a, ub = (uintptr_t)b, len = (uintptr_t)n * 4;
+    return ua < ub + len && ub < ua + len;
+}
+
 // conv_tiny.hip: direct convolution of the 3 -> 3 / 1 -> 1 image layers (3x3, 9x9; plain geometry): one workgroup per
 // GIM_TINY_TILE x GIM_TINY_TILE output tile of one image.  gim_tiny_shape is the eligibility test and gim_tiny_grid the launch grid
 // of all three directions (the planners in conv_igemm.hip report them); the launchers run eligible shapes only.

@@ -8,17 +8,6 @@
 //   gim_buffer_exchange: a <-> b as bit patterns (uint4), so NaN payloads and -0 survive; twice is the identity.
 #include "common.h"
 
-static inline long long stream_blocks(long long n) {   // adam.hip's grid: one pass of the grid covers 4096 * 256 * 4 floats
-    long long blocks = (n + 1023) / 1024;
-    return blocks > 4096 ? 4096 : blocks;
-}
-
-// byte ranges [a, a + 4n) and [b, b + 4n) share an element (a == b included)
-static inline bool ranges_overlap(const void* a, const void* b, int64_t n) {
-    const uintptr_t ua = (uintptr_t)a, ub = (uintptr_t)b, len = (uintptr_t)n * 4;
-    return ua < ub + len && ub < ua + len;
-}
-
 // GUARDED: `state` = the loss scaler's words after scaler_update_kernel; the read is uniform, one scalar load per wave
 template <bool GUARDED>
 __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ avg, const float* __restrict__ p, long long n, float decay,

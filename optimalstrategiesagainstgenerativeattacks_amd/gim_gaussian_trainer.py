@@ -7,13 +7,14 @@ from .optim import FusedAdam
 
 class GIMGaussianTrainer(GimTrainerBase):
     def __init__(self, outdir, m, n, k, authenticator, impersonator, au_lr, im_lr, reg_param=0., remove_noise_mean=True,
-                 im_ema_decay=None, au_ema_decay=None):
+                 im_optimism=None, au_optimism=None, im_ema_decay=None, au_ema_decay=None):
         super().__init__()
         self._init_agents(m, n, k, authenticator, impersonator, reg_param, remove_noise_mean)
         self.authenticator_opt = FusedAdam(self.authenticator.parameters(), lr=au_lr)
         self.impersonator_opt = FusedAdam(self.impersonator.parameters(), lr=im_lr)
         self._init_checkpoints(outdir)
         self._init_averaging(im_ema_decay, au_ema_decay)
+        self._init_optimism(im_optimism, au_optimism)
 
     def authenticator_forward(self, fake_sample, real_sample, si_sample, grad=True):
         self._wants_input_grad(real_sample, si_sample)

@@ -126,11 +126,28 @@ class GimTrainerBase(nn.Module):
                 for (_, net, _), mode in zip(agents, modes):
                     net.train(mode)
 
+    # ---- optimistic updates: each optimizer steps along d_t + omega (d_t - d_{t-1}) (optim.FusedAdam.enable_optimism) ----
+    def _init_optimism(self, im_optimism, au_optimism):
+        """None = off: no buffer, no launch, no checkpoint entry.  Call after _init_checkpoints."""
+        for (_, _, opt), omega in zip(self._agents(), (im_optimism, au_optimism)):
+            if omega is not None:
+                opt.enable_optimism(omega)
+        self._optimism = _Optimism(self)
+        self.checkpoint_io.register_optional(optimism=self._optimism)
+
     def resume_from_ckpt(self, ckpt_path):
-        averaged = getattr(self, "_averaged", None)
+        averaged, optimism = getattr(self, "_averaged", None), getattr(self, "_optimism", None)
         if averaged is not None:
             averaged.loaded = set()
+        if optimism is not None:
+            optimism.loaded = set()
         found = self.checkpoint_io.load(ckpt_path) != (-1, -1)
+        if optimism is not None and found:
+            # a file without the entry (or without this agent): the previous direction is the one of the loaded Adam state, so the
+            # first step after resuming is a plain Adam step, not a doubled one
+            for name, _, opt in self._agents():
+                if opt.optimism is not None and name not in optimism.loaded:
+                    opt.prime_optimism()
         if averaged is not None and found:
             # a file without the entry (or without this agent): the average starts from the loaded weights
             for name, _, opt in self._agents():
@@ -195,12 +212,38 @@ class _Averaged:
                 self.loaded.add(name)
 
 
+class _Optimism:
+    """Checkpoint entry "optimism": {agent: {"omega": w, "state": {parameter name as in the module's state_dict: previous direction}}}
+    for the agents that step optimistically.  Absent when none does, so the file then has the reference's keys only.  Loading
+    restores the directions; omega stays the one the trainer was built with."""
+
+    def __init__(self, trainer):
+        self.agents = trainer._agents
+        self.loaded = set()   # the agents the most recent load_state_dict() restored (resume_from_ckpt primes the others)
+
+    def state_dict(self):
+        out = {}
+        for name, net, opt in self.agents():
+            if opt.optimism is not None:
+                prev = opt.optimism_state()
+                out[name] = {"omega": opt.optimism,
+                             "state": {k: prev[p].detach().clone() for k, p in net.named_parameters() if p in prev}}
+        return out or None
+
+    def load_state_dict(self, sd):
+        for name, net, opt in self.agents():
+            if opt.optimism is not None and name in sd:
+                params = dict(net.named_parameters())
+                opt.load_optimism({params[k]: v for k, v in sd[name]["state"].items()})
+                self.loaded.add(name)
+
+
 class GIMImgTrainer(GimTrainerBase):
     IM_GROUPS = ("src_encoder", "env_encoder", "env_decoder", "img2img", "img_att", "env_noise_mapper")
 
     def __init__(self, outdir, m, n, k, authenticator, impersonator, au_lr, im_lr, env_noise_mapping_lr,
                  beta1=0., beta2=0.99, lr_milestones=(), lr_gamma=0.3, reg_param=10., remove_noise_mean=True,
-                 im_ema_decay=None, au_ema_decay=None):
+                 im_optimism=None, au_optimism=None, im_ema_decay=None, au_ema_decay=None):
         super().__init__()
         self._init_agents(m, n, k, authenticator, impersonator, reg_param, remove_noise_mean)
         betas = (beta1, beta2)
@@ -216,6 +259,7 @@ class GIMImgTrainer(GimTrainerBase):
         self.checkpoint_io.register_optional(loss_scalers=_LossScalers(authenticator_opt=self.authenticator_opt,
                                                                        impersonator_opt=self.impersonator_opt))
         self._init_averaging(im_ema_decay, au_ema_decay)
+        self._init_optimism(im_optimism, au_optimism)
 
     def authenticator_forward(self, fake_sample, real_sample, si_sample, grad=True):
         ops.join_lanes()

@@ -461,9 +461,10 @@ def train_gim_imgs(device_name, device_ids, outdir, train_ds, val_ds, authentica
                    reg_param, remove_noise_mean, au_lr, im_lr, beta1, beta2, env_noise_mapping_lr, lr_gamma, milestones,
                    resume_from_ckpt, n_epochs, batch_size, num_workers, save_every, eval_every, save_imgs_every,
                    train_eval_indices, val_eval_indices, n_au_steps=1, dbg=False, micro_batches=1,
-                   im_ema_decay=None, au_ema_decay=None):
+                   im_optimism=None, au_optimism=None, im_ema_decay=None, au_ema_decay=None):
     """training/gim_img_training.py:356-441.  micro_batches: see train_epoch.  im_ema_decay / au_ema_decay: keep an exponential moving
-    average of the impersonator's / authenticator's weights (GIMImgTrainer; None = off).  `device_ids` keeps its meaning as "the GPUs of the job": with more than one,
+    average of the impersonator's / authenticator's weights (GIMImgTrainer; None = off).  im_optimism / au_optimism: omega in (0, 1] of
+    the optimistic Adam step of the impersonator / authenticator (GIMImgTrainer; None = off).  `device_ids` keeps its meaning as "the GPUs of the job": with more than one,
     launch one process per GPU (torchrun) - each process builds the same trainer, takes its slice of every global batch
     and the two optimizers all-reduce their gradient buckets over RCCL (EpisodeParallel replaces nn.DataParallel)."""
     from .gim_img_trainer import GIMImgTrainer
@@ -484,7 +485,8 @@ def train_gim_imgs(device_name, device_ids, outdir, train_ds, val_ds, authentica
     trainer = GIMImgTrainer(outdir=outdir, m=m, n=n, k=k, authenticator=authenticator, impersonator=impersonator,
                             au_lr=au_lr, im_lr=im_lr, env_noise_mapping_lr=env_noise_mapping_lr, beta1=beta1, beta2=beta2,
                             lr_milestones=milestones, lr_gamma=lr_gamma, reg_param=reg_param,
-                            remove_noise_mean=remove_noise_mean, im_ema_decay=im_ema_decay, au_ema_decay=au_ema_decay).to(device)
+                            remove_noise_mean=remove_noise_mean, im_ema_decay=im_ema_decay, au_ema_decay=au_ema_decay,
+                            im_optimism=im_optimism, au_optimism=au_optimism).to(device)
     if resume_from_ckpt:
         trainer.resume_from_ckpt(ckpt_path=resume_from_ckpt)
         trainer.to(device)

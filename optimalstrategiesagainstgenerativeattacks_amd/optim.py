@@ -131,6 +131,9 @@ class FusedAdam(torch.optim.Optimizer):
         self.flat_avg = None
         self._avg_carry = None         # {parameter: average} waiting for the next (re)build of the flat buffers
         self._swapped = False          # inside averaged_weights(): flat_p holds the averages
+        self._omega = None             # optimistic step (enable_optimism): omega; flat_prev exists from the build on
+        self.flat_prev = None
+        self._prev_carry = None        # {parameter: previous direction} waiting for the next (re)build of the flat buffers
 
     def dynamic_scaler(self):
         """The LossScaler the step functions use (created on first use from ops.set_loss_scale's settings), or None when the loss
@@ -182,11 +185,14 @@ class FusedAdam(torch.optim.Optimizer):
                 seg_end.append(o)
         self._seg_end = torch.tensor(seg_end, dtype=torch.int64, device=dev)
         self._lr_dev = torch.zeros(len(seg_end), dtype=torch.float32, device=dev)
+        self._lr_cache = None   # a rebuild after the first step: the new table is zeros until _push_lrs fills it
         self._step_dev = torch.full((1,), self._host_step, dtype=torch.int32, device=dev)
         self._built = True
         self._publish_state()
         if self._avg_decay is not None:
             self._alloc_average()
+        if self._omega is not None:
+            self._alloc_prev()
 
     def _publish_state(self):
         """Expose the flat moments through ``self.state`` in torch.optim.Adam's per-parameter format."""
@@ -206,6 +212,8 @@ class FusedAdam(torch.optim.Optimizer):
                 self._sync_host_step()
                 if self.flat_avg is not None:   # the averages move with their parameters, as the moments do through self.state
                     self._avg_carry = self._average_views()
+                if self.flat_prev is not None:  # and so do the previous directions: a rebuild never zeroes them
+                    self._prev_carry = self._prev_views()
                 self._built = False
                 self._build()
                 return
@@ -275,6 +283,9 @@ class FusedAdam(torch.optim.Optimizer):
             check(lib.gim_adam_step_scaled(*args, self.loss_scaler.words.data_ptr(), torch.cuda.current_stream().cuda_stream), "adam_step_scaled")
         else:
             check(lib.gim_adam_step(*args, torch.cuda.current_stream().cuda_stream), "adam_step")
+        if self._omega is not None:
+            # one correction per step(), behind the Adam launches and in front of the average, which must see the corrected weights
+            self._launch_optimism(self._omega)
         if self._avg_decay is not None:
             # one update per step(), behind the Adam launches on the same stream; with a loss scaler the kernel reads the scaler's
             # "last call skipped" word (scaler_update_kernel has just written it): a skipped step leaves the average alone
@@ -376,6 +387,81 @@ class FusedAdam(torch.optim.Optimizer):
         finally:
             self._exchange()
             self._swapped = False
+
+    # ------------------------------------------------------------------ optimistic step
+    # Optimistic Adam (Daskalakis et al., "Training GANs with Optimism", Algorithm 1): the step along d_t + omega (d_t - d_{t-1}), d_t =
+    # Adam's bias-corrected direction.  flat_prev holds d_{t-1} in the layout of flat_p; it starts as zeros, so with omega = 1 the
+    # first step is 2 lr d_1, as in the paper.  One streaming kernel behind Adam (csrc/oadam.hip), which also keeps d_t.
+    @property
+    def optimism(self):
+        """omega of the optimistic step, or None when it is off."""
+        return self._omega
+
+    def enable_optimism(self, omega):
+        self._not_swapped("enable_optimism()")
+        w = float(omega)
+        w32 = torch.tensor(w, dtype=torch.float32).item() if not math.isnan(w) else w   # what the kernel is given
+        if not (0.0 < w32 <= 1.0):
+            raise ValueError("enable_optimism: omega must be in (0, 1] as a float32, got %r" % (omega,))
+        self._omega = w
+        if self._built and self.flat_prev is None:
+            self._alloc_prev()
+
+    def disable_optimism(self):
+        self._not_swapped("disable_optimism()")
+        self._omega = self.flat_prev = self._prev_carry = None
+
+    def _alloc_prev(self):
+        carry, self._prev_carry = self._prev_carry or {}, None
+        self.flat_prev = torch.zeros_like(self.flat_p)
+        with torch.no_grad():
+            for p, (o, n) in self._offsets.items():
+                if p in carry:
+                    _view_like(self.flat_prev[o:o + n], p).copy_(carry[p])
+
+    def _prev_views(self):
+        return {p: _view_like(self.flat_prev[o:o + n], p) for p, (o, n) in self._offsets.items()}
+
+    def _optimism_ready(self, what):
+        if self._omega is None:
+            raise RuntimeError("FusedAdam.%s: the optimistic step is off (enable_optimism)" % what)
+        self._not_swapped(what)
+        self._ensure()
+
+    def _launch_optimism(self, omega, guarded=True):
+        """gim_adam_optimism on the current stream; omega = 0 only records the direction.  The kernel reads the step counter and the
+        learning rates on the device and, when guarded behind a loss scaler, the scaler's "last call skipped" word."""
+        g0 = self.param_groups[0]
+        scaler = self.loss_scaler if guarded else None
+        check(_lib.load().gim_adam_optimism(
+            self.flat_p.data_ptr(), self.flat_prev.data_ptr(), self.flat_m.data_ptr(), self.flat_v.data_ptr(), self.flat_p.numel(),
+            self._seg_end.data_ptr(), self._lr_dev.data_ptr(), len(self.param_groups), g0["betas"][0], g0["betas"][1], g0["eps"],
+            omega, self._step_dev.data_ptr(), scaler.words.data_ptr() if scaler is not None else None,
+            torch.cuda.current_stream().cuda_stream), "adam_optimism")
+
+    def optimism_state(self):
+        """{parameter: the direction d of its last applied step}, views of the flat buffer in each parameter's logical shape."""
+        self._optimism_ready("optimism_state()")
+        return self._prev_views()
+
+    @torch.no_grad()
+    def load_optimism(self, mapping):
+        """Copy previous directions in: {parameter: tensor of its shape}; parameters the mapping does not have keep theirs."""
+        self._optimism_ready("load_optimism()")
+        views = self._prev_views()
+        for p, t in mapping.items():
+            views[p].copy_(t)
+
+    @torch.no_grad()
+    def prime_optimism(self):
+        """prev = Adam's direction from the current moments and step count, the parameters untouched: after loading an Adam state
+        that came without directions, the next step is then a plain Adam step up to the change of direction, not a doubled one.
+        Nothing to record while no step has been applied."""
+        self._optimism_ready("prime_optimism()")
+        self._sync_host_step()
+        if self._host_step == 0:
+            return
+        self._launch_optimism(0.0, guarded=False)   # whatever became of the last step before the state was saved
 
     # ------------------------------------------------------------------ checkpoint format
     def state_dict(self):
